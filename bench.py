@@ -19,10 +19,15 @@ not share one (GPU_MAX_HW_QUEUES, below).  Total work per step is one frame
 whatever N is ("scaling": "strong").
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C4]
-                    [--precision fast|exact] [--no-cpu-baseline]
+                    [--precision fast|exact] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] ...]
 
 Prints ONE JSON line (rank 0).  `value` = frame pixels x K / max-over-ranks
-wall time of the K timed steps, in Mpixels/s.  `roofline` is the render
+wall time of the K timed steps, in Mpixels/s; `ms_per_step` is that wall time
+per timed step.  A plain run does only this: it sets up, warms up, times the
+K steps, writes the last timed frame if --dump-outputs is given, and prints
+the line (the objects below are null).  Everything else is measured with
+--full.  `roofline` is the render
 kernel's executed FP32 rate (the hardware flop count of the committed PMC
 summary, profiles/pmc_<cfg>_<prec>.json) over the kernel's average duration
 measured with HIP events on the launch stream, against the 157.3 TFLOP/s FP32
@@ -116,6 +121,18 @@ def parse():
     ap.add_argument("--driver", default="native", choices=["native", "python"],
                     help="frame loop: native = sdf_driver_* (C++, RCCL called directly); "
                          "python = multigpu.FrameDriver over torch.distributed")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the render "
+                         "kernel's own duration and roofline, the RGBA8 framebuffer, the other "
+                         "precision, the committed and the same-run parity, the CPU baseline; "
+                         "N>1: the frames without the gather and the assembled frame against "
+                         "a single-device render (the --no-* options below leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed frame (rank 0's "
+                         "assembled frame) as float32 DIR/frame.npy [H, W, C]; a frame over "
+                         "48 MB as DIR/frame_sample.npy [n, C], the pixels at the flat indices "
+                         "y * W + x of DIR/frame_sample_index.npy (float64; a fixed seeded "
+                         "sample, the same for every run of the same frame size)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-exact", "--no-other", action="store_true",
                     help="N=1: skip the sub-object of the other precision (`fast` beside "
@@ -343,8 +360,32 @@ def same_run_parity(gpu_frame, ref, ys, precision):
                     "cpu_baseline (same scene, camera, size), compared after the timed region"}
 
 
+DUMP_WHOLE_BYTES = 48 << 20       # a larger frame is dumped as a pixel sample
+DUMP_SAMPLE_PIXELS = 1 << 21      # 2 Mi pixels: 32 MiB of RGBA32F + 16 MiB of indices
+DUMP_SEED = 20240607
+
+
+def dump_outputs(dirname, frame):
+    """Write what the timed path computed in its last step -- `frame`, the
+    [H, W, C] tensor a caller of the frame driver reads back -- as float32
+    .npy files under `dirname`, at most 64 MB in all."""
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    a = np.ascontiguousarray(frame.float().cpu().numpy(), dtype=np.float32)
+    if a.nbytes <= DUMP_WHOLE_BYTES:
+        np.save(out / "frame.npy", a)
+        return {"frame": list(a.shape)}
+    h, w, c = a.shape
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, DUMP_SAMPLE_PIXELS,
+                                                          replace=False))
+    np.save(out / "frame_sample.npy", a.reshape(h * w, c)[idx])
+    np.save(out / "frame_sample_index.npy", idx.astype(np.float64))
+    return {"frame_sample": [len(idx), c], "frame_sample_index": [len(idx)]}
+
+
 def main():
     args = parse()
+    full = args.full
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -552,7 +593,7 @@ def main():
         torch.cuda.synchronize(dev)
         return sum(a.elapsed_time(b) for a, b in kev) / len(kev)
 
-    kavg_ms = kernel_avg_ms(fk)
+    kavg_ms = kernel_avg_ms(fk) if full else None
     log(f"[bench] rank {rank}/{world} {args.config} {W}x{H} rows={rows} "
         f"precision={args.precision} warmup={args.warmup} steps={args.steps}")
     elapsed, kernel_ms, drv = timed_run(frame, args.steps, args.warmup)
@@ -561,7 +602,7 @@ def main():
     # the same workload written as the reference window's RGBA8 framebuffer:
     # 4 B/pixel on the gather wire instead of 12 (reported beside `value`)
     display = None
-    if args.format == "rgba32f" and not args.no_display:
+    if full and args.format == "rgba32f" and not args.no_display:
         fr8 = frame.copy()
         fr8.params.output_format = abi.FORMAT_RGBA8
         el8, km8, _ = timed_run(fr8, args.steps, args.warmup)
@@ -579,7 +620,7 @@ def main():
     # few branch flips, profiles/parity_fullsize.json) is this sub-object
     other, drv_other = None, None
     other_name = "fast" if prec == abi.PRECISION_EXACT else "exact"
-    if world == 1 and not args.no_exact:
+    if full and world == 1 and not args.no_exact:
         fe = frame.copy()
         fe.params.precision = (abi.PRECISION_FAST if prec == abi.PRECISION_EXACT
                                else abi.PRECISION_EXACT)
@@ -599,7 +640,7 @@ def main():
     # the same frames without the gather (scaling with and
     # without it): each rank renders its blocks only, max over ranks
     no_gather = None
-    if world > 1:
+    if full and world > 1:
         # the rank's own rows as RGBA32F, frames on alternating streams as in
         # the driver, nothing shipped
         fp = frame.copy()
@@ -624,7 +665,7 @@ def main():
         del bufs
 
     verified = None
-    if world > 1 and not args.no_verify and rank == 0:
+    if full and world > 1 and not args.no_verify and rank == 0:
         # outside the timed region: the assembled frame of the last step must
         # equal a whole-frame render on this device (pixels are independent)
         whole = scenes.config(args.config, precision=prec, pose=args.pose)
@@ -636,9 +677,13 @@ def main():
         verified = bool(torch.equal(got.view(torch.uint8), ref.view(torch.uint8)))
         log(f"[bench] assembled frame == single-device frame: {verified}")
 
-    flops = rank_flops(frame, t, args.pose)
-
     native = hasattr(drv, "read_frame")
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed frame, as a caller of the frame driver reads it
+        got = drv.read_frame(k_steps - 1) if native else drv.frame(k_steps - 1)
+        torch.cuda.synchronize(dev)
+        dumped = dump_outputs(args.dump_outputs, got)
     driver_desc = ("native (sdf_driver_*, C++)" if native
                    else "python (multigpu.FrameDriver, torch.distributed)")
     if native:
@@ -652,7 +697,7 @@ def main():
         value = W * H * args.steps / elapsed / 1e6
         out = {
             "metric": METRIC, "value": round(value, 3), "unit": "Mpixels/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
@@ -672,7 +717,7 @@ def main():
             "display_rgba8": display,
             other_name: other,
             "no_gather": no_gather,
-            "kernel_ms": round(kavg_ms, 4),
+            "kernel_ms": round(kavg_ms, 4) if full else None,
             # host (CPU) time of the frame loop's own calls per frame, waits
             # for the GPU / peers excluded (native driver only)
             "driver_host_us_per_frame": drv.stats()["host_us_per_frame"] if native else None,
@@ -681,12 +726,17 @@ def main():
             "driver_enqueue_us_per_frame": (drv.stats()["enqueue_us_per_frame"] if native
                                             else None),
         }
-        pmc = (pmc_summary(args.config, args.precision)
-               if world == 1 and args.format == "rgba32f" else {})
-        out["roofline"] = roofline(pmc, flops, kavg_ms, rows * W * lib_bpp(frame))
-        # the full-size parity of the precision `value` was timed in
-        out["parity"] = parity_summary(args.config, args.precision)
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        out["roofline"] = out["parity"] = None
+        if full:
+            pmc = (pmc_summary(args.config, args.precision)
+                   if world == 1 and args.format == "rgba32f" else {})
+            out["roofline"] = roofline(pmc, rank_flops(frame, t, args.pose), kavg_ms,
+                                       rows * W * lib_bpp(frame))
+            # the full-size parity of the precision `value` was timed in
+            out["parity"] = parity_summary(args.config, args.precision)
+        if full and world == 1 and not args.no_cpu_baseline:
             log("[bench] cpu baseline ...")
             out["cpu_baseline"], ref, ys = cpu_baseline(frame, args.cpu_sample_stride,
                                                         args.cpu_frames)

@@ -165,7 +165,7 @@ def test_native_driver_multirank(tmp_path, nproc, cfg, shares, batch, streams, n
              str(nproc), "--master-addr", "127.0.0.1", "--master-port", str(port), "--tee", "2",
              str(ROOT / "bench.py"), "--gpus", str(nproc), "--steps", "6", "--warmup", "2",
              "--backend", "gloo", "--comm-lib", str(SHMCOMM), "--driver", "native",
-             "--config", cfg, "--no-display", "--clock-warm-s", "0"]
+             "--config", cfg, "--full", "--no-display", "--clock-warm-s", "0"]
         c += ["--batch", str(batch)] if batch else []
         c += ["--streams", str(streams)] if streams else []
         c += ["--lag", str(lag), "--steps", "20"] if lag else []

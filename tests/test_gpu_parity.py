@@ -455,7 +455,7 @@ def test_multirank_bench_rehearsal(renderer, tmp_path, nproc, wire, shares):
         c = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node",
              str(nproc), "--master-addr", "127.0.0.1", "--master-port", str(port),
              str(root / "bench.py"), "--gpus", str(nproc), "--steps", "4", "--warmup", "2",
-             "--backend", "gloo", "--config", "C3", "--wire", wire, "--no-display"]
+             "--backend", "gloo", "--config", "C3", "--wire", wire, "--full", "--no-display"]
         return c + (["--shares", shares] if shares else [])
     r = run_launcher(cmd, timeout=300, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
