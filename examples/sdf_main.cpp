@@ -5,7 +5,10 @@
 // cl->get_tic()/get_toc(), :89/:97) and clean up.  The last frame is written
 // as a PPM instead of being presented in a window (:95-96).
 //
-//   sdf_main [width height frames out.ppm scene]     scene: ref | csg8 | bulb
+//   sdf_main [width height frames out.ppm scene [samples]]
+//     scene: ref | csg8 | bulb; samples: 1 (default), 2 or 4 sub-samples per
+//     axis, resolved in the render kernel (single-GPU path only: the frame
+//     driver refuses supersampling)
 //
 // Multi-GPU: launched once per GPU by any launcher that sets RANK,
 // WORLD_SIZE and LOCAL_RANK (e.g. `torchrun --nproc-per-node 8 --no-python
@@ -149,8 +152,10 @@ int main(int argc, char** argv) {
   const int frames = argc > 3 ? std::atoi(argv[3]) : 8;
   const std::string out = argc > 4 ? argv[4] : "sdf_main.ppm";
   const std::string kind = argc > 5 ? argv[5] : "ref";
+  const int samples = argc > 6 ? std::atoi(argv[6]) : 1;
   try {
     sdf::Frame f = sdf::Frame::reference(W, H);
+    f.supersample(samples);
     if (kind == "csg8") {
       const int S = SDF_OP_SMOOTH_UNION;
       const float k = 0.1f;

@@ -141,6 +141,14 @@ struct Frame {
       for (int r = 0; r < 4; ++r) camera.view[c * 4 + r] = static_cast<float>(m[r][c]);
     return *this;
   }
+  // Sub-samples per axis (params.samples): 1 one ray per pixel, 2 or 4 fused
+  // supersampling -- every pixel the box-filtered S x S sub-samples, resolved
+  // in the kernel (sdf_abi.h "Supersampling"); the framebuffer stays W x H.
+  // Renderer::render's `steps` then takes S H x S W int2.
+  Frame& supersample(int samples) {
+    params.samples = samples;
+    return *this;
+  }
 };
 
 // Arcball navigation producing V_mat: the reference

@@ -56,7 +56,7 @@ typedef __hip_internal::int64_t int64_t;
 extern "C" {
 #endif
 
-#define SDF_ABI_VERSION 11  /* 7: sdf_comm_create timeout, sdf_render_multi;
+#define SDF_ABI_VERSION 12  /* 7: sdf_comm_create timeout, sdf_render_multi;
                                 8: sdf_render_frames;
                                 9: TILES carries shading terms (64-byte
                                    stream header), SDF_FORMAT_SHADE32F;
@@ -66,7 +66,10 @@ extern "C" {
                                 11: sdf_schedule_*, sdf_render_scheduled,
                                    sdf_tiles_decode_checked (SDF_TILES_BAD_*
                                    one byte each), sdf_validate bounds every
-                                   length to 1e15 */
+                                   length to 1e15;
+                                12: sdf_params.samples (was reserved[0]):
+                                   fused 2x2 / 4x4 supersampling in sdf_render
+                                   and sdf_render_scheduled */
 
 /* ---- status codes ------------------------------------------------------ */
 #define SDF_OK               0
@@ -198,8 +201,49 @@ typedef struct {
   int32_t dispatch;            /* sdf_dispatch (AUTO: compile-time scene
                                   variant when one matches the scene)         */
   int32_t output_format;       /* sdf_format of the framebuffer written       */
-  int32_t reserved[2];
+  int32_t samples;             /* sub-samples per axis: 0 or 1 one sample per
+                                  pixel, 2 or 4 supersampling (below); anything
+                                  else is SDF_E_INVALID_ARG                    */
+  int32_t reserved[1];
 } sdf_params;
+
+/* Supersampling (sdf_params.samples = S, 2 or 4; ABI 12).  The pixel -> quad
+ * map is ((2x+1)/W - 1, (2y+1)/H - 1), so the S x S sub-sample grid of a
+ * W x H frame is exactly the pixel grid of the S W x S H frame (and the
+ * default aspect (float)(S W) / (float)(S H) is the same float as W / H):
+ *   - sub-sample (i, j) of output pixel (x, y) is pixel (S x + i, S y + j) of
+ *     the S W x S H frame; its colour c[i][j] is what sdf_render writes for
+ *     that pixel as RGBA32F with samples = 0, in the request's precision.
+ *   - resolve, per channel R, G, B, in fp32 round-to-nearest without fused
+ *     multiply-add, a balanced pairwise tree, first along x, then along y,
+ *     left / lower operand first:
+ *       S = 2   h_j = c[0][j] + c[1][j];   out = (h_0 + h_1) * 0.25f
+ *       S = 4   a_j = (c[0][j] + c[1][j]) + (c[2][j] + c[3][j]);
+ *               out = ((a_0 + a_1) + (a_2 + a_3)) * 0.0625f
+ *     alpha is 1; denormals are kept.  tests/ssaa_ref.py states it in NumPy.
+ *   - the output format's conversion (RGBA16F, RGBA8, RGB32F) is applied to
+ *     the resolved colour exactly as to a pixel's colour.  `rgba` holds the
+ *     W x H output (owned rows x W): no S W x S H buffer exists.
+ *   - limits: S * width <= 65536 and S * height <= 65536 (and S * block_rows
+ *     of a tiling fits int32), else SDF_E_INVALID_ARG; SDF_FORMAT_TILES and
+ *     SDF_FORMAT_SHADE32F are SDF_E_UNSUPPORTED (shading terms do not average
+ *     to the colour).
+ *   - a tiling refers to output rows: the render equals the S W x S H render
+ *     under the same tiling with block_rows * S, resolved; packed rows and
+ *     SDF_TILING_FRAME_ROWS work as with one sample.
+ *   - `steps`, when non-null, receives the sub-samples' counts: S * rows x
+ *     S * width int2, laid out as the steps buffer of the S W x S H render
+ *     under that scaled tiling (S * height rows with SDF_TILING_FRAME_ROWS);
+ *     sdf_heatmap works on it unchanged.
+ *   - sdf_render_scheduled serves it with a schedule created for S x the
+ *     owned rows (the kernel's 8-row cost blocks are sub-sample rows, so S *
+ *     rows <= 4096); a schedule of any other row count renders in launch
+ *     order, as for any render it does not fit.
+ *   - sdf_render_frames, sdf_render_multi and sdf_driver_create (at any world
+ *     size) return SDF_E_UNSUPPORTED for samples > 1, decided before any
+ *     device call: their TILES streams and the persistent frames kernel carry
+ *     no resolve.  Jittered or rotated grids, filters other than the box and
+ *     samples = 8 are not offered. */
 
 /* Framebuffer element formats (4 channels R,G,B,A per pixel).
  *   RGBA32F  the shader's float fragment_color (voxel_fragment.frag:12,210).
@@ -368,7 +412,9 @@ int64_t sdf_tiles_bytes(int32_t width, int32_t rows);
  * described above).
  * `steps` (device, may be NULL) receives 2 int32 per pixel: the primary and
  * the shadow march iteration counts (diagnostics / flop accounting).
- * Asynchronous on `stream`. */
+ * With params->samples > 1 every output pixel is the resolve of its S x S
+ * sub-samples and `steps` holds the sub-samples' counts ("Supersampling"
+ * above).  Asynchronous on `stream`. */
 int sdf_render(const sdf_scene* scene, const sdf_camera* camera,
                const sdf_light* light, const sdf_material* material,
                const sdf_params* params, const sdf_tiling* tiling,

@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 from pathlib import Path
 
-SDF_ABI_VERSION = 11
+SDF_ABI_VERSION = 12
 MAX_DECODE_PARTS = 64   # SDF_MAX_DECODE_PARTS
 SDF_MAX_PRIMS = 16
 
@@ -89,7 +89,8 @@ class sdf_params(C.Structure):
                 ("ao_step", C.c_float), ("ao_base", C.c_float), ("ao_falloff", C.c_float),
                 ("ao_strength", C.c_float), ("precision", C.c_int32),
                 ("dispatch", C.c_int32), ("output_format", C.c_int32),
-                ("reserved", C.c_int32 * 2)]
+                # sub-samples per axis: 0 / 1 one sample per pixel, 2 / 4 supersampling
+                ("samples", C.c_int32), ("reserved", C.c_int32 * 1)]
 
 
 class sdf_tiling(C.Structure):

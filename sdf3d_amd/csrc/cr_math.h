@@ -163,7 +163,11 @@ __device__ __forceinline__ float div_prepared(float a, float b, float yb) {
 // The residual's sign convention keeps a signed zero numerator's sign (q0 =
 // +-0, r = +0, q1 = -0 + q0 = q0).  Domain: l in [2^-30, 2^30), every a zero
 // or |a| >= 2^-60 (quotients and residuals stay normal); other lanes of the
-// wave take the IEEE division.
+// wave take the IEEE division.  The pixel's quad division (render_kernel.inc
+// shade_pixel) calls it without a guard: its numerator 2x + 1 is an integer
+// in [1, 2^17) and its divisor the width (height) the KERNEL indexes, an
+// integer in [1, 2^16] -- with supersampling the sub-sample width S W, which
+// sdf_validate holds to 65536 like a plain frame's.
 // SDF_CRM_DIV_STEPS 2: rounds 1-5's second step (A/B only; same results)
 #ifndef SDF_CRM_DIV_STEPS
 #define SDF_CRM_DIV_STEPS 1

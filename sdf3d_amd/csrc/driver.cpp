@@ -561,6 +561,9 @@ int sdf_driver_create(const sdf_scene* scene, const sdf_camera* camera, const sd
       batch > 16 || c.nbuf % batch != 0 || c.lag > c.nbuf - batch ||
       (c.flags & ~SDF_DRIVER_ROOT_AS_PEER) != 0)
     return SDF_E_INVALID_ARG;
+  // the ranks' TILES streams carry shading terms: no supersampling resolve
+  // (at world 1 either, so a frame does not change with the world size)
+  if (params->samples > 1) return SDF_E_UNSUPPORTED;
   const bool peer_root = (c.flags & SDF_DRIVER_ROOT_AS_PEER) != 0;
   const bool collectives = c.world > 1 || peer_root;
   if (collectives) {

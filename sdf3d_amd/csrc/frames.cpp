@@ -100,6 +100,8 @@ extern "C" int sdf_render_frames(const sdf_scene* scene, const sdf_camera* camer
   if (n == 0) return SDF_OK;
   if (!params) return SDF_E_INVALID_ARG;
   if (params->output_format == SDF_FORMAT_TILES) return SDF_E_UNSUPPORTED;
+  // supersampling is sdf_render's alone: the persistent kernel has no resolve
+  if (params->samples > 1) return SDF_E_UNSUPPORTED;
   for (int i = 0; i < n; ++i) {
     const int rc = sdf_validate(scene, &cameras[i], light, material, params, nullptr);
     if (rc != SDF_OK) return rc;

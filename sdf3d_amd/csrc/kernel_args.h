@@ -66,6 +66,12 @@ struct KernelArgs {
   // outputs
   void* rgba;           // rows * width pixels of `format`, packed rows
   int32_t* steps;       // rows * width int2 or null
+  // supersampling (sdf_params.samples = S > 1, render_ssaa): width, height,
+  // rows and the tiling above are then those of the S W x S H sub-sample
+  // frame, `steps` its buffer, and `rgba` holds rows / S rows of out_width =
+  // width / S resolved pixels
+  int32_t out_width;    // pixels per output row (width when S = 1)
+  int32_t ss_log2;      // log2 S: 0 (one sample per pixel), 1 or 2
 };
 
 // ---- dispatch order of a frame's 8-row blocks (sdf_render_scheduled) -------
@@ -89,7 +95,8 @@ struct RenderArgs {
 };
 
 // Waves (8x8 tiles side by side) per render workgroup (render_kernel.inc
-// render / render_tiles; the built-in and the run-time specialised launchers).
+// render / render_tiles / render_ssaa; the built-in and the run-time
+// specialised launchers).
 // Round 4: one wave per workgroup -- each wave is placed on its own, so the
 // frame's last, longest tiles pack onto the CUs better than in 4-wave groups
 // that need four slots of one CU: C4 fast 0-1.6 % faster, C5 fast up to 4 %,

@@ -165,6 +165,8 @@ static int render_multi(const sdf_scene* scene, const sdf_camera* camera,
   if (!params || !devices || !rgba || ndev < 1 || ndev > SDF_MAX_DECODE_PARTS)
     return SDF_E_INVALID_ARG;
   if (params->output_format != SDF_FORMAT_RGBA32F) return SDF_E_UNSUPPORTED;
+  // the peers' TILES streams carry shading terms: no supersampling resolve
+  if (params->samples > 1) return SDF_E_UNSUPPORTED;
   int rc = sdf_validate(scene, camera, light, material, params, nullptr);
   if (rc != SDF_OK) return rc;
   int a = share_root, b = share_peer;

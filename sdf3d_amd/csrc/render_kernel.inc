@@ -1683,8 +1683,9 @@ __device__ __forceinline__ float4 shade_pixel(KA& A, const Scene& scene, const V
   // quad = ((2x+1)/W - 1, (2y+1)/H - 1)   (voxel_geometry.geom:26-52)
 #if SDF_EXACT && SDF_EXACT_QDIV
   // (2x+1) / W by one Markstein step from the host's RN(1/W): an integer
-  // numerator in [1, 2^17) over an integer W in [1, 2^16], where no step
-  // underflows or overflows (cr_math.h div_refined): the IEEE quotient
+  // numerator in [1, 2^17) over an integer W in [1, 2^16] (A.width: the
+  // sub-sample width S W of a supersampled frame, held to 2^16 as well), where
+  // no step underflows or overflows (cr_math.h div_refined): the IEEE quotient
   const float qx = crm::div_refined((float)(2 * x + 1), (float)A.width, A.inv_width) - 1.0f;
   const float qy = crm::div_refined((float)(2 * y + 1), (float)A.height, A.inv_height) - 1.0f;
 #elif SDF_EXACT
@@ -1925,10 +1926,37 @@ __device__ __forceinline__ float4 pixel_value(KA& A, int format, float4 t) {
   return shade_colour<SDF_EXACT>(frame_shade(A), t.x, t.y, t.z);
 }
 
+// ---- supersampling resolve (sdf_abi.h sdf_params.samples) ------------------
+// The wave's 8x8 tile holds whole S x S groups of sub-samples (S = 2 or 4, a
+// uniform): lane bits 0, 1 carry a sub-sample's x inside the tile and bits 3,
+// 4 its y.  One channel's group sum in the contract's order -- a balanced
+// pairwise tree, first along x, then along y, left / lower operand first:
+//   S = 2   h_j = c[0][j] + c[1][j];                      (h_0 + h_1)
+//   S = 4   a_j = (c[0][j] + c[1][j]) + (c[2][j] + c[3][j]);
+//           (a_0 + a_1) + (a_2 + a_3)
+// by adding the xor-partner's value (wave_bits.h: DPP quad_perm for 1 and 2,
+// ds_swizzle for 8 and 16).  The group's (0, 0) lane is the left / lower
+// operand of every addition it makes, so it ends with the tree's value; the
+// other lanes' sums are not used.  Plain fp32 additions, never fused.
+// (The exchanges for 8 and 16 as VALU moves instead -- DPP row_ror:8 and
+// v_permlane16_swap -- measured no faster, DESIGN.md: the LDS round trips at
+// the wave's end are not what the epilogue costs.)
+__device__ __forceinline__ float ssaa_sum(float v, bool four) {
+#pragma clang fp contract(off)
+  v = v + __uint_as_float(xor_partner<1>(__float_as_uint(v)));
+  if (four) v = v + __uint_as_float(xor_partner<2>(__float_as_uint(v)));
+  v = v + __uint_as_float(xor_partner<8>(__float_as_uint(v)));
+  if (four) v = v + __uint_as_float(xor_partner<16>(__float_as_uint(v)));
+  return v;
+}
+
 // TILES: the output is the TILES wire format (a separate instantiation, so
 // the encoder's registers never weigh on the plain-format kernels)
-template <class Scene, bool TILES, bool STEPS>
+// SSAA: the lanes are the sub-samples of a supersampled frame and the output
+// is their resolved pixels (render_ssaa, an instantiation of its own as well)
+template <class Scene, bool TILES, bool STEPS, bool SSAA = false>
 __device__ __forceinline__ void render_body() {
+  static_assert(!(TILES && SSAA), "a TILES stream carries shading terms, not colours");
   const KARG char* const seg = (const KARG char*)__builtin_amdgcn_kernarg_segment_ptr();
   KA& A = *(KA*)seg;
   const KARG RowOrder& O = *(const KARG RowOrder*)(seg + __builtin_offsetof(RenderArgs, o));
@@ -1944,6 +1972,14 @@ __device__ __forceinline__ void render_body() {
   const int pr = by * 8 + (lane >> 3);
   const bool valid = x < A.width && pr < A.rows;
   if constexpr (!TILES) {
+    // SSAA: a group of S x S sub-samples leaves whole or not at all.  The
+    // tile starts at multiples of 8 in x and in packed rows and 8 is a
+    // multiple of S, so a group never straddles a wave; A.width = S W and
+    // A.rows = S rows are multiples of S, and so is every run of packed rows
+    // (block_rows and the frame's last row are S times the request's), so a
+    // group lies wholly inside or wholly outside the frame and inside one
+    // tiling block: its lanes share `valid` and consecutive frame rows, and
+    // the resolve below exchanges values among lanes that are all present.
     if (!valid) return;
   } else {
     // every lane of a wave with a pixel in the frame stays: the tile encoder
@@ -1991,6 +2027,20 @@ __device__ __forceinline__ void render_body() {
     const int tile = by * tiles_x + blockIdx.x * kWgWaves + wave;
     store_tiles(A.rgba, tiles_x * ((A.rows + 7) >> 3), tile, lane, valid, c);
     if (tile == 0) store_tiles_shade(A.rgba, frame_shade(A), lane);
+  } else if constexpr (SSAA) {
+    // every lane's colour, the group sums in the contract's tree order, and
+    // the group's (0, 0) lane scales by 1 / S^2 (a power of two: one
+    // rounding, denormals kept), converts and writes the output pixel
+    const float4 s = shade_colour<SDF_EXACT>(frame_shade(A), c.x, c.y, c.z);
+    const int lg = A.ss_log2;
+    const bool four = lg == 2;
+    const float sx = ssaa_sum(s.x, four), sy = ssaa_sum(s.y, four), sz = ssaa_sum(s.z, four);
+    const int sub = (1 << lg) - 1;
+    if ((lane & sub) == 0 && ((lane >> 3) & sub) == 0) {
+      const float w = four ? 0.0625f : 0.25f;
+      const size_t oo = (size_t)((A.frame_rows ? y : pr) >> lg) * A.out_width + (x >> lg);
+      store_pixel(A.format, A.rgba, oo, make_float4(sx * w, sy * w, sz * w, 1.0f));
+    }
   } else {
     store_pixel(A.format, A.rgba, o, pixel_value(A, A.format, c));
   }
@@ -2012,6 +2062,17 @@ __global__ __launch_bounds__(64 * kWgWaves) __attribute__((amdgpu_waves_per_eu(S
 void render_tiles(RenderArgs args) {
   (void)args;
   render_body<Scene, true, STEPS>();
+}
+// the supersampling instantiation (sdf_params.samples = 2 or 4, a uniform
+// read from the arguments): the plain kernel's pixels as sub-samples, with
+// the resolve epilogue; with and without step recording like `render`, so a
+// sub-sample is bit for bit the pixel the plain kernel of the same STEPS
+// writes for the S W x S H frame
+template <class Scene, bool STEPS>
+__global__ __launch_bounds__(64 * kWgWaves) __attribute__((amdgpu_waves_per_eu(SDF_WAVES_PER_EU, SDF_WAVES_PER_EU)))
+void render_ssaa(RenderArgs args) {
+  (void)args;
+  render_body<Scene, false, STEPS, true>();
 }
 
 // The persistent frame-sequence kernel (sdf_render_frames): every wave
@@ -2116,6 +2177,11 @@ static void launch_scene(const RenderArgs& a, dim3 grid, dim3 block, hipStream_t
       hipLaunchKernelGGL((SDF_NS::render_tiles<S, true, true>), grid, block, 0, s, a);
     else
       hipLaunchKernelGGL((SDF_NS::render_tiles<S, true, false>), grid, block, 0, s, a);
+  } else if (a.a.ss_log2 > 0) {
+    if (a.a.steps)
+      hipLaunchKernelGGL((SDF_NS::render_ssaa<S, true>), grid, block, 0, s, a);
+    else
+      hipLaunchKernelGGL((SDF_NS::render_ssaa<S, false>), grid, block, 0, s, a);
   } else {
     if (a.a.steps)
       hipLaunchKernelGGL((SDF_NS::render<S, false, true>), grid, block, 0, s, a);

@@ -367,8 +367,16 @@ int make_render_plan(const sdf_scene* scene, const sdf_camera* camera, const sdf
   int rc = sdf_validate(scene, camera, light, material, params, tiling);
   if (rc != SDF_OK) return rc;
   if (!plan) return SDF_E_INVALID_ARG;
-  const sdf_tiling t = tiling ? *tiling : kWholeFrame;
-  const int rows = count_rows(params->height, t);
+  // Supersampling (params->samples = S > 1): the kernel is handed the S W x
+  // S H sub-sample frame, whose pixel grid is exactly the request's S x S
+  // sub-sample grid ((2x+1)/W - 1 at S W), under the request's tiling with
+  // block_rows S times as long: S times the rows, every block and the frame's
+  // last row a multiple of S.  The plan's rows (what a schedule matches and
+  // the grid covers) are sub-sample rows.
+  const int S = params->samples > 1 ? params->samples : 1;
+  sdf_tiling t = tiling ? *tiling : kWholeFrame;
+  t.block_rows *= S;
+  const int rows = count_rows(params->height * S, t);
   std::memset(plan, 0, sizeof(*plan));
   plan->rows = rows;
   if (rows == 0) return SDF_OK;  // a rank that owns no block: nothing to write
@@ -378,8 +386,10 @@ int make_render_plan(const sdf_scene* scene, const sdf_camera* camera, const sdf
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return SDF_E_NO_DEVICE;
 
   KernelArgs& a = plan->a;
-  a.width = params->width;
-  a.height = params->height;
+  a.width = params->width * S;
+  a.height = params->height * S;
+  a.out_width = params->width;
+  a.ss_log2 = S == 4 ? 2 : S == 2 ? 1 : 0;
   plan_set_camera(plan, camera);
   for (int i = 0; i < 3; ++i) {
     a.light_pos[i] = light->pos[i];
@@ -420,8 +430,8 @@ int make_render_plan(const sdf_scene* scene, const sdf_camera* camera, const sdf
       a.ao_path[i] = f;
     }
   }
-  a.inv_width = 1.0f / (float)params->width;
-  a.inv_height = 1.0f / (float)params->height;
+  a.inv_width = 1.0f / (float)a.width;
+  a.inv_height = 1.0f / (float)a.height;
   a.block_rows = t.block_rows;
   a.chunk_rows = t.block_rows * run_of(t);
   a.run_gap_rows = sdf::tiling_gap_rows(t);
@@ -743,6 +753,17 @@ int sdf_validate(const sdf_scene* scene, const sdf_camera* camera, const sdf_lig
   const sdf_params& p = *params;
   if (p.width <= 0 || p.height <= 0 || p.width > 65536 || p.height > 65536)
     return SDF_E_INVALID_ARG;
+  // sub-samples per axis: 0 and 1 are one sample per pixel.  The sub-sample
+  // frame S W x S H is what the kernels index (cr_math.h div_refined: a quad
+  // numerator below 2^17 over at most 2^16), and its tiling's block_rows are
+  // S times the request's
+  if (p.samples != 0 && p.samples != 1 && p.samples != 2 && p.samples != 4)
+    return SDF_E_INVALID_ARG;
+  if (p.samples > 1) {
+    if (p.samples * (long long)p.width > 65536 || p.samples * (long long)p.height > 65536)
+      return SDF_E_INVALID_ARG;
+    if (tiling && tiling->block_rows > INT32_MAX / p.samples) return SDF_E_INVALID_ARG;
+  }
   if (p.max_steps < 0 || p.max_steps > (1 << 24)) return SDF_E_INVALID_ARG;
   // every length the marches add to a coordinate stays in the working range
   // (kMaxCoord below): normal_eps^2 and the AO tap lengths must not overflow,
@@ -826,6 +847,11 @@ int sdf_validate(const sdf_scene* scene, const sdf_camera* camera, const sdf_lig
       return SDF_E_INVALID_ARG;
   if (std::fabs(p.max_dist) > kMaxCoord) return SDF_E_INVALID_ARG;
   (void)material;
+  // a valid request no kernel serves: shading terms do not average to the
+  // colour, so a resolve of TILES or SHADE32F sub-samples would be wrong
+  if (p.samples > 1 &&
+      (p.output_format == SDF_FORMAT_TILES || p.output_format == SDF_FORMAT_SHADE32F))
+    return SDF_E_UNSUPPORTED;
   return SDF_OK;
 }
 

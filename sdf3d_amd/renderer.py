@@ -79,6 +79,19 @@ def channels(fmt: int) -> int:
     return abi.FORMAT_CHANNELS[fmt]
 
 
+def samples(frame: Frame) -> int:
+    """Sub-samples per axis of a frame's render (sdf_params.samples; 0 is 1)."""
+    return max(int(frame.params.samples), 1)
+
+
+def steps_shape(frame: Frame, t: abi.sdf_tiling | None = None) -> tuple[int, int, int]:
+    """Shape of the steps tensor of ``Renderer.render(frame, t)``: one int2 per
+    sample -- (S rows, S W, 2) with S x S supersampling, the layout of the
+    S W x S H render's steps under the tiling with block_rows * S."""
+    s = samples(frame)
+    return (s * buffer_rows(frame.params.height, t), s * frame.params.width, 2)
+
+
 class Renderer:
     """Renders frames on one HIP device through ``sdf_render``."""
 
@@ -115,8 +128,8 @@ class Renderer:
         else:
             rgba = self.torch.empty((rows, w, channels(fmt)), dtype=torch_dtype(fmt),
                                     device=self.device)
-        st = (self.torch.empty((rows, w, 2), dtype=self.torch.int32, device=self.device)
-              if steps else None)
+        st = (self.torch.empty(steps_shape(frame, t), dtype=self.torch.int32,
+                               device=self.device) if steps else None)
         return rgba, st
 
     def schedule(self, rows: int, period: int = 1) -> "Schedule":
@@ -131,6 +144,8 @@ class Renderer:
 
         Returns (rgba[rows, W, 4] float32, steps[rows, W, 2] int32 or None), both
         on the device, asynchronous on `stream` (default: torch's current).
+        With ``frame.params.samples`` = S > 1 every pixel is the resolve of its
+        S x S sub-samples and steps is (S rows, S W, 2): the sub-samples' counts.
         `schedule`: dispatch order of the row blocks (sdf_render_scheduled)."""
         torch = self.torch
         rows = buffer_rows(frame.params.height, t)
@@ -154,9 +169,10 @@ class Renderer:
                     or not rgba.is_contiguous() or rgba.device != self.device:
                 raise ValueError(f"rgba must be a contiguous {dt} ({rows}, {w}, {ch}) tensor "
                                  f"on {self.device}")
-        if st is not None and (tuple(st.shape) != (rows, w, 2) or st.dtype != torch.int32
+        sshape = steps_shape(frame, t)
+        if st is not None and (tuple(st.shape) != sshape or st.dtype != torch.int32
                                or not st.is_contiguous()):
-            raise ValueError(f"steps must be a contiguous int32 ({rows}, {w}, 2) tensor")
+            raise ValueError(f"steps must be a contiguous int32 {sshape} tensor")
         with self._on_device():
             args = (C.byref(frame.scene), C.byref(frame.camera), C.byref(frame.light),
                     C.byref(frame.material), C.byref(frame.params),
