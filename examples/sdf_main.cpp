@@ -5,10 +5,15 @@
 // cl->get_tic()/get_toc(), :89/:97) and clean up.  The last frame is written
 // as a PPM instead of being presented in a window (:95-96).
 //
-//   sdf_main [width height frames out.ppm scene [samples]]
+//   sdf_main [width height frames out.ppm scene [samples [lights]]]
 //     scene: ref | csg8 | bulb; samples: 1 (default), 2 or 4 sub-samples per
 //     axis, resolved in the render kernel (single-GPU path only: the frame
 //     driver refuses supersampling)
+//     lights: "x,y,z[,r,g,b];..." -- up to SDF_MAX_LIGHTS point lights that
+//     light the frame together (sdf_render_lights; single-GPU path only).  The
+//     first carries the reference's ambient term, the others none; a light
+//     with r,g,b turns SDF_LIGHTS_COLOR on (lights without get white).  The
+//     default is the reference's one light.
 //
 // Multi-GPU: launched once per GPU by any launcher that sets RANK,
 // WORLD_SIZE and LOCAL_RANK (e.g. `torchrun --nproc-per-node 8 --no-python
@@ -33,6 +38,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "../include/sdf3d.hpp"
 
@@ -69,6 +75,32 @@ struct Navigator {
     ball.apply(f);
   }
 };
+
+// argv[7]: "x,y,z[,r,g,b];..." (see the header comment)
+bool parse_lights(const std::string& text, const sdf_light& first, std::vector<sdf_light>& lights,
+                  int32_t& flags) {
+  size_t at = 0;
+  while (at < text.size()) {
+    size_t end = text.find(';', at);
+    if (end == std::string::npos) end = text.size();
+    const std::string item = text.substr(at, end - at);
+    at = end + 1;
+    if (item.empty()) continue;
+    float v[6];
+    const int n = std::sscanf(item.c_str(), "%f,%f,%f,%f,%f,%f", &v[0], &v[1], &v[2], &v[3], &v[4],
+                              &v[5]);
+    if (n != 3 && n != 6) return false;
+    sdf_light l = first;
+    l.ambient = lights.empty() ? first.ambient : 0.0f;
+    for (int c = 0; c < 3; ++c) {
+      l.pos[c] = v[c];
+      l.color[c] = n == 6 ? v[3 + c] : 1.0f;
+    }
+    if (n == 6) flags |= SDF_LIGHTS_COLOR;
+    lights.push_back(l);
+  }
+  return !lights.empty() && lights.size() <= SDF_MAX_LIGHTS;
+}
 
 int run_driver(sdf::Frame f, int frames, const std::string& out) {
   const int rank = std::atoi(env("RANK", "0").c_str());
@@ -155,6 +187,10 @@ int main(int argc, char** argv) {
   const int samples = argc > 6 ? std::atoi(argv[6]) : 1;
   try {
     sdf::Frame f = sdf::Frame::reference(W, H);
+    std::vector<sdf_light> lights;
+    int32_t light_flags = 0;
+    if (argc > 7 && !parse_lights(argv[7], f.light, lights, light_flags))
+      throw sdf::Error(SDF_E_INVALID_ARG, "lights: \"x,y,z[,r,g,b];...\", at most 8");
     f.supersample(samples);
     if (kind == "csg8") {
       const int S = SDF_OP_SMOOTH_UNION;
@@ -199,7 +235,8 @@ int main(int argc, char** argv) {
       for (int i = 0; i < frames; ++i) {
         nav.frame(f, i, frames);
         sdf::check_hip(hipEventRecord(t0, stream), "hipEventRecord");
-        r.render(f);
+        if (lights.empty()) r.render(f);
+        else r.render(f, lights, light_flags);
         sdf::check_hip(hipEventRecord(t1, stream), "hipEventRecord");
         sdf::check_hip(hipEventSynchronize(t1), "hipEventSynchronize");
         float ms = 0;

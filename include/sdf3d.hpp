@@ -248,6 +248,19 @@ class Renderer {
                      stream_),
           "sdf_render");
   }
+  // The frame under `lights` (1 .. SDF_MAX_LIGHTS, f.light is ignored) with
+  // light_flags (SDF_LIGHTS_COLOR: every light scaled by its colour):
+  // sdf_render_lights, the surface traced once for all of them.
+  void render(const Frame& f, const std::vector<sdf_light>& lights, int32_t light_flags = 0,
+              const sdf_tiling* tiling = nullptr, int32_t* steps = nullptr,
+              sdf_schedule* schedule = nullptr) {
+    if (f.params.width != w_ || f.params.height != h_)
+      throw Error(SDF_E_INVALID_ARG, "Renderer: frame size differs from framebuffer");
+    check(sdf_render_lights(&f.scene, &f.camera, lights.data(),
+                            static_cast<int32_t>(lights.size()), light_flags, &f.material,
+                            &f.params, tiling, rgba_, steps, schedule, stream_),
+          "sdf_render_lights");
+  }
   // Blocking copy of an RGBA32F framebuffer (row 0 = bottom, GL order).
   std::vector<float> download() const {
     std::vector<float> out(size_t(w_) * h_ * 4);

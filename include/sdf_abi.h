@@ -69,7 +69,12 @@ extern "C" {
                                    length to 1e15;
                                 12: sdf_params.samples (was reserved[0]):
                                    fused 2x2 / 4x4 supersampling in sdf_render
-                                   and sdf_render_scheduled */
+                                   and sdf_render_scheduled;
+                                still 12: sdf_validate_lights and
+                                   sdf_render_lights (SDF_MAX_LIGHTS,
+                                   SDF_LIGHTS_COLOR) are additions -- no struct
+                                   and no existing entry point changed, so the
+                                   version stays; detect them by the symbol */
 
 /* ---- status codes ------------------------------------------------------ */
 #define SDF_OK               0
@@ -155,9 +160,16 @@ typedef struct {
 typedef struct {
   float pos[3];                /* (5, 5, 0)                                    */
   float ambient;               /* light.amb = 0.1                              */
-  float color[3];              /* light.col = 0.7: declared, never used (:183) */
+  float color[3];              /* light.col = 0.7: declared, never used by the
+                                  shader (:183) nor by sdf_render; a factor on
+                                  the light's diffuse and specular under
+                                  sdf_render_lights with SDF_LIGHTS_COLOR      */
   float reserved;
 } sdf_light;
+
+/* Several lights (sdf_render_lights, "Lights" below) */
+#define SDF_MAX_LIGHTS   8
+#define SDF_LIGHTS_COLOR 0x1   /* light_flags: scale light i's diffuse and specular by lights[i].color */
 
 /* Material: voxel_fragment.frag:42-49, :186-189.                            */
 typedef struct {
@@ -244,6 +256,58 @@ typedef struct {
  *     device call: their TILES streams and the persistent frames kernel carry
  *     no resolve.  Jittered or rotated grids, filters other than the box and
  *     samples = 8 are not offered. */
+
+/* Lights (sdf_render_lights: L = nlights point lights, 1 .. SDF_MAX_LIGHTS,
+ * with light_flags).  The frame is defined from what sdf_render gives with one
+ * light at a time, so it can be checked bit for bit (tests/lights_ref.py
+ * states it in NumPy):
+ *   - geometry: the primary march, the hit point P, the normal N and the
+ *     ambient-occlusion term ao of a pixel are those of sdf_render; they do
+ *     not depend on the light.
+ *   - per-light terms: (dif_i, x_i) of light i are bit for bit channels 1 and
+ *     2 of what sdf_render writes as SDF_FORMAT_SHADE32F with light =
+ *     lights[i], in the request's precision (dif = clamp(N.L, 0, 1) * shadow,
+ *     x = max(N.H, 0)); spec_i = x_i ^ shininess as sdf_render forms it in
+ *     that precision (exact: fp64 pow rounded to fp32 once; fast: exp2(shin *
+ *     log2(x)) with the hardware's v_exp_f32 / v_log_f32 and one fp32 product).
+ *   - ambient: la = the fp32 sum of lights[i].ambient in index order (one
+ *     light: its own value); lam[c] = RN(la * material.amb[c]).  The ambient
+ *     term is never coloured.
+ *   - colour sum, per channel c = R, G, B, in fp32 round-to-nearest, lights
+ *     in index order, never reassociated:
+ *       acc = RN(lam[c] * ao)
+ *       for i in 0 .. L-1:
+ *         with SDF_LIGHTS_COLOR  d = RN(dif_i * lights[i].color[c]),
+ *                                s = RN(spec_i * lights[i].color[c])
+ *                                (plain products, never fused)
+ *         otherwise              d = dif_i, s = spec_i
+ *         exact precision  acc = RN(RN(acc + RN(d * mat.dif[c])) + RN(s * mat.ref[c]))
+ *         fast precision   acc = fma(s, mat.ref[c], fma(d, mat.dif[c], acc))
+ *                          (each fma rounded once)
+ *     out[c] = acc, alpha is 1.  For one light without the flag this is
+ *     sdf_render's colour exactly.  A colour is an arbitrary finite factor
+ *     (negative ones included); lights[i].color is ignored without the flag.
+ *   - steps, when non-null, receives (primary, sum over i of shadow_i) per
+ *     pixel, shadow_i being light i's count in its own sdf_render; as in
+ *     sdf_render every shadow march then runs to the reference's break.
+ *     sdf_heatmap works on the result unchanged.
+ *   - nlights = 1 with light_flags = 0 is sdf_render / sdf_render_scheduled
+ *     itself: the same kernels, every format, the same bits.
+ *   - output conversion (RGBA16F, RGBA8, RGB32F), tilings, SDF_TILING_FRAME_ROWS
+ *     and schedules work as in sdf_render / sdf_render_scheduled.  With
+ *     samples = 2 or 4 a sub-sample's colour is the L-light colour of its pixel
+ *     of the S W x S H frame, resolved as under "Supersampling".
+ *   - SDF_E_INVALID_ARG (sdf_validate_lights, and sdf_render_lights before any
+ *     device call): lights NULL; nlights < 1 or > SDF_MAX_LIGHTS; light_flags
+ *     bits other than SDF_LIGHTS_COLOR; a light whose position fails
+ *     sdf_validate's checks of its one light (finite, |.| <= 1e15); with
+ *     SDF_LIGHTS_COLOR a non-finite colour component.  Everything else is
+ *     validated by sdf_validate with lights[0].
+ *   - SDF_E_UNSUPPORTED: SDF_FORMAT_TILES and SDF_FORMAT_SHADE32F with
+ *     nlights > 1 or SDF_LIGHTS_COLOR (a stream carries one light's terms).
+ *   - sdf_render_frames, sdf_render_multi and the frame driver keep their one
+ *     light.  Directional and spot lights, per-light shadow switches,
+ *     attenuation and more than SDF_MAX_LIGHTS lights are not offered. */
 
 /* Framebuffer element formats (4 channels R,G,B,A per pixel).
  *   RGBA32F  the shader's float fragment_color (voxel_fragment.frag:12,210).
@@ -444,6 +508,20 @@ int sdf_render_scheduled(const sdf_scene* scene, const sdf_camera* camera,
                          const sdf_light* light, const sdf_material* material,
                          const sdf_params* params, const sdf_tiling* tiling,
                          void* rgba, int32_t* steps, sdf_schedule* schedule, void* stream);
+
+/* sdf_render / sdf_render_scheduled (`schedule` may be NULL) under `nlights`
+ * lights ("Lights" above): the surface is traced once and every light adds
+ * its diffuse and specular terms.  sdf_validate_lights is the host-only check
+ * sdf_render_lights makes first (no device call). */
+int sdf_validate_lights(const sdf_scene* scene, const sdf_camera* camera,
+                        const sdf_light* lights, int32_t nlights, int32_t light_flags,
+                        const sdf_material* material, const sdf_params* params,
+                        const sdf_tiling* tiling);
+int sdf_render_lights(const sdf_scene* scene, const sdf_camera* camera,
+                      const sdf_light* lights, int32_t nlights, int32_t light_flags,
+                      const sdf_material* material, const sdf_params* params,
+                      const sdf_tiling* tiling, void* rgba, int32_t* steps,
+                      sdf_schedule* schedule, void* stream);
 
 /* Scatter `nparts` packed row-block buffers (part r = rank r's output for
  * tiling {block_rows, r, nparts}), laid out back to back in `parts` with a

@@ -13,6 +13,8 @@ from pathlib import Path
 SDF_ABI_VERSION = 12
 MAX_DECODE_PARTS = 64   # SDF_MAX_DECODE_PARTS
 SDF_MAX_PRIMS = 16
+MAX_LIGHTS = 8        # SDF_MAX_LIGHTS (sdf_render_lights)
+LIGHTS_COLOR = 0x1    # SDF_LIGHTS_COLOR: light i's diffuse and specular scaled by its colour
 
 # status codes
 SDF_OK = 0
@@ -140,6 +142,12 @@ SIGNATURES = {
     "sdf_render_scheduled": (C.c_int, [_P(sdf_scene), _P(sdf_camera), _P(sdf_light),
                                        _P(sdf_material), _P(sdf_params), _P(sdf_tiling),
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sdf_validate_lights": (C.c_int, [_P(sdf_scene), _P(sdf_camera), _P(sdf_light), C.c_int32,
+                                      C.c_int32, _P(sdf_material), _P(sdf_params),
+                                      _P(sdf_tiling)]),
+    "sdf_render_lights": (C.c_int, [_P(sdf_scene), _P(sdf_camera), _P(sdf_light), C.c_int32,
+                                    C.c_int32, _P(sdf_material), _P(sdf_params), _P(sdf_tiling),
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sdf_tiles_decode_checked": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _P(sdf_tiling),
                                            _P(C.c_int64), C.c_int32, C.c_int32, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

@@ -89,9 +89,24 @@ struct RowOrder {
   int32_t reserved;
   uint16_t order[kMaxOrderBlocks];
 };
+// ---- several lights (sdf_render_lights) ------------------------------------
+// The lights of a multi-light render ride in the kernel-argument segment
+// behind the row order, so the kernel's loop over them reads scalars: light
+// i's position and colour, the summed ambient `la` (fp32, index order) and
+// the SDF_LIGHTS_* flags.  n = 0: a plain render, which reads none of this
+// (KernelArgs::light_pos / light_amb are the one light's).
+struct LightsArgs {
+  float pos[SDF_MAX_LIGHTS][3];
+  float color[SDF_MAX_LIGHTS][3];
+  float la;
+  int32_t n;
+  int32_t flags;
+  int32_t reserved;
+};
 struct RenderArgs {
   KernelArgs a;   // first: the kernels read it at the start of the segment
   RowOrder o;
+  LightsArgs l;   // only RenderArgs has the room (FramesArgs is near 4 KiB)
 };
 
 // Waves (8x8 tiles side by side) per render workgroup (render_kernel.inc

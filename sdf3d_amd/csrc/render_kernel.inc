@@ -1677,9 +1677,21 @@ struct FrameView {
 // own: without it the per-lane iteration counts are dead after the loops,
 // so no per-step copy of the uniform loop counter is made, and the exact
 // shadow skip is always taken).
-template <bool STEPS, class Scene, class View>
-__device__ __forceinline__ float4 shade_pixel(KA& A, const Scene& scene, const View& V, int x,
-                                              int y, int& sp, int& ss) {
+//
+// The pixel is traced in two parts, so that a render with several lights
+// (shade_pixel_lights) shares every expression with this one: trace_surface
+// is what does not depend on the light -- the primary march, the normal and
+// the ambient occlusion, leaving the culling state `mst` at P -- and
+// light_terms is one light's (dif, x) with its shadow march from P.
+struct Surface {
+  V3 cam, P, N;
+  float tP;   // path length at P
+  float ao;
+};
+
+template <class Scene, class View>
+__device__ __forceinline__ void trace_surface(KA& A, const Scene& scene, const View& V, int x,
+                                              int y, int& sp, MarchState& mst, Surface& S) {
   // quad = ((2x+1)/W - 1, (2y+1)/H - 1)   (voxel_geometry.geom:26-52)
 #if SDF_EXACT && SDF_EXACT_QDIV
   // (2x+1) / W by one Markstein step from the host's RN(1/W): an integer
@@ -1710,7 +1722,6 @@ __device__ __forceinline__ float4 shade_pixel(KA& A, const Scene& scene, const V
   float d = 0.0f;
   // Culling state along the pixel's path (FixedScene::march): the primary
   // ray, side trips to the normal and AO taps, then the shadow ray from P.
-  MarchState mst;
   for (; sp < A.max_steps;) {
     V3 rp = add(cam, muls(ray, d));
     float sdf = scene.march_primary(rp, d, mst);
@@ -1777,12 +1788,42 @@ __device__ __forceinline__ float4 shade_pixel(KA& A, const Scene& scene, const V
     }
     ao = gclamp(1.0f - A.ao_strength * occ, 0.0f, 1.0f);
   }
+  S.cam = cam;
+  S.P = P;
+  S.N = N;
+  S.tP = tP;
+  S.ao = ao;
+}
 
+// The terms of the light at Lp for the surface S: dif = clamp(N.L, 0, 1) *
+// shadow and spec_x = max(N.H, 0); `mst` is the culling state at P (advanced
+// along the shadow ray), `ss` counts the shadow march's iterations from 0.
+template <bool STEPS, class Scene, class View>
+__device__ __forceinline__ void light_terms(KA& A, const Scene& scene, const View& V,
+                                            const Surface& S, const V3 Lp, MarchState& mst,
+                                            int& ss, float& dif_out, float& spec_x_out) {
+  const V3 cam = S.cam, P = S.P, N = S.N;
+  const float tP = S.tP;
+  const float max_dist = A.max_dist, eps = A.eps;
   // Blinn-Phong, :200-204
-  const V3 Lp = mk(A.light_pos[0], A.light_pos[1], A.light_pos[2]);
+#if SDF_EXACT
   const V3 view = normalize(sub(cam, P));
   const V3 incident = normalize(sub(Lp, P));
   const V3 halfway = normalize(add(incident, view));
+#else
+  const V3 incident = normalize(sub(Lp, P));
+  // incident + normalize(cam - P) with the view's scaling fused into the sum:
+  // what contraction makes of it where both stand in one block, as in every
+  // single-light kernel.  Written out, because the loop over several lights
+  // hoists the light-independent `view` as rounded products and would add it
+  // unfused: x one ulp apart on ~10 % of the pixels.  (The view is recomputed
+  // per light instead of kept live: a subtraction, a v_rsq and three FMAs.)
+  const V3 cp = sub(cam, P);
+  const float rv = frsqrt(dot(cp, cp));
+  const V3 halfway = normalize(mk(__builtin_fmaf(cp.x, rv, incident.x),
+                                  __builtin_fmaf(cp.y, rv, incident.y),
+                                  __builtin_fmaf(cp.z, rv, incident.z)));
+#endif
   const float spec_x = gmax(dot(N, halfway), 0.0f);   // spec = pow(spec_x, shininess)
 
   // soft shadow, :105-132, :205
@@ -1903,9 +1944,60 @@ __device__ __forceinline__ float4 shade_pixel(KA& A, const Scene& scene, const V
     }
     sh = gclamp(s, 0.0f, 1.0f);
   }
-  const float dif = gclamp(ndl, 0.0f, 1.0f) * sh;
+  dif_out = gclamp(ndl, 0.0f, 1.0f) * sh;
+  spec_x_out = spec_x;
+}
+
+template <bool STEPS, class Scene, class View>
+__device__ __forceinline__ float4 shade_pixel(KA& A, const Scene& scene, const View& V, int x,
+                                              int y, int& sp, int& ss) {
+  MarchState mst;
+  Surface S;
+  trace_surface(A, scene, V, x, y, sp, mst, S);
+  float dif, spec_x;
+  light_terms<STEPS>(A, scene, V, S, mk(A.light_pos[0], A.light_pos[1], A.light_pos[2]), mst, ss,
+                     dif, spec_x);
   // ambient (+ AO extension) and the colour sum, :206-210: shade.h
-  return make_float4(ao, dif, spec_x, 1.0f);
+  return make_float4(S.ao, dif, spec_x, 1.0f);
+}
+
+// The pixel's colour under the launch's L.n lights (sdf_abi.h "Lights"): the
+// surface is traced once, then every light adds its diffuse and specular to
+// the three channels in index order.  Each light's shadow march starts from
+// a copy of the culling state the single-light kernel has at P, and its
+// terms come from the very light_terms above, so (dif_i, x_i) are the bits
+// sdf_render gives with that light alone.  The count, the colour flag and
+// the lights are uniforms of the kernel-argument segment: one kernel serves
+// every L, and the loop reads scalars.  `ss` sums the lights' shadow counts.
+template <bool STEPS, class Scene, class View>
+__device__ __forceinline__ float4 shade_pixel_lights(KA& A, const KARG LightsArgs& L,
+                                                     const Scene& scene, const View& V, int x,
+                                                     int y, int& sp, int& ss) {
+  MarchState mst;
+  Surface S;
+  trace_surface(A, scene, V, x, y, sp, mst, S);
+  float acc[3];
+#pragma unroll
+  for (int c = 0; c < 3; c++) acc[c] = shade_ambient(L.la * A.mat_amb[c], S.ao);
+  const bool tint = (L.flags & SDF_LIGHTS_COLOR) != 0;
+  const int n = L.n;
+#pragma unroll 1
+  for (int i = 0; i < n; i++) {
+    MarchState ms = mst;
+    int ssi = 0;
+    float dif, spec_x;
+    light_terms<STEPS>(A, scene, V, S, mk(L.pos[i][0], L.pos[i][1], L.pos[i][2]), ms, ssi, dif,
+                       spec_x);
+    ss += ssi;
+    const float spec = spec_pow<SDF_EXACT>(spec_x, A.shininess);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      const float d = tint ? shade_tint(dif, L.color[i][c]) : dif;
+      const float s = tint ? shade_tint(spec, L.color[i][c]) : spec;
+      acc[c] = shade_light<SDF_EXACT>(acc[c], A.mat_dif[c], A.mat_ref[c], d, s);
+    }
+  }
+  return make_float4(acc[0], acc[1], acc[2], 1.0f);
 }
 
 // The frame's shading constants (shade.h), as every pixel's colour uses them
@@ -1954,9 +2046,12 @@ __device__ __forceinline__ float ssaa_sum(float v, bool four) {
 // the encoder's registers never weigh on the plain-format kernels)
 // SSAA: the lanes are the sub-samples of a supersampled frame and the output
 // is their resolved pixels (render_ssaa, an instantiation of its own as well)
-template <class Scene, bool TILES, bool STEPS, bool SSAA = false>
+// LIGHTS: the pixel's colour is the sum over the launch's lights
+// (shade_pixel_lights; render_lights, instantiations of their own)
+template <class Scene, bool TILES, bool STEPS, bool SSAA = false, bool LIGHTS = false>
 __device__ __forceinline__ void render_body() {
   static_assert(!(TILES && SSAA), "a TILES stream carries shading terms, not colours");
+  static_assert(!(TILES && LIGHTS), "a TILES stream carries one light's terms");
   const KARG char* const seg = (const KARG char*)__builtin_amdgcn_kernarg_segment_ptr();
   KA& A = *(KA*)seg;
   const KARG RowOrder& O = *(const KARG RowOrder*)(seg + __builtin_offsetof(RenderArgs, o));
@@ -2012,7 +2107,13 @@ __device__ __forceinline__ void render_body() {
   int sp = 0, ss = 0;
   if (valid) {
     const Scene scene(A);
-    c = shade_pixel<STEPS>(A, scene, ArgsView{A}, x, y, sp, ss);
+    if constexpr (LIGHTS) {
+      const KARG LightsArgs& L =
+          *(const KARG LightsArgs*)(seg + __builtin_offsetof(RenderArgs, l));
+      c = shade_pixel_lights<STEPS>(A, L, scene, ArgsView{A}, x, y, sp, ss);   // the colour
+    } else {
+      c = shade_pixel<STEPS>(A, scene, ArgsView{A}, x, y, sp, ss);
+    }
   }
   const size_t o = (size_t)(A.frame_rows ? y : pr) * A.width + x;
   if (O.cost) {
@@ -2031,7 +2132,8 @@ __device__ __forceinline__ void render_body() {
     // every lane's colour, the group sums in the contract's tree order, and
     // the group's (0, 0) lane scales by 1 / S^2 (a power of two: one
     // rounding, denormals kept), converts and writes the output pixel
-    const float4 s = shade_colour<SDF_EXACT>(frame_shade(A), c.x, c.y, c.z);
+    float4 s = c;
+    if constexpr (!LIGHTS) s = shade_colour<SDF_EXACT>(frame_shade(A), c.x, c.y, c.z);
     const int lg = A.ss_log2;
     const bool four = lg == 2;
     const float sx = ssaa_sum(s.x, four), sy = ssaa_sum(s.y, four), sz = ssaa_sum(s.z, four);
@@ -2041,6 +2143,8 @@ __device__ __forceinline__ void render_body() {
       const size_t oo = (size_t)((A.frame_rows ? y : pr) >> lg) * A.out_width + (x >> lg);
       store_pixel(A.format, A.rgba, oo, make_float4(sx * w, sy * w, sz * w, 1.0f));
     }
+  } else if constexpr (LIGHTS) {
+    store_pixel(A.format, A.rgba, o, c);
   } else {
     store_pixel(A.format, A.rgba, o, pixel_value(A, A.format, c));
   }
@@ -2073,6 +2177,23 @@ __global__ __launch_bounds__(64 * kWgWaves) __attribute__((amdgpu_waves_per_eu(S
 void render_ssaa(RenderArgs args) {
   (void)args;
   render_body<Scene, false, STEPS, true>();
+}
+
+// the multi-light instantiations (sdf_render_lights; the count and the colour
+// flag are uniforms), with and without step recording and the supersampling
+// resolve.  P, N, ao, the channel sums and a copy of the culling state live
+// across the loop over the lights on top of a shadow march's registers, so
+// these kernels take an occupancy of their own (DESIGN.md, Lights)
+// (CSG8: 79 VGPRs fast, which 6 waves per SIMD hold; exact spilled 32 bytes
+// per lane there and takes 5)
+#ifndef SDF_LIGHTS_WAVES_PER_EU
+#define SDF_LIGHTS_WAVES_PER_EU (SDF_EXACT ? 5 : 6)
+#endif
+template <class Scene, bool STEPS, bool SSAA>
+__global__ __launch_bounds__(64 * kWgWaves) __attribute__((amdgpu_waves_per_eu(SDF_LIGHTS_WAVES_PER_EU, SDF_LIGHTS_WAVES_PER_EU)))
+void render_lights(RenderArgs args) {
+  (void)args;
+  render_body<Scene, false, STEPS, SSAA, true>();
 }
 
 // The persistent frame-sequence kernel (sdf_render_frames): every wave
@@ -2177,6 +2298,19 @@ static void launch_scene(const RenderArgs& a, dim3 grid, dim3 block, hipStream_t
       hipLaunchKernelGGL((SDF_NS::render_tiles<S, true, true>), grid, block, 0, s, a);
     else
       hipLaunchKernelGGL((SDF_NS::render_tiles<S, true, false>), grid, block, 0, s, a);
+  } else if (a.l.n > 0) {
+    // several lights (the host refuses TILES with them)
+    if (a.a.ss_log2 > 0) {
+      if (a.a.steps)
+        hipLaunchKernelGGL((SDF_NS::render_lights<S, true, true>), grid, block, 0, s, a);
+      else
+        hipLaunchKernelGGL((SDF_NS::render_lights<S, false, true>), grid, block, 0, s, a);
+    } else {
+      if (a.a.steps)
+        hipLaunchKernelGGL((SDF_NS::render_lights<S, true, false>), grid, block, 0, s, a);
+      else
+        hipLaunchKernelGGL((SDF_NS::render_lights<S, false, false>), grid, block, 0, s, a);
+    }
   } else if (a.a.ss_log2 > 0) {
     if (a.a.steps)
       hipLaunchKernelGGL((SDF_NS::render_ssaa<S, true>), grid, block, 0, s, a);
@@ -2199,6 +2333,11 @@ static dim3 render_grid(const KernelArgs& a) {
 static bool order_fits(const RenderArgs& r, dim3 grid) {
   return r.o.n == 0 || (r.o.n == (int)grid.y && r.o.n <= kMaxOrderBlocks);
 }
+// several lights: at most SDF_MAX_LIGHTS, and never into a TILES stream
+static bool lights_fit(const RenderArgs& r) {
+  return r.l.n == 0 || (r.l.n > 0 && r.l.n <= SDF_MAX_LIGHTS && r.a.format != SDF_FORMAT_TILES &&
+                        r.a.format != SDF_FORMAT_SHADE32F);
+}
 
 template <class S>
 static void launch_frames_scene(const FramesArgs& a, int nblocks, hipStream_t s) {
@@ -2215,7 +2354,7 @@ static void launch_frames_scene(const FramesArgs& a, int nblocks, hipStream_t s)
 int SDF_LAUNCH_BULB(const RenderArgs& a, void* stream) {
   const dim3 block = render_block(), grid = render_grid(a.a);
   if (grid.x == 0 || grid.y == 0) return 0;
-  if (!order_fits(a, grid)) return (int)hipErrorInvalidValue;
+  if (!order_fits(a, grid) || !lights_fit(a)) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
   if (a.a.format == SDF_FORMAT_TILES) launch_scene<SDF_NS::BulbScene, true>(a, grid, block, s);
@@ -2252,7 +2391,7 @@ int SDF_LAUNCH(const RenderArgs& a, int variant, void* stream) {
   if (variant == kVariantBulb) return SDF_LAUNCH_BULB(a, stream);   // its own unit
   const dim3 block = render_block(), grid = render_grid(a.a);
   if (grid.x == 0 || grid.y == 0) return 0;
-  if (!order_fits(a, grid)) return (int)hipErrorInvalidValue;
+  if (!order_fits(a, grid) || !lights_fit(a)) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   if (a.a.format == SDF_FORMAT_TILES) return launch_variant<true>(a, variant, grid, block, s);
   return launch_variant<false>(a, variant, grid, block, s);

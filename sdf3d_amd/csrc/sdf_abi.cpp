@@ -479,6 +479,7 @@ int launch_render_plan(const RenderPlan& plan, void* stream) {
   r.o.n = plan.order.n;
   r.o.reserved = 0;
   std::memcpy(r.o.order, plan.order.order, sizeof(uint16_t) * (size_t)std::max(plan.order.n, 0));
+  r.l = plan.lights;
   if (plan.jit) err = launch_render_jit(r, plan.sig, plan.nsig, plan.exact, stream);
   if (err == -1)
     err = plan.exact ? launch_render_exact(r, plan.variant, stream)
@@ -884,6 +885,66 @@ int sdf_render(const sdf_scene* scene, const sdf_camera* camera, const sdf_light
                                        steps, &plan);
   if (rc != SDF_OK) return rc;
   return sdf::launch_render_plan(plan, stream);
+}
+
+int sdf_validate_lights(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
+                        int32_t nlights, int32_t light_flags, const sdf_material* material,
+                        const sdf_params* params, const sdf_tiling* tiling) {
+  if (!lights || nlights < 1 || nlights > SDF_MAX_LIGHTS) return SDF_E_INVALID_ARG;
+  if (light_flags & ~SDF_LIGHTS_COLOR) return SDF_E_INVALID_ARG;
+  // every light as sdf_validate checks its one light
+  for (int i = 0; i < nlights; ++i) {
+    if (!finite3(lights[i].pos)) return SDF_E_INVALID_ARG;
+    for (float v : lights[i].pos)
+      if (std::fabs(v) > kMaxCoord) return SDF_E_INVALID_ARG;
+    // a colour is an arbitrary finite factor (negative ones included)
+    if ((light_flags & SDF_LIGHTS_COLOR) && !finite3(lights[i].color)) return SDF_E_INVALID_ARG;
+  }
+  const int rc = sdf_validate(scene, camera, &lights[0], material, params, tiling);
+  if (rc != SDF_OK) return rc;
+  // a TILES or SHADE32F stream carries one light's terms
+  if ((nlights > 1 || light_flags != 0) && (params->output_format == SDF_FORMAT_TILES ||
+                                            params->output_format == SDF_FORMAT_SHADE32F))
+    return SDF_E_UNSUPPORTED;
+  return SDF_OK;
+}
+
+int sdf_render_lights(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
+                      int32_t nlights, int32_t light_flags, const sdf_material* material,
+                      const sdf_params* params, const sdf_tiling* tiling, void* rgba,
+                      int32_t* steps, sdf_schedule* schedule, void* stream) {
+  int rc = sdf_validate_lights(scene, camera, lights, nlights, light_flags, material, params,
+                               tiling);
+  if (rc != SDF_OK) return rc;
+  // one plain light: sdf_render's own path, kernels and bits
+  if (nlights == 1 && light_flags == 0)
+    return sdf_render_scheduled(scene, camera, &lights[0], material, params, tiling, rgba, steps,
+                                schedule, stream);
+  sdf::RenderPlan plan;
+  rc = sdf::make_render_plan(scene, camera, &lights[0], material, params, tiling, rgba, steps,
+                             &plan);
+  if (rc != SDF_OK) return rc;
+  sdf::LightsArgs& l = plan.lights;
+  l.n = nlights;
+  l.flags = light_flags;
+  // the summed ambient: fp32, index order (this unit is built without
+  // contraction; one light gives its own value)
+  float la = lights[0].ambient;
+  for (int i = 1; i < nlights; ++i) la = la + lights[i].ambient;
+  l.la = la;
+  for (int i = 0; i < nlights; ++i)
+    for (int c = 0; c < 3; ++c) {
+      l.pos[i][c] = lights[i].pos[c];
+      l.color[i][c] = lights[i].color[c];
+    }
+  if (schedule) {
+    rc = sdf::schedule_apply(schedule->s, &plan);
+    if (rc != SDF_OK) return rc;
+  }
+  rc = sdf::launch_render_plan(plan, stream);
+  if (rc == SDF_OK && schedule && plan.rows == schedule->s->rows)
+    rc = sdf::schedule_after(schedule->s, stream);
+  return rc;
 }
 
 int sdf_jit_count(void) { return sdf::jit_compiled_count(); }

@@ -134,6 +134,29 @@ __device__ __forceinline__ float shade_channel(float lam, float md, float mr, fl
   }
 }
 
+// One light's diffuse and specular added to a channel's running sum (several
+// lights, sdf_abi.h "Lights"): shade_channel is shade_light(lam * ao, ...).
+// The sum starts from the ambient term lam * ao, and with SDF_LIGHTS_COLOR a
+// light's terms are first scaled by its colour: plain products, never fused.
+__device__ __forceinline__ float shade_ambient(float lam, float ao) {
+#pragma clang fp contract(off)
+  return lam * ao;
+}
+__device__ __forceinline__ float shade_tint(float term, float colour) {
+#pragma clang fp contract(off)
+  return term * colour;
+}
+template <bool EXACT>
+__device__ __forceinline__ float shade_light(float acc, float md, float mr, float dif,
+                                             float spec) {
+#pragma clang fp contract(off)
+  if constexpr (EXACT) {
+    return (acc + dif * md) + spec * mr;
+  } else {
+    return __builtin_fmaf(spec, mr, __builtin_fmaf(dif, md, acc));
+  }
+}
+
 template <bool EXACT>
 __device__ __forceinline__ float4 shade_colour(const ShadeK& K, float ao, float dif, float x) {
   const float spec = spec_pow<EXACT>(x, K.shin);

@@ -139,14 +139,18 @@ class Renderer:
         return Schedule(self, rows, period)
 
     def render(self, frame: Frame, t: abi.sdf_tiling | None = None, out=None,
-               steps=False, stream=None, schedule: "Schedule | None" = None):
+               steps=False, stream=None, schedule: "Schedule | None" = None,
+               lights=None, light_flags: int = 0):
         """Render the rows owned by tiling `t` (None = whole frame).
 
         Returns (rgba[rows, W, 4] float32, steps[rows, W, 2] int32 or None), both
         on the device, asynchronous on `stream` (default: torch's current).
         With ``frame.params.samples`` = S > 1 every pixel is the resolve of its
         S x S sub-samples and steps is (S rows, S W, 2): the sub-samples' counts.
-        `schedule`: dispatch order of the row blocks (sdf_render_scheduled)."""
+        `schedule`: dispatch order of the row blocks (sdf_render_scheduled).
+        `lights`: a sequence of 1 .. abi.MAX_LIGHTS ``abi.sdf_light`` lighting the
+        frame together (sdf_render_lights; ``frame.light`` is then ignored), with
+        `light_flags` (abi.LIGHTS_COLOR: every light scaled by its colour)."""
         torch = self.torch
         rows = buffer_rows(frame.params.height, t)
         w = frame.params.width
@@ -174,11 +178,20 @@ class Renderer:
                                or not st.is_contiguous()):
             raise ValueError(f"steps must be a contiguous int32 {sshape} tensor")
         with self._on_device():
-            args = (C.byref(frame.scene), C.byref(frame.camera), C.byref(frame.light),
-                    C.byref(frame.material), C.byref(frame.params),
+            tail = (C.byref(frame.material), C.byref(frame.params),
                     C.byref(t) if t is not None else None,
                     C.c_void_p(rgba.data_ptr()),
                     C.c_void_p(st.data_ptr()) if st is not None else None)
+            args = (C.byref(frame.scene), C.byref(frame.camera), C.byref(frame.light), *tail)
+            if lights is not None:
+                lights = list(lights)
+                arr = (abi.sdf_light * max(len(lights), 1))(*lights)
+                rc = self.lib.sdf_render_lights(
+                    C.byref(frame.scene), C.byref(frame.camera), arr, len(lights),
+                    int(light_flags), *tail,
+                    schedule.handle if schedule is not None else None, self._stream(stream))
+                abi.check(rc, "sdf_render_lights")
+                return rgba, st
             if schedule is None:
                 rc = self.lib.sdf_render(*args, self._stream(stream))
             else:
