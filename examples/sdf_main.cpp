@@ -5,7 +5,7 @@
 // cl->get_tic()/get_toc(), :89/:97) and clean up.  The last frame is written
 // as a PPM instead of being presented in a window (:95-96).
 //
-//   sdf_main [width height frames out.ppm scene [samples [lights]]]
+//   sdf_main [--palette] [width height frames out.ppm scene [samples [lights]]]
 //     scene: ref | csg8 | bulb; samples: 1 (default), 2 or 4 sub-samples per
 //     axis, resolved in the render kernel (single-GPU path only: the frame
 //     driver refuses supersampling)
@@ -14,6 +14,9 @@
 //     first carries the reference's ambient term, the others none; a light
 //     with r,g,b turns SDF_LIGHTS_COLOR on (lights without get white).  The
 //     default is the reference's one light.
+//     --palette (anywhere on the line): a material per primitive from
+//     sdf::palette, blended along the CSG fold (sdf_render_materials;
+//     single-GPU path only); a Mandelbulb gets the palette's first entry
 //
 // Multi-GPU: launched once per GPU by any launcher that sets RANK,
 // WORLD_SIZE and LOCAL_RANK (e.g. `torchrun --nproc-per-node 8 --no-python
@@ -179,6 +182,16 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
+  // --palette may stand anywhere: take it out of the positional arguments
+  bool use_palette = false;
+  {
+    int n = 1;
+    for (int i = 1; i < argc; ++i) {
+      if (std::string(argv[i]) == "--palette") use_palette = true;
+      else argv[n++] = argv[i];
+    }
+    argc = n;
+  }
   const int W = argc > 1 ? std::atoi(argv[1]) : 800;   // main.cpp:4 SX
   const int H = argc > 2 ? std::atoi(argv[2]) : 600;   // main.cpp:5 SY
   const int frames = argc > 3 ? std::atoi(argv[3]) : 8;
@@ -224,6 +237,11 @@ int main(int argc, char** argv) {
     if (std::getenv("WORLD_SIZE") || env("SDF3D_DRIVER", "0") == "1")
       return run_driver(f, frames, out);
 
+    std::vector<sdf_material> materials;
+    if (use_palette) {
+      materials = sdf::palette(f.scene.kind == SDF_SCENE_PRIMITIVES ? f.scene.count : 1);
+      if (lights.empty()) lights.push_back(f.light);   // the reference's one light
+    }
     hipStream_t stream;
     sdf::check_hip(hipStreamCreate(&stream), "hipStreamCreate");
     hipEvent_t t0, t1;
@@ -235,7 +253,8 @@ int main(int argc, char** argv) {
       for (int i = 0; i < frames; ++i) {
         nav.frame(f, i, frames);
         sdf::check_hip(hipEventRecord(t0, stream), "hipEventRecord");
-        if (lights.empty()) r.render(f);
+        if (use_palette) r.render(f, lights, light_flags, materials);
+        else if (lights.empty()) r.render(f);
         else r.render(f, lights, light_flags);
         sdf::check_hip(hipEventRecord(t1, stream), "hipEventRecord");
         sdf::check_hip(hipEventSynchronize(t1), "hipEventSynchronize");

@@ -227,6 +227,33 @@ class Arcball {
   double vyaw_ = 0, vpitch_ = 0, vpx_ = 0, vpy_ = 0;
 };
 
+// n (<= SDF_MAX_PRIMS) distinct materials, one per primitive, for
+// Renderer::render(f, lights, light_flags, materials): a fixed table (the
+// Python package's scenes.palette), amb = dif = the entry's colour, ref = its
+// reflectance on every channel, all with the same shininess
+// (sdf_render_materials keeps the exponent frame-wide).
+inline std::vector<sdf_material> palette(int n, float shininess = 12.0f) {
+  static const float kPalette[SDF_MAX_PRIMS][4] = {
+      {0.75f, 0.75f, 0.72f, 0.2f}, {0.85f, 0.15f, 0.1f, 0.5f}, {0.1f, 0.55f, 0.85f, 0.5f},
+      {0.95f, 0.7f, 0.1f, 0.6f},   {0.2f, 0.7f, 0.25f, 0.4f},  {0.6f, 0.25f, 0.75f, 0.5f},
+      {0.95f, 0.45f, 0.1f, 0.5f},  {0.1f, 0.75f, 0.7f, 0.6f},  {0.9f, 0.35f, 0.6f, 0.4f},
+      {0.35f, 0.3f, 0.85f, 0.5f},  {0.6f, 0.8f, 0.15f, 0.4f},  {0.55f, 0.35f, 0.2f, 0.3f},
+      {0.25f, 0.25f, 0.3f, 0.7f},  {0.95f, 0.9f, 0.8f, 0.3f},  {0.0f, 0.2f, 0.8f, 0.5f},
+      {0.5f, 0.05f, 0.15f, 0.6f}};
+  if (n < 0 || n > SDF_MAX_PRIMS) throw Error(SDF_E_INVALID_ARG, "palette: at most 16 entries");
+  std::vector<sdf_material> out(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) {
+    sdf_material m{};
+    for (int c = 0; c < 3; ++c) {
+      m.amb[c] = m.dif[c] = kPalette[i][c];
+      m.ref[c] = kPalette[i][3];
+    }
+    m.shininess = shininess;
+    out[static_cast<size_t>(i)] = m;
+  }
+  return out;
+}
+
 // Owns a device framebuffer and renders frames into it on one HIP stream.
 // The buffer holds width x height pixels of up to 16 bytes (any sdf_format).
 class Renderer {
@@ -260,6 +287,20 @@ class Renderer {
                             static_cast<int32_t>(lights.size()), light_flags, &f.material,
                             &f.params, tiling, rgba_, steps, schedule, stream_),
           "sdf_render_lights");
+  }
+  // The frame under `lights` with a material per primitive of the scene (one
+  // for a Mandelbulb; f.material is ignored), blended along the CSG fold at
+  // every pixel: sdf_render_materials.  sdf::palette(n) gives n distinct ones.
+  void render(const Frame& f, const std::vector<sdf_light>& lights, int32_t light_flags,
+              const std::vector<sdf_material>& materials, const sdf_tiling* tiling = nullptr,
+              int32_t* steps = nullptr, sdf_schedule* schedule = nullptr) {
+    if (f.params.width != w_ || f.params.height != h_)
+      throw Error(SDF_E_INVALID_ARG, "Renderer: frame size differs from framebuffer");
+    check(sdf_render_materials(&f.scene, &f.camera, lights.data(),
+                               static_cast<int32_t>(lights.size()), light_flags,
+                               materials.data(), static_cast<int32_t>(materials.size()),
+                               &f.params, tiling, rgba_, steps, schedule, stream_),
+          "sdf_render_materials");
   }
   // Blocking copy of an RGBA32F framebuffer (row 0 = bottom, GL order).
   std::vector<float> download() const {

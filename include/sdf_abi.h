@@ -74,7 +74,9 @@ extern "C" {
                                    sdf_render_lights (SDF_MAX_LIGHTS,
                                    SDF_LIGHTS_COLOR) are additions -- no struct
                                    and no existing entry point changed, so the
-                                   version stays; detect them by the symbol */
+                                   version stays; detect them by the symbol;
+                                still 12: sdf_validate_materials and
+                                   sdf_render_materials, additions likewise */
 
 /* ---- status codes ------------------------------------------------------ */
 #define SDF_OK               0
@@ -309,6 +311,58 @@ typedef struct {
  *     light.  Directional and spot lights, per-light shadow switches,
  *     attenuation and more than SDF_MAX_LIGHTS lights are not offered. */
 
+/* Materials (sdf_render_materials: materials[i] belongs to scene->prims[i];
+ * nmaterials = scene->count for a primitive scene, 1 for a Mandelbulb).  The
+ * frame is sdf_render_lights's with the one material replaced, per pixel, by
+ * a blend of the primitives' materials that follows the scene's CSG fold, so
+ * it can be checked bit for bit (tests/materials_ref.c states it in C over
+ * the CPU oracle):
+ *   - geometry and lights: the primary march, P, N, ao and every light's
+ *     (dif_i, x_i) are exactly those of sdf_render_lights; they do not depend
+ *     on the materials.
+ *   - the material fold: after the march the primitive list is evaluated once
+ *     more at P, every primitive, in list order, carrying the scene fold's
+ *     running distance d (+INF before primitive 0) and a running material m
+ *     of 9 components (amb, dif, ref), which starts as materials[0].  For
+ *     primitive i with value v = s_i(P) and blend radius k, (a, b) are the
+ *     arguments the scene fold hands to min / smooth-min:
+ *       UNION, SMOOTH_UNION           (a, b) = ( d,  v)
+ *       SUBTRACT, SMOOTH_SUBTRACT     (a, b) = (-d,  v)
+ *       INTERSECT, SMOOTH_INTERSECT   (a, b) = (-d, -v)
+ *     hard operators: t = (b < a) ? 1 : 0 -- on a tie the earlier owner stays,
+ *     and the cutter of a subtraction owns the surface it carves;
+ *     smooth operators: h = max(k - |a - b|, 0) / k, the smooth-min's own h
+ *     (exact precision: these fp32 operations with an IEEE division; fast
+ *     precision: the clamped fma(-|a - b|, 1/k, 1) of its smooth-min),
+ *     q = RN(RN(h h) 0.5), t = (b < a) ? RN(1 - q) : q;
+ *     each of the 9 components: unchanged for t = 0, materials[i]'s for t = 1,
+ *     else  exact precision  m = RN(m + RN(t RN(M_i - m)))   (never fused)
+ *           fast precision   m = fma(t, RN(M_i - m), m);
+ *     then d advances by the scene fold's combine.  There is no miss branch
+ *     (the reference has none): the fold runs at whatever P the march ended
+ *     on.  With d = +-INF, h = 0 and t is 0 or 1: no NaN arises.
+ *   - colour: the "Lights" colour sum with material.amb / dif / ref[c]
+ *     replaced by the pixel's blended components, lam[c] = RN(la amb_px[c]).
+ *   - shininess stays frame-wide: every entry must carry the bits of
+ *     materials[0].shininess (SDF_E_UNSUPPORTED otherwise).
+ *   - if the amb, dif and ref of all entries are byte-identical (always with
+ *     nmaterials = 1, so for a Mandelbulb) the call is sdf_render_lights with
+ *     materials[0]: the same kernels, every format, the same bits.
+ *   - output conversion, tilings, SDF_TILING_FRAME_ROWS, schedules, samples =
+ *     2 / 4 and `steps` work as in sdf_render_lights (the fold is not counted
+ *     in steps; a sub-sample's colour is its pixel's of the S W x S H frame).
+ *   - SDF_E_INVALID_ARG (sdf_validate_materials, and sdf_render_materials
+ *     before any device call): materials NULL; nmaterials not the scene's
+ *     count (1 for a Mandelbulb); anything sdf_validate_lights rejects
+ *     (sdf_validate checks a material's presence only, so an entry cannot
+ *     fail on its own).
+ *   - SDF_E_UNSUPPORTED: entries whose shininess differs; SDF_FORMAT_TILES or
+ *     SDF_FORMAT_SHADE32F with distinct materials (a stream carries one
+ *     material's constants).
+ *   - sdf_render_frames, sdf_render_multi and the frame driver keep their one
+ *     material.  Textures, procedural patterns and a shininess per primitive
+ *     are not offered. */
+
 /* Framebuffer element formats (4 channels R,G,B,A per pixel).
  *   RGBA32F  the shader's float fragment_color (voxel_fragment.frag:12,210).
  *   RGBA16F  IEEE half, round to nearest even.
@@ -522,6 +576,19 @@ int sdf_render_lights(const sdf_scene* scene, const sdf_camera* camera,
                       const sdf_material* material, const sdf_params* params,
                       const sdf_tiling* tiling, void* rgba, int32_t* steps,
                       sdf_schedule* schedule, void* stream);
+
+/* sdf_validate_lights / sdf_render_lights with a material per primitive
+ * ("Materials" above) in place of the one material.  Additions like the
+ * lights entry points: SDF_ABI_VERSION stays 12, detect them by the symbol. */
+int sdf_validate_materials(const sdf_scene* scene, const sdf_camera* camera,
+                           const sdf_light* lights, int32_t nlights, int32_t light_flags,
+                           const sdf_material* materials, int32_t nmaterials,
+                           const sdf_params* params, const sdf_tiling* tiling);
+int sdf_render_materials(const sdf_scene* scene, const sdf_camera* camera,
+                         const sdf_light* lights, int32_t nlights, int32_t light_flags,
+                         const sdf_material* materials, int32_t nmaterials,
+                         const sdf_params* params, const sdf_tiling* tiling, void* rgba,
+                         int32_t* steps, sdf_schedule* schedule, void* stream);
 
 /* Scatter `nparts` packed row-block buffers (part r = rank r's output for
  * tiling {block_rows, r, nparts}), laid out back to back in `parts` with a

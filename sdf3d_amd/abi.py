@@ -148,6 +148,13 @@ SIGNATURES = {
     "sdf_render_lights": (C.c_int, [_P(sdf_scene), _P(sdf_camera), _P(sdf_light), C.c_int32,
                                     C.c_int32, _P(sdf_material), _P(sdf_params), _P(sdf_tiling),
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sdf_validate_materials": (C.c_int, [_P(sdf_scene), _P(sdf_camera), _P(sdf_light), C.c_int32,
+                                         C.c_int32, _P(sdf_material), C.c_int32, _P(sdf_params),
+                                         _P(sdf_tiling)]),
+    "sdf_render_materials": (C.c_int, [_P(sdf_scene), _P(sdf_camera), _P(sdf_light), C.c_int32,
+                                       C.c_int32, _P(sdf_material), C.c_int32, _P(sdf_params),
+                                       _P(sdf_tiling), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
     "sdf_tiles_decode_checked": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _P(sdf_tiling),
                                            _P(C.c_int64), C.c_int32, C.c_int32, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

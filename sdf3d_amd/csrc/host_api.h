@@ -25,6 +25,7 @@ struct RenderPlan {
   uint32_t* tiles_used = nullptr;   // TILES: also receives the stream's length (device)
   RowOrder order{};        // dispatch order of the 8-row blocks (a Schedule's; n = 0: none)
   LightsArgs lights{};     // sdf_render_lights (n = 0: the one light of `a`)
+  MaterialArgs materials{};   // sdf_render_materials (n = 0: the one material of `a`)
 };
 
 // A render schedule (sdf_schedule): the dispatch order of a plan's 8-row

@@ -103,10 +103,21 @@ struct LightsArgs {
   int32_t flags;
   int32_t reserved;
 };
+// ---- per-primitive materials (sdf_render_materials) ------------------------
+// m[i] = primitive i's material as 9 components (amb, dif, ref), read with
+// scalar loads by the material fold at P (render_kernel.inc material_fold).
+// The shininess stays KernelArgs::shininess (frame-wide).  n = 0: one material
+// for the frame (KernelArgs::mat_*), nothing here is read.
+struct MaterialArgs {
+  float m[SDF_MAX_PRIMS][9];
+  int32_t n;
+  int32_t reserved[3];
+};
 struct RenderArgs {
   KernelArgs a;   // first: the kernels read it at the start of the segment
   RowOrder o;
   LightsArgs l;   // only RenderArgs has the room (FramesArgs is near 4 KiB)
+  MaterialArgs m; // behind the lights: a materials render always has lights (l.n >= 1)
 };
 
 // Waves (8x8 tiles side by side) per render workgroup (render_kernel.inc

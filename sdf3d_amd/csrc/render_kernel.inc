@@ -483,6 +483,42 @@ __device__ __forceinline__ float combine(int op, float d, float v, float k, floa
   }
 }
 
+// One primitive of the material fold (sdf_abi.h "Materials"): the running
+// material m[9] (amb, dif, ref) moves towards the primitive's `mi` by the
+// weight t its operator gives at the running distance d and the primitive's
+// value v, before `combine` advances d.  (a, b) are the arguments combine
+// hands to min / smin; a hard operator selects (b < a: the primitive owns the
+// surface, the earlier owner keeps a tie), a smooth one blends with the
+// smooth-min's own h.  Exact precision forms h with an IEEE division from
+// k = 4 (k/4) -- exact, sdf_validate keeps k in [2^-64, 1e15] -- because
+// crm::smin_h is only proven to give the right h h; fast precision's h is its
+// smin's clamped FMA.  d = +-INF (before primitive 0) gives h = 0 and t = 0
+// or 1 without a NaN.  Evaluated once per pixel, so none of this is tuned;
+// a wave whose lanes all keep their owner skips the nine updates.
+__device__ __forceinline__ void material_step(int op, float d, float v, float k4, float ik, KF mi,
+                                              float (&m)[9]) {
+  const bool smooth =
+      op == SDF_OP_SMOOTH_UNION || op == SDF_OP_SMOOTH_SUBTRACT || op == SDF_OP_SMOOTH_INTERSECT;
+  const float a = (op == SDF_OP_UNION || op == SDF_OP_SMOOTH_UNION) ? d : -d;
+  const float b = (op == SDF_OP_INTERSECT || op == SDF_OP_SMOOTH_INTERSECT) ? -v : v;
+  const bool nearer = b < a;
+  float t = nearer ? 1.0f : 0.0f;
+  if (smooth) {
+#if SDF_EXACT
+    (void)ik;
+    const float k = 4.0f * k4;
+    const float h = gmax(k - fabsf(a - b), 0.0f) / k;
+#else
+    (void)k4;
+    const float h = fminf(fmaxf(fmaf(-fabsf(a - b), ik, 1.0f), 0.0f), 1.0f);
+#endif
+    t = material_weight(h, nearer);
+  }
+  if (__builtin_amdgcn_ballot_w64(t != 0.0f) == 0) return;
+#pragma unroll
+  for (int c = 0; c < 9; c++) m[c] = material_mix<SDF_EXACT>(m[c], mi[c], t);
+}
+
 // Power-8 Mandelbulb DE, trig-free polynomial form (DESIGN.md Scene spec).
 #if SDF_EXACT
 // Measured and not kept (round 4, profiles/r04_ab_bulb_exact_C5.json, code
@@ -1114,6 +1150,20 @@ struct GenericScene {
     }
     return d;
   }
+  // the material fold at p (material_step): every primitive, unculled, in
+  // list order, d advanced as eval does
+  __device__ __forceinline__ void material_fold(V3 p, const KARG MaterialArgs& M,
+                                                float (&m)[9]) const {
+    float d = INFINITY;
+    const int n = A.prim_count;
+    for (int i = 0; i < n; i++) {
+      const KARG sdf_primitive& pr = A.prims[i];
+      KF q = pr.p;
+      const float v = prim_sdf(pr.kind, p, q);
+      material_step(pr.op, d, v, SMIN_K(pr), SMIN_IK(pr), M.m[i], m);
+      d = combine(pr.op, d, v, SMIN_K(pr), SMIN_IK(pr), SMIN_SC(pr), SMIN_KSC(pr));
+    }
+  }
 };
 
 // kinds whose value is never -0 (smin<HW>)
@@ -1326,6 +1376,27 @@ struct FixedScene {
       if (wave_near(cl[0], cl[1], cl[2], cl[3], p, d)) d = suffix(d, p, MakeSeq<N>{});
     }
     return d;
+  }
+  // The material fold at p (material_step), unrolled over the list: every
+  // primitive, unculled, with its compile-time kind and operator, d advanced
+  // by the march's own combine (apply), so it holds the bits it has there.
+  template <int I>
+  __device__ __forceinline__ void material_fold_step(float& d, V3 p, const KARG MaterialArgs& M,
+                                                     float (&m)[9]) const {
+    constexpr int ko = kKO[I];
+    const float v = prim_ct<(ko >> 3)>(p, q[I]);
+    material_step(ko & 7, d, v, k[I], ik[I], M.m[I], m);
+    d = apply<I, 0>(d, v);
+  }
+  template <int... I>
+  __device__ __forceinline__ void material_fold_seq(V3 p, const KARG MaterialArgs& M,
+                                                    float (&m)[9], Seq<I...>) const {
+    float d = INFINITY;
+    (material_fold_step<I>(d, p, M, m), ...);
+  }
+  __device__ __forceinline__ void material_fold(V3 p, const KARG MaterialArgs& M,
+                                                float (&m)[9]) const {
+    material_fold_seq(p, M, m, MakeSeq<N>{});
   }
   // Evaluation at a point p reached by a path of length t (see the pixel
   // pipeline: the primary ray, then side trips to the normal / AO taps and the
@@ -2000,6 +2071,54 @@ __device__ __forceinline__ float4 shade_pixel_lights(KA& A, const KARG LightsArg
   return make_float4(acc[0], acc[1], acc[2], 1.0f);
 }
 
+// shade_pixel_lights with a material per primitive (sdf_abi.h "Materials"):
+// between the surface and the lights the scene's material fold runs once at
+// P and leaves the pixel's blended amb, dif and ref.  The ambient part goes
+// into the channel sums at once, so only dif and ref (6 values) live across
+// the shadow marches.  trace_surface and light_terms are the shared ones:
+// P, N, ao, (dif_i, x_i) and the step counts are sdf_render_lights's bits.
+template <bool STEPS, class Scene, class View>
+__device__ __forceinline__ float4 shade_pixel_materials(KA& A, const KARG LightsArgs& L,
+                                                        const KARG MaterialArgs& M,
+                                                        const Scene& scene, const View& V, int x,
+                                                        int y, int& sp, int& ss) {
+  MarchState mst;
+  Surface S;
+  trace_surface(A, scene, V, x, y, sp, mst, S);
+  float acc[3], md[3], mr[3];
+  {
+    float m[9];
+#pragma unroll
+    for (int c = 0; c < 9; c++) m[c] = M.m[0][c];
+    scene.material_fold(S.P, M, m);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      acc[c] = shade_ambient(shade_tint(L.la, m[c]), S.ao);
+      md[c] = m[3 + c];
+      mr[c] = m[6 + c];
+    }
+  }
+  const bool tint = (L.flags & SDF_LIGHTS_COLOR) != 0;
+  const int n = L.n;
+#pragma unroll 1
+  for (int i = 0; i < n; i++) {
+    MarchState ms = mst;
+    int ssi = 0;
+    float dif, spec_x;
+    light_terms<STEPS>(A, scene, V, S, mk(L.pos[i][0], L.pos[i][1], L.pos[i][2]), ms, ssi, dif,
+                       spec_x);
+    ss += ssi;
+    const float spec = spec_pow<SDF_EXACT>(spec_x, A.shininess);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      const float d = tint ? shade_tint(dif, L.color[i][c]) : dif;
+      const float s = tint ? shade_tint(spec, L.color[i][c]) : spec;
+      acc[c] = shade_light<SDF_EXACT>(acc[c], md[c], mr[c], d, s);
+    }
+  }
+  return make_float4(acc[0], acc[1], acc[2], 1.0f);
+}
+
 // The frame's shading constants (shade.h), as every pixel's colour uses them
 __device__ __forceinline__ ShadeK frame_shade(KA& A) {
   ShadeK K;
@@ -2048,10 +2167,14 @@ __device__ __forceinline__ float ssaa_sum(float v, bool four) {
 // is their resolved pixels (render_ssaa, an instantiation of its own as well)
 // LIGHTS: the pixel's colour is the sum over the launch's lights
 // (shade_pixel_lights; render_lights, instantiations of their own)
-template <class Scene, bool TILES, bool STEPS, bool SSAA = false, bool LIGHTS = false>
+// MATERIALS (with LIGHTS): a material per primitive, blended at P
+// (shade_pixel_materials; render_materials, instantiations of their own)
+template <class Scene, bool TILES, bool STEPS, bool SSAA = false, bool LIGHTS = false,
+          bool MATERIALS = false>
 __device__ __forceinline__ void render_body() {
   static_assert(!(TILES && SSAA), "a TILES stream carries shading terms, not colours");
   static_assert(!(TILES && LIGHTS), "a TILES stream carries one light's terms");
+  static_assert(LIGHTS || !MATERIALS, "the materials kernels are lights kernels");
   const KARG char* const seg = (const KARG char*)__builtin_amdgcn_kernarg_segment_ptr();
   KA& A = *(KA*)seg;
   const KARG RowOrder& O = *(const KARG RowOrder*)(seg + __builtin_offsetof(RenderArgs, o));
@@ -2110,7 +2233,13 @@ __device__ __forceinline__ void render_body() {
     if constexpr (LIGHTS) {
       const KARG LightsArgs& L =
           *(const KARG LightsArgs*)(seg + __builtin_offsetof(RenderArgs, l));
-      c = shade_pixel_lights<STEPS>(A, L, scene, ArgsView{A}, x, y, sp, ss);   // the colour
+      if constexpr (MATERIALS) {
+        const KARG MaterialArgs& M =
+            *(const KARG MaterialArgs*)(seg + __builtin_offsetof(RenderArgs, m));
+        c = shade_pixel_materials<STEPS>(A, L, M, scene, ArgsView{A}, x, y, sp, ss);
+      } else {
+        c = shade_pixel_lights<STEPS>(A, L, scene, ArgsView{A}, x, y, sp, ss);   // the colour
+      }
     } else {
       c = shade_pixel<STEPS>(A, scene, ArgsView{A}, x, y, sp, ss);
     }
@@ -2194,6 +2323,29 @@ __global__ __launch_bounds__(64 * kWgWaves) __attribute__((amdgpu_waves_per_eu(S
 void render_lights(RenderArgs args) {
   (void)args;
   render_body<Scene, false, STEPS, SSAA, true>();
+}
+
+// the per-primitive material instantiations (sdf_render_materials): the
+// lights kernels with the material fold at P between the surface and the
+// lights (shade_pixel_materials); the fold's nine running components are dead
+// before the first shadow march, where the blended dif and ref (6 VGPRs) stay
+// live instead of uniform ones (DESIGN.md, Materials: the register figures
+// and the choice of occupancy)
+// (CSG8 exact: 96 VGPRs at the lights kernels' 5 waves per SIMD, no scratch.
+// CSG8 fast at their 6 waves: 80 VGPRs and 20-28 bytes of scratch per lane,
+// stored once before the loop over the lights and read back after it, one
+// dword per light inside it, none in a march; at 5 waves 87-90 VGPRs without
+// scratch, measured slower by about half a percent (1 light) and one percent
+// (4 lights) on C4 at 1080p (profiles/materials_C4.json, materials_w5), so 6
+// stays)
+#ifndef SDF_MATERIALS_WAVES_PER_EU
+#define SDF_MATERIALS_WAVES_PER_EU SDF_LIGHTS_WAVES_PER_EU
+#endif
+template <class Scene, bool STEPS, bool SSAA>
+__global__ __launch_bounds__(64 * kWgWaves) __attribute__((amdgpu_waves_per_eu(SDF_MATERIALS_WAVES_PER_EU, SDF_MATERIALS_WAVES_PER_EU)))
+void render_materials(RenderArgs args) {
+  (void)args;
+  render_body<Scene, false, STEPS, SSAA, true, true>();
 }
 
 // The persistent frame-sequence kernel (sdf_render_frames): every wave
@@ -2298,6 +2450,22 @@ static void launch_scene(const RenderArgs& a, dim3 grid, dim3 block, hipStream_t
       hipLaunchKernelGGL((SDF_NS::render_tiles<S, true, true>), grid, block, 0, s, a);
     else
       hipLaunchKernelGGL((SDF_NS::render_tiles<S, true, false>), grid, block, 0, s, a);
+  } else if (a.m.n > 0) {
+    // a material per primitive (lights_fit: never a Mandelbulb, which has no
+    // primitive list to fold over; never TILES)
+    if constexpr (!SDF_TU_BULB) {
+      if (a.a.ss_log2 > 0) {
+        if (a.a.steps)
+          hipLaunchKernelGGL((SDF_NS::render_materials<S, true, true>), grid, block, 0, s, a);
+        else
+          hipLaunchKernelGGL((SDF_NS::render_materials<S, false, true>), grid, block, 0, s, a);
+      } else {
+        if (a.a.steps)
+          hipLaunchKernelGGL((SDF_NS::render_materials<S, true, false>), grid, block, 0, s, a);
+        else
+          hipLaunchKernelGGL((SDF_NS::render_materials<S, false, false>), grid, block, 0, s, a);
+      }
+    }
   } else if (a.l.n > 0) {
     // several lights (the host refuses TILES with them)
     if (a.a.ss_log2 > 0) {
@@ -2338,6 +2506,12 @@ static bool lights_fit(const RenderArgs& r) {
   return r.l.n == 0 || (r.l.n > 0 && r.l.n <= SDF_MAX_LIGHTS && r.a.format != SDF_FORMAT_TILES &&
                         r.a.format != SDF_FORMAT_SHADE32F);
 }
+// a material per primitive: one per primitive of a primitive scene, with
+// lights (the materials kernels are lights kernels)
+static bool materials_fit(const RenderArgs& r) {
+  return r.m.n == 0 || (r.m.n == r.a.prim_count && r.m.n <= SDF_MAX_PRIMS && r.l.n > 0 &&
+                        r.a.scene_kind == SDF_SCENE_PRIMITIVES);
+}
 
 template <class S>
 static void launch_frames_scene(const FramesArgs& a, int nblocks, hipStream_t s) {
@@ -2354,7 +2528,8 @@ static void launch_frames_scene(const FramesArgs& a, int nblocks, hipStream_t s)
 int SDF_LAUNCH_BULB(const RenderArgs& a, void* stream) {
   const dim3 block = render_block(), grid = render_grid(a.a);
   if (grid.x == 0 || grid.y == 0) return 0;
-  if (!order_fits(a, grid) || !lights_fit(a)) return (int)hipErrorInvalidValue;
+  if (!order_fits(a, grid) || !lights_fit(a) || !materials_fit(a))
+    return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
   if (a.a.format == SDF_FORMAT_TILES) launch_scene<SDF_NS::BulbScene, true>(a, grid, block, s);
@@ -2391,7 +2566,8 @@ int SDF_LAUNCH(const RenderArgs& a, int variant, void* stream) {
   if (variant == kVariantBulb) return SDF_LAUNCH_BULB(a, stream);   // its own unit
   const dim3 block = render_block(), grid = render_grid(a.a);
   if (grid.x == 0 || grid.y == 0) return 0;
-  if (!order_fits(a, grid) || !lights_fit(a)) return (int)hipErrorInvalidValue;
+  if (!order_fits(a, grid) || !lights_fit(a) || !materials_fit(a))
+    return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   if (a.a.format == SDF_FORMAT_TILES) return launch_variant<true>(a, variant, grid, block, s);
   return launch_variant<false>(a, variant, grid, block, s);

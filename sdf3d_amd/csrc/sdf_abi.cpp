@@ -480,6 +480,7 @@ int launch_render_plan(const RenderPlan& plan, void* stream) {
   r.o.reserved = 0;
   std::memcpy(r.o.order, plan.order.order, sizeof(uint16_t) * (size_t)std::max(plan.order.n, 0));
   r.l = plan.lights;
+  r.m = plan.materials;
   if (plan.jit) err = launch_render_jit(r, plan.sig, plan.nsig, plan.exact, stream);
   if (err == -1)
     err = plan.exact ? launch_render_exact(r, plan.variant, stream)
@@ -936,6 +937,92 @@ int sdf_render_lights(const sdf_scene* scene, const sdf_camera* camera, const sd
     for (int c = 0; c < 3; ++c) {
       l.pos[i][c] = lights[i].pos[c];
       l.color[i][c] = lights[i].color[c];
+    }
+  if (schedule) {
+    rc = sdf::schedule_apply(schedule->s, &plan);
+    if (rc != SDF_OK) return rc;
+  }
+  rc = sdf::launch_render_plan(plan, stream);
+  if (rc == SDF_OK && schedule && plan.rows == schedule->s->rows)
+    rc = sdf::schedule_after(schedule->s, stream);
+  return rc;
+}
+
+// amb, dif and ref of two materials byte for byte (the shininess apart)
+static bool same_colours(const sdf_material& a, const sdf_material& b) {
+  return std::memcmp(a.amb, b.amb, sizeof(a.amb)) == 0 &&
+         std::memcmp(a.dif, b.dif, sizeof(a.dif)) == 0 &&
+         std::memcmp(a.ref, b.ref, sizeof(a.ref)) == 0;
+}
+// every entry's amb, dif and ref are materials[0]'s: the frame has one material
+static bool one_material(const sdf_material* materials, int32_t n) {
+  for (int i = 1; i < n; ++i)
+    if (!same_colours(materials[i], materials[0])) return false;
+  return true;
+}
+
+int sdf_validate_materials(const sdf_scene* scene, const sdf_camera* camera,
+                           const sdf_light* lights, int32_t nlights, int32_t light_flags,
+                           const sdf_material* materials, int32_t nmaterials,
+                           const sdf_params* params, const sdf_tiling* tiling) {
+  if (!materials || !scene) return SDF_E_INVALID_ARG;
+  // one material per primitive; a Mandelbulb has one
+  const int32_t want = scene->kind == SDF_SCENE_PRIMITIVES ? scene->count : 1;
+  if (nmaterials < 1 || nmaterials > SDF_MAX_PRIMS || nmaterials != want)
+    return SDF_E_INVALID_ARG;
+  // everything else as sdf_validate_lights checks it; sdf_validate's checks of
+  // a material are its presence alone, which holds for every entry here
+  const int rc = sdf_validate_lights(scene, camera, lights, nlights, light_flags, &materials[0],
+                                     params, tiling);
+  if (rc != SDF_OK) return rc;
+  // the exponent is frame-wide: the bits of materials[0].shininess everywhere
+  for (int i = 1; i < nmaterials; ++i)
+    if (std::memcmp(&materials[i].shininess, &materials[0].shininess, sizeof(float)) != 0)
+      return SDF_E_UNSUPPORTED;
+  // a TILES or SHADE32F stream carries one material's constants
+  if (!one_material(materials, nmaterials) && (params->output_format == SDF_FORMAT_TILES ||
+                                               params->output_format == SDF_FORMAT_SHADE32F))
+    return SDF_E_UNSUPPORTED;
+  return SDF_OK;
+}
+
+int sdf_render_materials(const sdf_scene* scene, const sdf_camera* camera,
+                         const sdf_light* lights, int32_t nlights, int32_t light_flags,
+                         const sdf_material* materials, int32_t nmaterials,
+                         const sdf_params* params, const sdf_tiling* tiling, void* rgba,
+                         int32_t* steps, sdf_schedule* schedule, void* stream) {
+  int rc = sdf_validate_materials(scene, camera, lights, nlights, light_flags, materials,
+                                  nmaterials, params, tiling);
+  if (rc != SDF_OK) return rc;
+  // one material for the whole frame (a Mandelbulb always): sdf_render_lights's
+  // own path, kernels and bits
+  if (one_material(materials, nmaterials))
+    return sdf_render_lights(scene, camera, lights, nlights, light_flags, &materials[0], params,
+                             tiling, rgba, steps, schedule, stream);
+  sdf::RenderPlan plan;
+  rc = sdf::make_render_plan(scene, camera, &lights[0], &materials[0], params, tiling, rgba,
+                             steps, &plan);
+  if (rc != SDF_OK) return rc;
+  // the lights as sdf_render_lights fills them: the materials kernels are
+  // lights kernels for every L >= 1, one plain light included
+  sdf::LightsArgs& l = plan.lights;
+  l.n = nlights;
+  l.flags = light_flags;
+  float la = lights[0].ambient;
+  for (int i = 1; i < nlights; ++i) la = la + lights[i].ambient;
+  l.la = la;
+  for (int i = 0; i < nlights; ++i)
+    for (int c = 0; c < 3; ++c) {
+      l.pos[i][c] = lights[i].pos[c];
+      l.color[i][c] = lights[i].color[c];
+    }
+  sdf::MaterialArgs& m = plan.materials;
+  m.n = nmaterials;
+  for (int i = 0; i < nmaterials; ++i)
+    for (int c = 0; c < 3; ++c) {
+      m.m[i][c] = materials[i].amb[c];
+      m.m[i][3 + c] = materials[i].dif[c];
+      m.m[i][6 + c] = materials[i].ref[c];
     }
   if (schedule) {
     rc = sdf::schedule_apply(schedule->s, &plan);

@@ -157,6 +157,29 @@ __device__ __forceinline__ float shade_light(float acc, float md, float mr, floa
   }
 }
 
+// Per-primitive materials (sdf_abi.h "Materials"): the weight q = RN(RN(h h)
+// 0.5) of a smooth operator's blend from its smooth-min's h, the weight t of
+// the incoming primitive (b < a: it is the nearer one), and one material
+// component moved towards the primitive's by t.  t = 0 and t = 1 select, so a
+// hard decision never rounds.  Plain operations in exact precision, one FMA
+// in fast precision.
+__device__ __forceinline__ float material_weight(float h, bool nearer) {
+#pragma clang fp contract(off)
+  const float q = (h * h) * 0.5f;
+  return nearer ? 1.0f - q : q;
+}
+template <bool EXACT>
+__device__ __forceinline__ float material_mix(float m, float mi, float t) {
+#pragma clang fp contract(off)
+  float r;
+  if constexpr (EXACT) {
+    r = m + t * (mi - m);
+  } else {
+    r = __builtin_fmaf(t, mi - m, m);
+  }
+  return t == 0.0f ? m : (t == 1.0f ? mi : r);
+}
+
 template <bool EXACT>
 __device__ __forceinline__ float4 shade_colour(const ShadeK& K, float ao, float dif, float x) {
   const float spec = spec_pow<EXACT>(x, K.shin);

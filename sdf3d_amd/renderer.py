@@ -140,7 +140,7 @@ class Renderer:
 
     def render(self, frame: Frame, t: abi.sdf_tiling | None = None, out=None,
                steps=False, stream=None, schedule: "Schedule | None" = None,
-               lights=None, light_flags: int = 0):
+               lights=None, light_flags: int = 0, materials=None):
         """Render the rows owned by tiling `t` (None = whole frame).
 
         Returns (rgba[rows, W, 4] float32, steps[rows, W, 2] int32 or None), both
@@ -150,7 +150,12 @@ class Renderer:
         `schedule`: dispatch order of the row blocks (sdf_render_scheduled).
         `lights`: a sequence of 1 .. abi.MAX_LIGHTS ``abi.sdf_light`` lighting the
         frame together (sdf_render_lights; ``frame.light`` is then ignored), with
-        `light_flags` (abi.LIGHTS_COLOR: every light scaled by its colour)."""
+        `light_flags` (abi.LIGHTS_COLOR: every light scaled by its colour).
+        `materials`: one ``abi.sdf_material`` per primitive of the scene (one for a
+        Mandelbulb), blended along the CSG fold at every pixel
+        (sdf_render_materials; ``frame.material`` is then ignored, and without
+        `lights` the frame is lit by ``frame.light``); ``scenes.palette(n)`` gives
+        n distinct ones."""
         torch = self.torch
         rows = buffer_rows(frame.params.height, t)
         w = frame.params.width
@@ -183,6 +188,17 @@ class Renderer:
                     C.c_void_p(rgba.data_ptr()),
                     C.c_void_p(st.data_ptr()) if st is not None else None)
             args = (C.byref(frame.scene), C.byref(frame.camera), C.byref(frame.light), *tail)
+            if materials is not None:
+                materials = list(materials)
+                marr = (abi.sdf_material * max(len(materials), 1))(*materials)
+                lights = [frame.light] if lights is None else list(lights)
+                arr = (abi.sdf_light * max(len(lights), 1))(*lights)
+                rc = self.lib.sdf_render_materials(
+                    C.byref(frame.scene), C.byref(frame.camera), arr, len(lights),
+                    int(light_flags), marr, len(materials), *tail[1:],
+                    schedule.handle if schedule is not None else None, self._stream(stream))
+                abi.check(rc, "sdf_render_materials")
+                return rgba, st
             if lights is not None:
                 lights = list(lights)
                 arr = (abi.sdf_light * max(len(lights), 1))(*lights)

@@ -122,6 +122,37 @@ def set_mandelbulb(scene: abi.sdf_scene, iterations: int = 12, bailout: float = 
     scene.bulb_bailout = bailout
 
 
+# (diffuse r, g, b, reflectance) of palette(): 16 distinct surface colours.
+# Entry 0 is a light grey for the ground plane most scenes start with.
+PALETTE = [
+    (0.75, 0.75, 0.72, 0.2), (0.85, 0.15, 0.1, 0.5), (0.1, 0.55, 0.85, 0.5),
+    (0.95, 0.7, 0.1, 0.6), (0.2, 0.7, 0.25, 0.4), (0.6, 0.25, 0.75, 0.5),
+    (0.95, 0.45, 0.1, 0.5), (0.1, 0.75, 0.7, 0.6), (0.9, 0.35, 0.6, 0.4),
+    (0.35, 0.3, 0.85, 0.5), (0.6, 0.8, 0.15, 0.4), (0.55, 0.35, 0.2, 0.3),
+    (0.25, 0.25, 0.3, 0.7), (0.95, 0.9, 0.8, 0.3), (0.0, 0.2, 0.8, 0.5),
+    (0.5, 0.05, 0.15, 0.6),
+]
+
+
+def palette(n: int = 16, shininess: float = 12.0) -> list:
+    """n (<= 16) distinct materials for ``Renderer.render(..., materials=...)``,
+    one per primitive: a fixed table, all with the same `shininess`
+    (sdf_render_materials keeps the exponent frame-wide).  amb = dif = the
+    entry's colour, ref = its reflectance on every channel."""
+    if not 0 <= n <= len(PALETTE):
+        raise ValueError(f"palette has {len(PALETTE)} entries")
+    out = []
+    for r, g, b, ref in PALETTE[:n]:
+        m = abi.sdf_material()
+        for c, v in enumerate((r, g, b)):
+            m.amb[c] = v
+            m.dif[c] = v
+            m.ref[c] = ref
+        m.shininess = shininess
+        out.append(m)
+    return out
+
+
 CONFIGS = {
     # name: (width, height, description)
     "C1": (512, 512, "single sphere, 64 max steps, primary + shadow + shading (CPU plumbing)"),
@@ -169,5 +200,5 @@ def config(name: str, width: int | None = None, height: int | None = None,
 
 
 __all__ = ["Frame", "orbit_view", "POSES", "reference", "config", "CONFIGS", "set_view",
-           "set_sphere_only", "set_csg8", "set_mandelbulb", "PRECISION_EXACT", "PRECISION_FAST",
-           "NORMAL_CENTRAL", "NORMAL_TETRA"]
+           "set_sphere_only", "set_csg8", "set_mandelbulb", "palette", "PALETTE",
+           "PRECISION_EXACT", "PRECISION_FAST", "NORMAL_CENTRAL", "NORMAL_TETRA"]

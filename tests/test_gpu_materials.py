@@ -1,0 +1,463 @@
+"""GPU tests of per-primitive materials (sdf_render_materials; include/sdf_abi.h
+"Materials"): the frame is the multi-light composition with every pixel's own
+blended material (tests/materials_ref.py compose_px) -- bit for bit and on
+every pixel against the CPU oracle and the reference fold in exact precision,
+against the kernel's own probed fold in both precisions, within a measured
+bound against the reference fold in fast precision -- on every dispatch path,
+for every output format, tiling, a schedule and supersampling, with
+sdf_render_lights's step counts.
+
+Shape 37 x 23 (partial 8 x 8 tiles in x and y, a last block of 7 rows); the
+supersampled cases use test_gpu_ssaa.py's shapes.  Every render writes into
+buffers followed by sentinel rows, which must survive, and every case is
+rendered with and without a steps buffer, which must not change the colours.
+The SIX scenes run the generic kernel except where a test is about the path."""
+import ctypes as C
+import os
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import lights_ref as LR
+import materials_ref as MR
+import oracle
+import ssaa_ref
+from parity import quantize
+from sdf3d_amd import abi, renderer as R, scenes
+from test_gpu_lights import own_light
+from test_gpu_ssaa import (FILL, SHAPES, _guarded, _sentinel, bits, hi_frame, owned_row_index,
+                           read_ppm, same)
+
+pytestmark = pytest.mark.gpu
+
+EXACT, FAST = abi.PRECISION_EXACT, abi.PRECISION_FAST
+PRECS = [EXACT, FAST]
+FLAGS = [0, abi.LIGHTS_COLOR]
+LIGHTS = LR.rig(8)
+# Fast precision's blended components against the reference fold replayed at
+# the kernel's step counts, where no hard decision is closer than MR.GAP: the
+# largest absolute deviation measured on C4 and SIX on an MI355X (C4 1.25e-6
+# on 851 of 851 pixels, SIX and SIXH 2.21e-6 on 849 of 851; DESIGN.md
+# "Materials", profiles/materials_C4.json fast_fold_deviation), and the bound
+# asserted: 4 x that, the headroom the fast policy allows other poses.
+FAST_MEASURED = 2.21e-6
+FAST_BOUND = 4 * FAST_MEASURED
+
+
+def hard_union(prec, wh=MR.SHAPE, swapped=False):
+    """plane, capsule, box in hard union (`swapped`: plane, box, capsule): no
+    built-in variant, so SDF_DISPATCH_AUTO compiles its kernel at run time
+    (hipRTC); signatures no other test file uses, and `swapped` only the test
+    that counts its compilations."""
+    f = scenes.config("C3", *wh, precision=prec, pose=2)
+    C.memset(C.addressof(f.scene.prims), 0, C.sizeof(f.scene.prims))
+    f.scene.count = 3
+    scenes._prim(f.scene, 0, abi.PRIM_PLANE, abi.OP_UNION, 0.0, 0.0, 1.0, 0.0, 0.0)
+    cap, box = (2, 1) if swapped else (1, 2)
+    scenes._prim(f.scene, cap, abi.PRIM_CAPSULE, abi.OP_UNION, 0.0, -0.4, 0.1, 0.2, 0.3, 0.4,
+                 -0.1, 0.12)
+    scenes._prim(f.scene, box, abi.PRIM_BOX, abi.OP_UNION, 0.0, 0.5, 0.15, 0.1, 0.15, 0.15, 0.15)
+    return f
+
+
+def frame_of(name, pose, prec=EXACT, dispatch=None):
+    """The frame `name` (materials_ref.FRAMES, or HU: hard_union).  SIX and SIXH
+    run the generic kernel unless `dispatch` says otherwise."""
+    f = hard_union(prec) if name == "HU" else MR.frame_of(name, pose, prec)
+    if dispatch is None:
+        dispatch = abi.DISPATCH_GENERIC if name in ("SIX", "SIXH") else abi.DISPATCH_AUTO
+    f.params.dispatch = dispatch
+    return f
+
+
+def render(rd, frame, materials=None, lights=None, flags=0, t=None, steps=True, schedule=None):
+    """Renderer.render (with `materials`: sdf_render_materials) into
+    sentinel-filled buffers with guard rows behind them, which are checked."""
+    import torch
+    p = frame.params
+    rows = R.buffer_rows(p.height, t)
+    shape = (rows, p.width, R.channels(p.output_format))
+    buf = _guarded(torch, rd.device, shape, R.torch_dtype(p.output_format))
+    sshape = R.steps_shape(frame, t)
+    sbuf = _guarded(torch, rd.device, sshape, torch.int32) if steps else None
+    rd.render(frame, t, out=buf[:rows], steps=sbuf[:sshape[0]] if steps else False,
+              schedule=schedule, lights=lights, light_flags=flags, materials=materials)
+    torch.cuda.synchronize()
+    assert _sentinel(torch, buf[rows:]), "colour buffer: rows past the end were written"
+    if steps:
+        assert _sentinel(torch, sbuf[sshape[0]:]), "steps buffer: rows past the end were written"
+    return buf[:rows].cpu().numpy(), (sbuf[:sshape[0]].cpu().numpy() if steps else None)
+
+
+def both(rd, frame, materials=None, lights=None, flags=0, t=None):
+    a, _ = render(rd, frame, materials, lights, flags, t, steps=False)
+    b, st = render(rd, frame, materials, lights, flags, t, steps=True)
+    assert same(a, b), "renders with and without a steps buffer differ"
+    return a, st
+
+
+def ndiff(a, b):
+    a, b = (np.ascontiguousarray(v).view(np.uint32) for v in (a, b))
+    return int((a != b).sum())
+
+
+# ---- references, computed once and shared read-only ---------------------------
+
+_ORACLE = {}
+_FOLD = {}
+_PROBE = {}
+
+
+def oracle_light(name, pose, i):
+    """(terms, steps) of the oracle for the frame under rig light i alone."""
+    key = (name, pose, i)
+    if key not in _ORACLE:
+        g = LR.with_light(frame_of(name, pose), LIGHTS[i])
+        terms = oracle.render_terms(g)
+        _, steps = oracle.render(g)
+        assert np.isfinite(terms).all(), key
+        terms.setflags(write=False)
+        steps.setflags(write=False)
+        _ORACLE[key] = (terms, steps)
+    return _ORACLE[key]
+
+
+def ref_fold(name, pose):
+    """The reference fold of the frame with its palette."""
+    key = (name, pose)
+    if key not in _FOLD:
+        f = frame_of(name, pose)
+        r = MR.fold(f, MR.palette_for(f))
+        for k in ("amb", "dif", "ref"):
+            assert np.isfinite(r[k]).all(), key
+        for v in r.values():
+            v.setflags(write=False)
+        _FOLD[key] = r
+    return _FOLD[key]
+
+
+def check_reference(rd, name, pose, n, flags, dispatch=None):
+    """Check 1: the exact frame is compose_px(oracle terms, reference fold) on
+    every pixel, with sdf_render_lights's (and the oracle's) step counts."""
+    f = frame_of(name, pose, EXACT, dispatch)
+    parts = [oracle_light(name, pose, i) for i in range(n)]
+    r = ref_fold(name, pose)
+    want = MR.compose_px(f, [p[0] for p in parts], LIGHTS[:n], r["amb"], r["dif"], r["ref"], flags)
+    out, st = both(rd, f, MR.palette_for(f), LIGHTS[:n], flags)
+    print(f"differing words {ndiff(out, want)} of {out.size}")
+    assert same(out, want), ndiff(out, want)
+    _, lights_st = render(rd, f, None, LIGHTS[:n], flags, steps=True)
+    assert np.array_equal(st, lights_st)
+    want_st = parts[0][1].copy()
+    want_st[..., 1] = sum(p[1][..., 1] for p in parts)
+    assert np.array_equal(st, want_st)
+    return out
+
+
+def probe(rd, f, key=None):
+    """The kernel's own blended (amb, dif, ref) of `f` with its palette, bit for
+    bit, and the probe renders' steps: three renders under one light of
+    ambient 1 with AO off, whose materials carry the real amb, dif or ref as
+    their amb and zero dif and ref -- the colour is then la amb_px = amb_px."""
+    if key is not None and key in _PROBE:
+        return _PROBE[key]
+    g = f.copy()
+    g.params.flags &= ~abi.FLAG_AO
+    light = type(LIGHTS[0]).from_buffer_copy(LIGHTS[0])
+    light.ambient = 1.0
+    out, st = [], None
+    for field in ("amb", "dif", "ref"):
+        mats = []
+        for m in MR.palette_for(f):
+            q = abi.sdf_material()
+            q.shininess = m.shininess
+            for c in range(3):
+                q.amb[c] = getattr(m, field)[c]
+            mats.append(q)
+        rgba, st = both(rd, g, mats, [light], 0)
+        assert np.isfinite(rgba).all()
+        out.append(rgba[..., :3].copy())
+    for a in (*out, st):
+        a.setflags(write=False)
+    if key is not None:
+        _PROBE[key] = (out, st)
+    return out, st
+
+
+def check_own(rd, name, pose, n, flags, prec, dispatch=None):
+    """Check 2: the frame is compose_px(own terms, own specs, probed fold)."""
+    f = frame_of(name, pose, prec, dispatch)
+    mats = MR.palette_for(f)
+    assert all(m.shininess == f.material.shininess for m in mats)
+    key = (name, pose, prec, f.params.dispatch)
+    (amb, dif, ref), _ = probe(rd, f, key)
+    lights = LIGHTS[:n]
+    parts = [own_light(rd, f, l, ("materials", *key, i)) for i, l in enumerate(lights)]
+    want = MR.compose_px(f, [p[0] for p in parts], lights, amb, dif, ref, flags, prec,
+                         specs=[p[1] for p in parts])
+    want_st = parts[0][2].copy()
+    want_st[..., 1] = sum(p[2][..., 1] for p in parts)
+    out, st = both(rd, f, mats, lights, flags)
+    print(f"differing words {ndiff(out, want)} of {out.size}")
+    assert same(out, want), ndiff(out, want)
+    assert np.array_equal(st, want_st)
+    if prec == EXACT:
+        r = ref_fold(name, pose)
+        for got, k in zip((amb, dif, ref), ("amb", "dif", "ref")):
+            assert same(got, r[k]), k
+    return out
+
+
+# ---- 1. exact precision against the reference -----------------------------------
+
+@pytest.mark.parametrize("flags", FLAGS)
+@pytest.mark.parametrize("n", [1, 3])
+@pytest.mark.parametrize("name,pose", MR.FRAMES)
+def test_exact_equals_reference(renderer, name, pose, n, flags):
+    check_reference(renderer, name, pose, n, flags)
+
+
+# ---- 2. both precisions against the kernel's own fold ---------------------------
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("flags", FLAGS)
+@pytest.mark.parametrize("n", [1, 3])
+@pytest.mark.parametrize("name,pose", [("C4", 0), ("SIX", 2)])
+def test_equals_own_terms_and_fold(renderer, name, pose, n, flags, prec):
+    oracle_light(name, pose, n - 1)            # the inputs are finite
+    check_own(renderer, name, pose, n, flags, prec)
+
+
+# ---- 3. fast precision against the reference ------------------------------------
+
+@pytest.mark.parametrize("name,pose", [("C4", 0), ("SIX", 2), ("SIXH", 2)])
+def test_fast_fold_is_near_the_reference(renderer, name, pose):
+    """The fast kernel's probed components against the reference fold with the
+    primary march replayed at the kernel's recorded step counts, on the pixels
+    whose hard decisions are all at least MR.GAP apart (the others: at most
+    2 %, tests/test_materials_ref.py).
+    Measured on an MI355X: 1.25e-6 (C4), 2.21e-6 (SIX, SIXH); the bound is
+    4 x the largest, FAST_BOUND = 8.84e-6."""
+    f = frame_of(name, pose, FAST)
+    (amb, dif, ref), st = probe(renderer, f, (name, pose, FAST, f.params.dispatch))
+    r = MR.fold(frame_of(name, pose), MR.palette_for(f), steps=st)
+    keep = r["min_gap"] >= MR.GAP
+    assert keep.mean() >= 0.98
+    dev = max(float(np.abs(got[keep].astype(np.float64) - r[k][keep]).max())
+              for got, k in zip((amb, dif, ref), ("amb", "dif", "ref")))
+    everywhere = max(float(np.abs(got.astype(np.float64) - r[k]).max())
+                     for got, k in zip((amb, dif, ref), ("amb", "dif", "ref")))
+    print(f"{name}: largest deviation {dev:.3e} on {int(keep.sum())} of {keep.size} pixels "
+          f"(all pixels: {everywhere:.3e}); bound {FAST_BOUND:.3e}")
+    assert dev <= FAST_BOUND
+
+
+# ---- 4. degenerate cases: one material is sdf_render_lights ----------------------
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("fmt", [abi.FORMAT_RGBA32F, abi.FORMAT_RGBA16F, abi.FORMAT_RGBA8,
+                                 abi.FORMAT_RGB32F, abi.FORMAT_SHADE32F])
+def test_identical_materials_are_sdf_render_lights(renderer, fmt, prec):
+    f = frame_of("C4", 0, prec)
+    f.params.output_format = fmt
+    mats = [type(f.material).from_buffer_copy(f.material) for _ in range(f.scene.count)]
+    # a term stream carries one plain light; the other formats take the rig
+    lights, flags = ([LIGHTS[1]], 0) if fmt == abi.FORMAT_SHADE32F else (LIGHTS[:3],
+                                                                         abi.LIGHTS_COLOR)
+    want, want_st = both(renderer, f, None, lights, flags)
+    g = f.copy()                                # frame.material is ignored
+    for c in range(3):
+        g.material.dif[c] = 0.125
+    out, st = both(renderer, g, mats, lights, flags)
+    assert same(out, want) and np.array_equal(st, want_st)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_identical_materials_tiles_stream(renderer, prec):
+    import torch
+    f = frame_of("C4", 0, prec)
+    f.params.output_format = abi.FORMAT_TILES
+    mats = [type(f.material).from_buffer_copy(f.material) for _ in range(f.scene.count)]
+    w, h = f.params.width, f.params.height
+    a, b = (torch.zeros(R.tiles_bytes(w, h), dtype=torch.uint8, device=renderer.device)
+            for _ in range(2))
+    renderer.render(f, out=a, lights=[LIGHTS[1]])
+    renderer.render(f, out=b, lights=[LIGHTS[1]], materials=mats)
+    torch.cuda.synchronize()
+    n = R.tiles_stream_bytes(a)
+    assert n == R.tiles_stream_bytes(b) and n > abi.TILES_HEADER_BYTES
+    assert torch.equal(a[:n], b[:n])
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_mandelbulb_with_its_one_material(renderer, prec):
+    f = scenes.config("C5", *MR.SHAPE, precision=prec, pose=3)
+    m = scenes.palette(4)[3]
+    g = f.copy()
+    g.material = type(m).from_buffer_copy(m)
+    for fmt in (abi.FORMAT_RGBA32F, abi.FORMAT_RGBA8):
+        f.params.output_format = g.params.output_format = fmt
+        want, want_st = both(renderer, g, None, LIGHTS[:2], abi.LIGHTS_COLOR)
+        out, st = both(renderer, f, [m], LIGHTS[:2], abi.LIGHTS_COLOR)
+        assert same(out, want) and np.array_equal(st, want_st)
+
+
+# ---- 5. dispatch paths -------------------------------------------------------------
+
+PATHS = [("SIX", 2, abi.DISPATCH_GENERIC), ("SIX", 2, abi.DISPATCH_UNCULLED),
+         ("SIXH", 2, abi.DISPATCH_UNCULLED), ("C4", 0, abi.DISPATCH_AUTO),
+         ("C3", 2, abi.DISPATCH_GENERIC), ("HU", 2, abi.DISPATCH_AUTO)]
+
+
+@pytest.mark.parametrize("name,pose,dispatch", PATHS)
+def test_paths_exact_equals_reference(renderer, name, pose, dispatch):
+    check_reference(renderer, name, pose, 3, abi.LIGHTS_COLOR, dispatch)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("name,pose,dispatch", PATHS)
+def test_paths_equal_own_terms_and_fold(renderer, name, pose, dispatch, prec):
+    oracle_light(name, pose, 2)
+    check_own(renderer, name, pose, 3, abi.LIGHTS_COLOR, prec, dispatch)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_runtime_specialised_scene_compiles_one_kernel(renderer, prec):
+    """A scene without a built-in variant: one run-time compiled materials
+    kernel serves every light count and the colour flag (one more with step
+    recording, one more with supersampling)."""
+    f = hard_union(prec, swapped=True)
+    mats = MR.palette_for(f)
+    jit = os.environ.get("SDF3D_JIT") != "0"
+    count = renderer.lib.sdf_jit_count
+    generic = f.copy()
+    generic.params.dispatch = abi.DISPATCH_GENERIC
+    want, want_st = both(renderer, generic, mats, LIGHTS[:3], 0)
+    before = count()
+    for flags in FLAGS:
+        for n in (3, 1):
+            out, _ = render(renderer, f, mats, LIGHTS[:n], flags, steps=False)
+            assert count() - before == (1 if jit else 0)
+    out, _ = render(renderer, f, mats, LIGHTS[:3], 0, steps=False)
+    assert same(out, want)
+    out, st = render(renderer, f, mats, LIGHTS[:3], 0, steps=True)
+    assert same(out, want) and np.array_equal(st, want_st)
+    assert count() - before == (2 if jit else 0)
+    g = f.copy()
+    g.params.width, g.params.height, g.params.samples = SHAPES[2][0], SHAPES[2][1], 2
+    render(renderer, g, mats, LIGHTS[:3], 0, steps=False)
+    render(renderer, g, mats, LIGHTS[:2], abi.LIGHTS_COLOR, steps=False)
+    assert count() - before == (3 if jit else 0)
+
+
+# ---- 6. output formats -------------------------------------------------------------
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("flags", FLAGS)
+def test_formats_convert_the_colour(renderer, flags, prec):
+    oracle_light("C4", 0, 2)
+    f = frame_of("C4", 0, prec)
+    mats = MR.palette_for(f)
+    full, _ = render(renderer, f, mats, LIGHTS[:3], flags, steps=False)
+    for fmt in (abi.FORMAT_RGBA16F, abi.FORMAT_RGBA8, abi.FORMAT_RGB32F):
+        g = f.copy()
+        g.params.output_format = fmt
+        out, _ = both(renderer, g, mats, LIGHTS[:3], flags)
+        assert same(out, quantize(full, fmt)), fmt
+
+
+# ---- 7. supersampling --------------------------------------------------------------
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("s", [2, 4])
+@pytest.mark.parametrize("name", ["C3", "SIX"])
+def test_supersampled(renderer, name, s, prec):
+    f = MR.frame_of(name, 2, prec, wh=SHAPES[s])
+    if name == "SIX":
+        f.params.dispatch = abi.DISPATCH_GENERIC
+    f.params.samples = s
+    mats = MR.palette_for(f)
+    assert np.isfinite(oracle.render(hi_frame(f))[0]).all()
+    for flags in FLAGS:
+        hi, hi_st = both(renderer, hi_frame(f), mats, LIGHTS[:2], flags)
+        out, st = both(renderer, f, mats, LIGHTS[:2], flags)
+        assert same(out, ssaa_ref.resolve(hi, s)) and np.array_equal(st, hi_st)
+
+
+# ---- 8. tilings --------------------------------------------------------------------
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("world,shares", [(3, (1, 1)), (2, (1, 2))])
+def test_tilings(renderer, world, shares, prec):
+    oracle_light("C3", 2, 1)
+    f = frame_of("C3", 2, prec)
+    mats = MR.palette_for(f)
+    w, h = f.params.width, f.params.height
+    lights, flags = LIGHTS[:2], abi.LIGHTS_COLOR
+    whole, whole_st = both(renderer, f, mats, lights, flags)
+    seen = np.zeros(h, dtype=int)
+    for rank in range(world):
+        t = R.tiling(rank, world, 8, shares=shares)
+        rows = owned_row_index(h, t)
+        assert len(rows) == R.owned_rows(h, t)
+        seen[rows] += 1
+        out, st = both(renderer, f, mats, lights, flags, t)
+        assert out.shape == (len(rows), w, 4)
+        assert same(out, whole[rows]) and np.array_equal(st, whole_st[rows])
+        tf = R.tiling(rank, world, 8, frame_rows=True, shares=shares)
+        fr, fr_st = both(renderer, f, mats, lights, flags, tf)
+        other = np.setdiff1d(np.arange(h), rows)
+        assert same(fr[rows], whole[rows]) and np.array_equal(fr_st[rows], whole_st[rows])
+        assert (bits(fr[other]) == FILL).all() and (bits(fr_st[other]) == FILL).all()
+    assert (seen == 1).all()
+
+
+# ---- 9. schedule -------------------------------------------------------------------
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_scheduled(renderer, prec):
+    oracle_light("C3", 2, 1)
+    f = frame_of("C3", 2, prec)
+    mats = MR.palette_for(f)
+    ref, ref_st = render(renderer, f, mats, LIGHTS[:2], 0, steps=True)
+    sch = renderer.schedule(f.params.height, period=1)
+    try:
+        for _ in range(3):
+            out, st = render(renderer, f, mats, LIGHTS[:2], 0, steps=True, schedule=sch)
+            assert same(out, ref) and np.array_equal(st, ref_st)
+        assert sorted(sch.order()) == list(range((f.params.height + 7) // 8))
+    finally:
+        sch.close()
+
+
+# ---- 10. the C++ host program -------------------------------------------------------
+
+def test_cpp_host_program_palette_option(renderer, tmp_path):
+    exe = Path(__file__).resolve().parent.parent / "sdf3d_amd" / "bin" / "sdf_main"
+    assert exe.exists(), "build() must produce sdf3d_amd/bin/sdf_main"
+    f = scenes.config("C3", 160, 90, precision=EXACT)                 # sdf_main's default
+    scenes.set_view(f, scenes.orbit_view(180.0, 0.0))                 # frame 1 of 2: yaw 180
+    lights = LR.rig(2)
+    lights[0].ambient, lights[1].ambient = f.light.ambient, 0.0
+    for c in range(3):
+        lights[0].color[c] = 1.0
+    f.params.output_format = abi.FORMAT_RGBA8
+    want, _ = render(renderer, f, scenes.palette(8), lights, abi.LIGHTS_COLOR, steps=False)
+    plain, _ = render(renderer, f, None, lights, abi.LIGHTS_COLOR, steps=False)
+    assert not same(want, plain)
+    out = tmp_path / "f.ppm"
+    r = subprocess.run([str(exe), "160", "90", "2", str(out), "csg8", "1",
+                        "-4,3,3;-2,0.6,1,0.25,0.5,1", "--palette"], capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    img = read_ppm(out)
+    assert img.shape == (90, 160, 3)
+    assert np.array_equal(img, want[::-1, :, :3])
+    # without lights on the line: the reference's one light
+    one, _ = render(renderer, f, scenes.palette(8), [f.light], 0, steps=False)
+    r = subprocess.run([str(exe), "--palette", "160", "90", "2", str(out), "csg8"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert np.array_equal(read_ppm(out), one[::-1, :, :3])
