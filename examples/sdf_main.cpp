@@ -5,7 +5,8 @@
 // cl->get_tic()/get_toc(), :89/:97) and clean up.  The last frame is written
 // as a PPM instead of being presented in a window (:95-96).
 //
-//   sdf_main [--palette] [width height frames out.ppm scene [samples [lights]]]
+//   sdf_main [--palette] [--reflect B[,strength]]
+//            [width height frames out.ppm scene [samples [lights]]]
 //     scene: ref | csg8 | bulb; samples: 1 (default), 2 or 4 sub-samples per
 //     axis, resolved in the render kernel (single-GPU path only: the frame
 //     driver refuses supersampling)
@@ -17,6 +18,10 @@
 //     --palette (anywhere on the line): a material per primitive from
 //     sdf::palette, blended along the CSG fold (sdf_render_materials;
 //     single-GPU path only); a Mandelbulb gets the palette's first entry
+//     --reflect B[,strength] (anywhere on the line): B = 0 .. SDF_MAX_BOUNCES
+//     mirror bounces per pixel, every surface's ref times strength (default
+//     1) weighting what it reflects (sdf_render_reflect; single-GPU path
+//     only); without --palette every primitive has the reference's material
 //
 // Multi-GPU: launched once per GPU by any launcher that sets RANK,
 // WORLD_SIZE and LOCAL_RANK (e.g. `torchrun --nproc-per-node 8 --no-python
@@ -182,13 +187,32 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  // --palette may stand anywhere: take it out of the positional arguments
-  bool use_palette = false;
+  // --palette and --reflect may stand anywhere: take them out of the
+  // positional arguments
+  bool use_palette = false, use_reflect = false;
+  sdf_reflect reflect = {0, 1.0f, -1, 0};
   {
     int n = 1;
     for (int i = 1; i < argc; ++i) {
-      if (std::string(argv[i]) == "--palette") use_palette = true;
-      else argv[n++] = argv[i];
+      if (std::string(argv[i]) == "--palette") {
+        use_palette = true;
+      } else if (std::string(argv[i]) == "--reflect") {
+        char* end = nullptr;
+        const char* v = i + 1 < argc ? argv[++i] : "";
+        reflect.bounces = static_cast<int32_t>(std::strtol(v, &end, 10));
+        use_reflect = end != v;
+        if (use_reflect && *end == ',') {
+          const char* s = end + 1;
+          reflect.strength = std::strtof(s, &end);
+          use_reflect = end != s;
+        }
+        if (!use_reflect || *end != '\0') {
+          std::fprintf(stderr, "sdf_main: --reflect B[,strength]\n");
+          return 1;
+        }
+      } else {
+        argv[n++] = argv[i];
+      }
     }
     argc = n;
   }
@@ -238,10 +262,10 @@ int main(int argc, char** argv) {
       return run_driver(f, frames, out);
 
     std::vector<sdf_material> materials;
-    if (use_palette) {
+    if (use_palette)
       materials = sdf::palette(f.scene.kind == SDF_SCENE_PRIMITIVES ? f.scene.count : 1);
-      if (lights.empty()) lights.push_back(f.light);   // the reference's one light
-    }
+    if ((use_palette || use_reflect) && lights.empty())
+      lights.push_back(f.light);   // the reference's one light
     hipStream_t stream;
     sdf::check_hip(hipStreamCreate(&stream), "hipStreamCreate");
     hipEvent_t t0, t1;
@@ -253,7 +277,8 @@ int main(int argc, char** argv) {
       for (int i = 0; i < frames; ++i) {
         nav.frame(f, i, frames);
         sdf::check_hip(hipEventRecord(t0, stream), "hipEventRecord");
-        if (use_palette) r.render(f, lights, light_flags, materials);
+        if (use_reflect) r.render(f, lights, light_flags, materials, reflect);
+        else if (use_palette) r.render(f, lights, light_flags, materials);
         else if (lights.empty()) r.render(f);
         else r.render(f, lights, light_flags);
         sdf::check_hip(hipEventRecord(t1, stream), "hipEventRecord");

@@ -302,6 +302,25 @@ class Renderer {
                                &f.params, tiling, rgba_, steps, schedule, stream_),
           "sdf_render_materials");
   }
+  // The materials frame with mirror reflections: up to SDF_MAX_BOUNCES
+  // bounces per pixel, each surface's blended ref times reflect.strength
+  // weighting what it reflects (sdf_render_reflect; reflect.layer = -1 is the
+  // composite).  An empty `materials` gives every primitive f.material.
+  void render(const Frame& f, const std::vector<sdf_light>& lights, int32_t light_flags,
+              const std::vector<sdf_material>& materials, const sdf_reflect& reflect,
+              const sdf_tiling* tiling = nullptr, int32_t* steps = nullptr,
+              sdf_schedule* schedule = nullptr) {
+    if (f.params.width != w_ || f.params.height != h_)
+      throw Error(SDF_E_INVALID_ARG, "Renderer: frame size differs from framebuffer");
+    const std::vector<sdf_material> same(
+        f.scene.kind == SDF_SCENE_PRIMITIVES ? static_cast<size_t>(f.scene.count) : 1, f.material);
+    const std::vector<sdf_material>& m = materials.empty() ? same : materials;
+    check(sdf_render_reflect(&f.scene, &f.camera, lights.data(),
+                             static_cast<int32_t>(lights.size()), light_flags, m.data(),
+                             static_cast<int32_t>(m.size()), &reflect, &f.params, tiling, rgba_,
+                             steps, schedule, stream_),
+          "sdf_render_reflect");
+  }
   // Blocking copy of an RGBA32F framebuffer (row 0 = bottom, GL order).
   std::vector<float> download() const {
     std::vector<float> out(size_t(w_) * h_ * 4);

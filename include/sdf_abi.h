@@ -76,7 +76,10 @@ extern "C" {
                                    and no existing entry point changed, so the
                                    version stays; detect them by the symbol;
                                 still 12: sdf_validate_materials and
-                                   sdf_render_materials, additions likewise */
+                                   sdf_render_materials, additions likewise;
+                                still 12: sdf_validate_reflect and
+                                   sdf_render_reflect (sdf_reflect), additions
+                                   likewise */
 
 /* ---- status codes ------------------------------------------------------ */
 #define SDF_OK               0
@@ -180,6 +183,16 @@ typedef struct {
   float ref[3];                /* (0.5, 0.5, 0.5)                              */
   float shininess;             /* 12                                           */
 } sdf_material;
+
+/* Mirror reflections (sdf_render_reflect, "Reflections" below) */
+#define SDF_MAX_BOUNCES    4
+#define SDF_REFLECT_WEIGHT 0x1      /* with layer >= 0: write W_layer instead of C_layer */
+typedef struct {
+  int32_t bounces;   /* 0 .. SDF_MAX_BOUNCES reflected rays per pixel               */
+  float   strength;  /* finite; scales the blended ref into the mirror weight       */
+  int32_t layer;     /* -1: the composite; 0 .. bounces: that layer alone            */
+  int32_t flags;     /* SDF_REFLECT_WEIGHT                                          */
+} sdf_reflect;       /* 16 bytes */
 
 /* Render flags */
 #define SDF_FLAG_SHADOW     0x1  /* soft shadow march (voxel_fragment.frag:205) */
@@ -362,6 +375,62 @@ typedef struct {
  *   - sdf_render_frames, sdf_render_multi and the frame driver keep their one
  *     material.  Textures, procedural patterns and a shininess per primitive
  *     are not offered. */
+
+/* Reflections (sdf_render_reflect: the "Materials" frame with up to
+ * SDF_MAX_BOUNCES mirror bounces per pixel; everything except `reflect` means
+ * what it means in sdf_render_materials; tests/reflect_ref.c walks the same
+ * path with the CPU oracle's own shade_pixel):
+ *   - layers: a pixel's path is a sequence of rays (O_j, D_j), j = 0, 1, ...
+ *     (O_0, D_0) is the camera position and the pixel's ray exactly as
+ *     sdf_render forms them.  Layer j is the "Materials" pipeline run for a
+ *     fragment whose eye is O_j and whose ray is D_j: the primary march from
+ *     O_j along D_j gives d_j and P_j = O_j + D_j d_j; N_j and ao_j are taken
+ *     at P_j; the material fold at P_j gives amb_j, dif_j, ref_j (materials[0]'s
+ *     for a Mandelbulb); every light's (dif_i, x_i) uses view = normalize(O_j -
+ *     P_j) and a shadow march from P_j; the colour sum in the precision's
+ *     operation sequence gives C_j.  Layer 0 is sdf_render_materials's pixel,
+ *     bit for bit, in both precisions.
+ *   - next ray (fp32): nd = dot(N_j, D_j), the left-to-right sum of three
+ *     products; s = 2 nd; R.c = D_j.c - s N_j.c; D_(j+1) = normalize(R);
+ *     O_(j+1) = P_j + N_j shadow_offset eps, evaluated as the shadow march's
+ *     origin is ((P.c + N.c * shadow_offset * eps), left to right).  Exact
+ *     precision rounds every operation once and fuses nothing, normalize with
+ *     IEEE sqrt and division; fast precision is free to contract.  There is no
+ *     branch on the sign of nd.
+ *   - weights: W_0 = (1, 1, 1); k_j[c] = RN(strength ref_j[c]);
+ *     W_(j+1)[c] = RN(W_j[c] k_j[c]), in both precisions.
+ *   - end of a path: layer j is the pixel's last when j = bounces, or its
+ *     primary march ended with d_j > max_dist (a miss: nothing is reflected off
+ *     the far point), or all three components of W_(j+1) compare equal to 0 (a
+ *     matte surface spawns no ray).  Nothing else ends a path: a march that
+ *     runs out of steps, or a NaN normal, goes on as the arithmetic says.
+ *   - composite (layer = -1): acc = C_0, then for j = 1 .. last in order
+ *       exact precision  acc[c] = RN(acc[c] + RN(W_j[c] C_j[c]))
+ *       fast precision   acc[c] = fma(W_j[c], C_j[c], acc[c])
+ *     and the pixel is (acc, 1).  `steps`, when non-null, receives (sum_j
+ *     primary_j, sum_j sum_i shadow_(j,i)) over the layers traced; as in
+ *     sdf_render every shadow march then runs to the reference's break.
+ *   - one layer (layer = j >= 0, a render pass): the pixel is (C_j, 1), with
+ *     SDF_REFLECT_WEIGHT (W_j, 1); `steps` receives layer j's own counts; a
+ *     pixel whose path ended before layer j gets (0, 0, 0, 1) and (0, 0).
+ *   - bounces = 0 with layer -1 or 0 and no weight flag IS
+ *     sdf_render_materials: the same kernels, every format, the same bits.
+ *   - with bounces >= 1 (or the weight flag) SDF_FORMAT_TILES and
+ *     SDF_FORMAT_SHADE32F are SDF_E_UNSUPPORTED; RGBA16F, RGBA8 and RGB32F
+ *     convert the output colour as usual.
+ *   - tilings, SDF_TILING_FRAME_ROWS and schedules work as in
+ *     sdf_render_materials; with samples = 2 or 4 a sub-sample's colour is its
+ *     pixel's of the S W x S H frame, resolved as under "Supersampling"; the
+ *     shininess stays frame-wide.
+ *   - SDF_E_INVALID_ARG (sdf_validate_reflect, and sdf_render_reflect before
+ *     any device call): reflect NULL; bounces outside 0 .. SDF_MAX_BOUNCES;
+ *     layer outside -1 .. bounces; unknown flag bits, or the weight flag with
+ *     layer = -1; a non-finite strength; with bounces >= 1 a non-finite amb,
+ *     dif or ref component; anything sdf_validate_materials rejects (its
+ *     SDF_E_UNSUPPORTED cases stay SDF_E_UNSUPPORTED).
+ *   - refraction, Fresnel weighting, glossy reflection and a background colour
+ *     for misses are not offered; sdf_render_frames, sdf_render_multi and the
+ *     frame driver keep their one layer. */
 
 /* Framebuffer element formats (4 channels R,G,B,A per pixel).
  *   RGBA32F  the shader's float fragment_color (voxel_fragment.frag:12,210).
@@ -589,6 +658,21 @@ int sdf_render_materials(const sdf_scene* scene, const sdf_camera* camera,
                          const sdf_material* materials, int32_t nmaterials,
                          const sdf_params* params, const sdf_tiling* tiling, void* rgba,
                          int32_t* steps, sdf_schedule* schedule, void* stream);
+
+/* sdf_validate_materials / sdf_render_materials with mirror reflections
+ * ("Reflections" above).  Additions: SDF_ABI_VERSION stays 12, detect them by
+ * the symbol. */
+int sdf_validate_reflect(const sdf_scene* scene, const sdf_camera* camera,
+                         const sdf_light* lights, int32_t nlights, int32_t light_flags,
+                         const sdf_material* materials, int32_t nmaterials,
+                         const sdf_reflect* reflect, const sdf_params* params,
+                         const sdf_tiling* tiling);
+int sdf_render_reflect(const sdf_scene* scene, const sdf_camera* camera,
+                       const sdf_light* lights, int32_t nlights, int32_t light_flags,
+                       const sdf_material* materials, int32_t nmaterials,
+                       const sdf_reflect* reflect, const sdf_params* params,
+                       const sdf_tiling* tiling, void* rgba, int32_t* steps,
+                       sdf_schedule* schedule, void* stream);
 
 /* Scatter `nparts` packed row-block buffers (part r = rank r's output for
  * tiling {block_rows, r, nparts}), laid out back to back in `parts` with a

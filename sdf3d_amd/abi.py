@@ -15,6 +15,8 @@ MAX_DECODE_PARTS = 64   # SDF_MAX_DECODE_PARTS
 SDF_MAX_PRIMS = 16
 MAX_LIGHTS = 8        # SDF_MAX_LIGHTS (sdf_render_lights)
 LIGHTS_COLOR = 0x1    # SDF_LIGHTS_COLOR: light i's diffuse and specular scaled by its colour
+MAX_BOUNCES = 4       # SDF_MAX_BOUNCES (sdf_render_reflect)
+REFLECT_WEIGHT = 0x1  # SDF_REFLECT_WEIGHT: with layer >= 0, W_layer instead of C_layer
 
 # status codes
 SDF_OK = 0
@@ -83,6 +85,11 @@ class sdf_material(C.Structure):
                 ("shininess", C.c_float)]
 
 
+class sdf_reflect(C.Structure):
+    _fields_ = [("bounces", C.c_int32), ("strength", C.c_float), ("layer", C.c_int32),
+                ("flags", C.c_int32)]
+
+
 class sdf_params(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("max_steps", C.c_int32),
                 ("max_dist", C.c_float), ("eps", C.c_float), ("shadow_k", C.c_float),
@@ -110,7 +117,7 @@ class sdf_driver_config(C.Structure):
 STRUCT_SIZES = {
     "sdf_primitive": 64, "sdf_scene": 8 + 64 * SDF_MAX_PRIMS + 32, "sdf_camera": 88,
     "sdf_light": 32, "sdf_material": 40, "sdf_params": 80, "sdf_tiling": 24,
-    "sdf_driver_config": 36,
+    "sdf_driver_config": 36, "sdf_reflect": 16,
 }
 
 # every entry point of include/sdf_abi.h: name -> (restype, argtypes)
@@ -155,6 +162,13 @@ SIGNATURES = {
                                        C.c_int32, _P(sdf_material), C.c_int32, _P(sdf_params),
                                        _P(sdf_tiling), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
+    "sdf_validate_reflect": (C.c_int, [_P(sdf_scene), _P(sdf_camera), _P(sdf_light), C.c_int32,
+                                       C.c_int32, _P(sdf_material), C.c_int32, _P(sdf_reflect),
+                                       _P(sdf_params), _P(sdf_tiling)]),
+    "sdf_render_reflect": (C.c_int, [_P(sdf_scene), _P(sdf_camera), _P(sdf_light), C.c_int32,
+                                     C.c_int32, _P(sdf_material), C.c_int32, _P(sdf_reflect),
+                                     _P(sdf_params), _P(sdf_tiling), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
     "sdf_tiles_decode_checked": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _P(sdf_tiling),
                                            _P(C.c_int64), C.c_int32, C.c_int32, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

@@ -26,6 +26,7 @@ struct RenderPlan {
   RowOrder order{};        // dispatch order of the 8-row blocks (a Schedule's; n = 0: none)
   LightsArgs lights{};     // sdf_render_lights (n = 0: the one light of `a`)
   MaterialArgs materials{};   // sdf_render_materials (n = 0: the one material of `a`)
+  ReflectArgs reflect{};   // sdf_render_reflect (on = 0: one layer, no reflect kernel)
 };
 
 // A render schedule (sdf_schedule): the dispatch order of a plan's 8-row

@@ -113,11 +113,24 @@ struct MaterialArgs {
   int32_t n;
   int32_t reserved[3];
 };
+// ---- mirror reflections (sdf_render_reflect) --------------------------------
+// The uniforms of the loop over a pixel's layers (render_kernel.inc
+// shade_pixel_reflect): sdf_reflect's fields as the host validated them.
+// on = 0: no reflect kernel, nothing here is read.
+struct ReflectArgs {
+  int32_t on;
+  int32_t bounces;
+  float strength;
+  int32_t layer;    // -1 the composite, else the one layer written
+  int32_t weight;   // SDF_REFLECT_WEIGHT: write W_layer instead of C_layer
+  int32_t reserved[3];
+};
 struct RenderArgs {
   KernelArgs a;   // first: the kernels read it at the start of the segment
   RowOrder o;
   LightsArgs l;   // only RenderArgs has the room (FramesArgs is near 4 KiB)
   MaterialArgs m; // behind the lights: a materials render always has lights (l.n >= 1)
+  ReflectArgs r;  // behind the materials: a reflect render has lights, and a table per primitive
 };
 
 // Waves (8x8 tiles side by side) per render workgroup (render_kernel.inc

@@ -1758,7 +1758,20 @@ struct Surface {
   V3 cam, P, N;
   float tP;   // path length at P
   float ao;
+  V3 ray;     // the ray that was marched, and the distance d it went (P = cam +
+  float d;    // ray d): what a reflected ray starts from (shade_pixel_reflect)
 };
+
+// trace_surface itself is two steps, so that a reflected ray (shade_pixel_reflect)
+// is traced by the very code a pixel's ray is: the pixel's ray is formed
+// (:191-192), then trace_ray marches from an eye along a ray and takes the
+// normal and the occlusion at the point it ends on.  (The pixel's ray stays
+// written out in trace_surface: as a function of its own, fast precision
+// contracted its normalisations' sums of squares in another order, and every
+// fast kernel's rays moved by an ulp.)
+template <class Scene>
+__device__ __forceinline__ void trace_ray(KA& A, const Scene& scene, const V3 cam, const V3 ray,
+                                          int& sp, MarchState& mst, Surface& S);
 
 template <class Scene, class View>
 __device__ __forceinline__ void trace_surface(KA& A, const Scene& scene, const View& V, int x,
@@ -1787,6 +1800,15 @@ __device__ __forceinline__ void trace_surface(KA& A, const Scene& scene, const V
              m[2] * r0.x + m[6] * r0.y + m[10] * r0.z + m[14] * 0.0f);
   const V3 ray = normalize(r1);
   const V3 cam = mk(V.cam(0), V.cam(1), V.cam(2));
+  trace_ray(A, scene, cam, ray, sp, mst, S);
+}
+
+// The surface the ray from `cam` along `ray` ends on (S.d: the march's
+// distance, P = cam + ray d).  `mst`: the culling state of a path that starts
+// at `cam` (fresh), left at P.
+template <class Scene>
+__device__ __forceinline__ void trace_ray(KA& A, const Scene& scene, const V3 cam, const V3 ray,
+                                          int& sp, MarchState& mst, Surface& S) {
   const float max_dist = A.max_dist, eps = A.eps;
 
   // raymarch, :86-103
@@ -1864,6 +1886,8 @@ __device__ __forceinline__ void trace_surface(KA& A, const Scene& scene, const V
   S.N = N;
   S.tP = tP;
   S.ao = ao;
+  S.ray = ray;
+  S.d = d;
 }
 
 // The terms of the light at Lp for the surface S: dif = clamp(N.L, 0, 1) *
@@ -2119,6 +2143,152 @@ __device__ __forceinline__ float4 shade_pixel_materials(KA& A, const KARG Lights
   return make_float4(acc[0], acc[1], acc[2], 1.0f);
 }
 
+// The pixel's path of mirror bounces (sdf_abi.h "Reflections"): layer j is the
+// materials pipeline above for the fragment whose eye is O_j and whose ray is
+// D_j -- trace_ray, the material fold at P_j (FOLD; a Mandelbulb has the one
+// material of KernelArgs), light_terms per light with the view from O_j, the
+// colour sum C_j -- and the next ray leaves P_j + N_j offset eps, the shadow
+// march's origin, along D_j mirrored at N_j.
+//
+// reflect_colour is a layer's colour from its surface: shade_pixel_materials's
+// statements after trace_surface, with `mr` (the blended ref) handed back for
+// the weights.
+template <bool STEPS, bool FOLD, class Scene, class View>
+__device__ __forceinline__ void reflect_colour(KA& A, const KARG LightsArgs& L,
+                                               const KARG MaterialArgs& M, const Scene& scene,
+                                               const View& V, const Surface& S,
+                                               const MarchState& mst, int& ss, float (&acc)[3],
+                                               float (&mr)[3]) {
+  float md[3];
+  if constexpr (FOLD) {
+    float m[9];
+#pragma unroll
+    for (int c = 0; c < 9; c++) m[c] = M.m[0][c];
+    scene.material_fold(S.P, M, m);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      acc[c] = shade_ambient(shade_tint(L.la, m[c]), S.ao);
+      md[c] = m[3 + c];
+      mr[c] = m[6 + c];
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      acc[c] = shade_ambient(shade_tint(L.la, A.mat_amb[c]), S.ao);
+      md[c] = A.mat_dif[c];
+      mr[c] = A.mat_ref[c];
+    }
+  }
+  const bool tint = (L.flags & SDF_LIGHTS_COLOR) != 0;
+  const int n = L.n;
+#pragma unroll 1
+  for (int i = 0; i < n; i++) {
+    MarchState ms = mst;
+    int ssi = 0;
+    float dif, spec_x;
+    light_terms<STEPS>(A, scene, V, S, mk(L.pos[i][0], L.pos[i][1], L.pos[i][2]), ms, ssi, dif,
+                       spec_x);
+    ss += ssi;
+    const float spec = spec_pow<SDF_EXACT>(spec_x, A.shininess);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      const float d = tint ? shade_tint(dif, L.color[i][c]) : dif;
+      const float s = tint ? shade_tint(spec, L.color[i][c]) : spec;
+      acc[c] = shade_light<SDF_EXACT>(acc[c], md[c], mr[c], d, s);
+    }
+  }
+}
+
+// What a path carries from layer to layer: the next ray, the weights W_j,
+// the output and the step counts, and whether the lane's path goes on.
+//   composite (layer < 0): acc = C_0, then acc += W_j C_j in the precision's
+//   form; sp / ss sum the layers' counts.  One layer: acc = C_layer (or
+//   W_layer), sp / ss that layer's; a path that ended before it leaves zeros.
+struct ReflectPath {
+  V3 O = {0.0f, 0.0f, 0.0f}, D = {0.0f, 0.0f, 0.0f};
+  float W[3] = {1.0f, 1.0f, 1.0f};
+  float acc[3] = {0.0f, 0.0f, 0.0f};
+  int sp = 0, ss = 0;
+  bool live = true;
+  // layer j is traced: S its surface (S.d its march's distance), C its
+  // colour, mr its blended ref, spj / ssj its counts
+  __device__ __forceinline__ void layer_done(KA& A, const KARG ReflectArgs& R, int j,
+                                             const Surface& S, const float (&C)[3],
+                                             const float (&mr)[3], int spj, int ssj) {
+    const int want = R.layer;
+    if (want < 0) {
+#pragma unroll
+      for (int c = 0; c < 3; c++)
+        acc[c] = j == 0 ? C[c] : reflect_add<SDF_EXACT>(acc[c], W[c], C[c]);
+      sp += spj;
+      ss += ssj;
+    } else if (j == want) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) acc[c] = R.weight ? W[c] : C[c];
+      sp = spj;
+      ss = ssj;
+    }
+    // W_(j+1), and whether the path goes on: not past the last layer wanted,
+    // not off a miss, not off a surface that reflects nothing (a NaN weight
+    // is not 0: the path goes on)
+#pragma unroll
+    for (int c = 0; c < 3; c++) W[c] = shade_tint(W[c], shade_tint(R.strength, mr[c]));
+    const int last = want >= 0 ? want : R.bounces;
+    live = j < last && !(S.d > A.max_dist) && !(W[0] == 0.0f && W[1] == 0.0f && W[2] == 0.0f);
+    // the next ray: D mirrored at N (no branch on the sign of N.D), from the
+    // shadow march's origin (light_terms `o`)
+    const V3 N = S.N, P = S.P;
+    const float s2 = 2.0f * dot(N, D);
+    D = normalize(mk(D.x - s2 * N.x, D.y - s2 * N.y, D.z - s2 * N.z));
+    const float off = A.shadow_offset, eps = A.eps;
+    O = mk(P.x + N.x * off * eps, P.y + N.y * off * eps, P.z + N.z * off * eps);
+  }
+};
+
+// Layer 0 stands in front of the loop over the reflected layers and is
+// shade_pixel_materials statement for statement -- trace_surface, its eye the
+// uniform camera -- so that fast precision contracts it the way the materials
+// kernels do (layer 0 IS their pixel); the loop's layers take their eye per
+// lane.  (One loop body for every layer, layer 0's eye the camera moved into
+// VGPRs, measured 2-4 % faster, but in fast precision the generic kernel's
+// layer 0 then came out a few ulps off sdf_render_materials's: DESIGN.md,
+// Reflections.)  Each layer starts a fresh culling state: the path length a
+// MarchState measures restarts at O_j, which is conservative like the first
+// ray's.  The loop's exit is per lane (a pixel whose path has ended idles), so
+// the wave leaves it when no lane is live.  bounces, layer, the weight flag
+// and the strength are uniforms: one kernel serves them all.
+template <bool STEPS, bool FOLD, class Scene, class View>
+__device__ __forceinline__ float4 shade_pixel_reflect(KA& A, const KARG LightsArgs& L,
+                                                      const KARG MaterialArgs& M,
+                                                      const KARG ReflectArgs& R,
+                                                      const Scene& scene, const View& V, int x,
+                                                      int y, int& sp, int& ss) {
+  ReflectPath path;
+  {
+    MarchState mst;
+    Surface S;
+    int spj = 0, ssj = 0;
+    trace_surface(A, scene, V, x, y, spj, mst, S);
+    float C[3], mr[3];
+    reflect_colour<STEPS, FOLD>(A, L, M, scene, V, S, mst, ssj, C, mr);
+    path.D = S.ray;
+    path.layer_done(A, R, 0, S, C, mr, spj, ssj);
+  }
+#pragma unroll 1
+  for (int j = 1; path.live; j++) {
+    MarchState mst;
+    Surface S;
+    int spj = 0, ssj = 0;
+    trace_ray(A, scene, path.O, path.D, spj, mst, S);
+    float C[3], mr[3];
+    reflect_colour<STEPS, FOLD>(A, L, M, scene, V, S, mst, ssj, C, mr);
+    path.layer_done(A, R, j, S, C, mr, spj, ssj);
+  }
+  sp = path.sp;
+  ss = path.ss;
+  return make_float4(path.acc[0], path.acc[1], path.acc[2], 1.0f);
+}
+
 // The frame's shading constants (shade.h), as every pixel's colour uses them
 __device__ __forceinline__ ShadeK frame_shade(KA& A) {
   ShadeK K;
@@ -2169,12 +2339,16 @@ __device__ __forceinline__ float ssaa_sum(float v, bool four) {
 // (shade_pixel_lights; render_lights, instantiations of their own)
 // MATERIALS (with LIGHTS): a material per primitive, blended at P
 // (shade_pixel_materials; render_materials, instantiations of their own)
+// REFLECT (with LIGHTS; MATERIALS: the scene has a primitive list to fold
+// over): the pixel's path of mirror bounces (shade_pixel_reflect;
+// render_reflect, instantiations of their own)
 template <class Scene, bool TILES, bool STEPS, bool SSAA = false, bool LIGHTS = false,
-          bool MATERIALS = false>
+          bool MATERIALS = false, bool REFLECT = false>
 __device__ __forceinline__ void render_body() {
   static_assert(!(TILES && SSAA), "a TILES stream carries shading terms, not colours");
   static_assert(!(TILES && LIGHTS), "a TILES stream carries one light's terms");
   static_assert(LIGHTS || !MATERIALS, "the materials kernels are lights kernels");
+  static_assert(LIGHTS || !REFLECT, "the reflect kernels are lights kernels");
   const KARG char* const seg = (const KARG char*)__builtin_amdgcn_kernarg_segment_ptr();
   KA& A = *(KA*)seg;
   const KARG RowOrder& O = *(const KARG RowOrder*)(seg + __builtin_offsetof(RenderArgs, o));
@@ -2233,7 +2407,13 @@ __device__ __forceinline__ void render_body() {
     if constexpr (LIGHTS) {
       const KARG LightsArgs& L =
           *(const KARG LightsArgs*)(seg + __builtin_offsetof(RenderArgs, l));
-      if constexpr (MATERIALS) {
+      if constexpr (REFLECT) {
+        const KARG MaterialArgs& M =
+            *(const KARG MaterialArgs*)(seg + __builtin_offsetof(RenderArgs, m));
+        const KARG ReflectArgs& R =
+            *(const KARG ReflectArgs*)(seg + __builtin_offsetof(RenderArgs, r));
+        c = shade_pixel_reflect<STEPS, MATERIALS>(A, L, M, R, scene, ArgsView{A}, x, y, sp, ss);
+      } else if constexpr (MATERIALS) {
         const KARG MaterialArgs& M =
             *(const KARG MaterialArgs*)(seg + __builtin_offsetof(RenderArgs, m));
         c = shade_pixel_materials<STEPS>(A, L, M, scene, ArgsView{A}, x, y, sp, ss);
@@ -2348,6 +2528,21 @@ void render_materials(RenderArgs args) {
   render_body<Scene, false, STEPS, SSAA, true, true>();
 }
 
+// the reflect instantiations (sdf_render_reflect): the materials kernels'
+// pixel inside a loop over the path's layers (shade_pixel_reflect).  The next
+// ray, the weights, the composite and the step sums live across a whole layer
+// on top of the materials kernel's registers, so these kernels take an
+// occupancy of their own (DESIGN.md, Reflections: the register figures)
+#ifndef SDF_REFLECT_WAVES_PER_EU
+#define SDF_REFLECT_WAVES_PER_EU 4
+#endif
+template <class Scene, bool STEPS, bool SSAA, bool FOLD>
+__global__ __launch_bounds__(64 * kWgWaves) __attribute__((amdgpu_waves_per_eu(SDF_REFLECT_WAVES_PER_EU, SDF_REFLECT_WAVES_PER_EU)))
+void render_reflect(RenderArgs args) {
+  (void)args;
+  render_body<Scene, false, STEPS, SSAA, true, FOLD, true>();
+}
+
 // The persistent frame-sequence kernel (sdf_render_frames): every wave
 // builds its scene registers once, then renders 8x8 tiles (item = frame *
 // tiles_per_frame + tile, row-major), `chunk` consecutive items per
@@ -2450,6 +2645,21 @@ static void launch_scene(const RenderArgs& a, dim3 grid, dim3 block, hipStream_t
       hipLaunchKernelGGL((SDF_NS::render_tiles<S, true, true>), grid, block, 0, s, a);
     else
       hipLaunchKernelGGL((SDF_NS::render_tiles<S, true, false>), grid, block, 0, s, a);
+  } else if (a.r.on) {
+    // mirror reflections (reflect_fit: lights, and a material table for every
+    // scene with a primitive list; never TILES)
+    constexpr bool kFold = !SDF_TU_BULB;
+    if (a.a.ss_log2 > 0) {
+      if (a.a.steps)
+        hipLaunchKernelGGL((SDF_NS::render_reflect<S, true, true, kFold>), grid, block, 0, s, a);
+      else
+        hipLaunchKernelGGL((SDF_NS::render_reflect<S, false, true, kFold>), grid, block, 0, s, a);
+    } else {
+      if (a.a.steps)
+        hipLaunchKernelGGL((SDF_NS::render_reflect<S, true, false, kFold>), grid, block, 0, s, a);
+      else
+        hipLaunchKernelGGL((SDF_NS::render_reflect<S, false, false, kFold>), grid, block, 0, s, a);
+    }
   } else if (a.m.n > 0) {
     // a material per primitive (lights_fit: never a Mandelbulb, which has no
     // primitive list to fold over; never TILES)
@@ -2513,6 +2723,17 @@ static bool materials_fit(const RenderArgs& r) {
                         r.a.scene_kind == SDF_SCENE_PRIMITIVES);
 }
 
+// mirror reflections: a lights launch that is no stream (lights_fit), with a
+// material per primitive exactly when the scene has a primitive list, and
+// uniforms inside the contract's ranges (the loop over the layers trusts them)
+static bool reflect_fit(const RenderArgs& r) {
+  if (!r.r.on) return true;
+  const bool prims = r.a.scene_kind == SDF_SCENE_PRIMITIVES;
+  return r.l.n > 0 && r.a.format != SDF_FORMAT_TILES && r.a.format != SDF_FORMAT_SHADE32F &&
+         (prims ? r.m.n == r.a.prim_count && r.m.n > 0 : r.m.n == 0) && r.r.bounces >= 0 &&
+         r.r.bounces <= SDF_MAX_BOUNCES && r.r.layer >= -1 && r.r.layer <= r.r.bounces;
+}
+
 template <class S>
 static void launch_frames_scene(const FramesArgs& a, int nblocks, hipStream_t s) {
   bool steps = false;
@@ -2528,7 +2749,7 @@ static void launch_frames_scene(const FramesArgs& a, int nblocks, hipStream_t s)
 int SDF_LAUNCH_BULB(const RenderArgs& a, void* stream) {
   const dim3 block = render_block(), grid = render_grid(a.a);
   if (grid.x == 0 || grid.y == 0) return 0;
-  if (!order_fits(a, grid) || !lights_fit(a) || !materials_fit(a))
+  if (!order_fits(a, grid) || !lights_fit(a) || !materials_fit(a) || !reflect_fit(a))
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
@@ -2566,7 +2787,7 @@ int SDF_LAUNCH(const RenderArgs& a, int variant, void* stream) {
   if (variant == kVariantBulb) return SDF_LAUNCH_BULB(a, stream);   // its own unit
   const dim3 block = render_block(), grid = render_grid(a.a);
   if (grid.x == 0 || grid.y == 0) return 0;
-  if (!order_fits(a, grid) || !lights_fit(a) || !materials_fit(a))
+  if (!order_fits(a, grid) || !lights_fit(a) || !materials_fit(a) || !reflect_fit(a))
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   if (a.a.format == SDF_FORMAT_TILES) return launch_variant<true>(a, variant, grid, block, s);

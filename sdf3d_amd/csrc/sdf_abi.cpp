@@ -481,6 +481,7 @@ int launch_render_plan(const RenderPlan& plan, void* stream) {
   std::memcpy(r.o.order, plan.order.order, sizeof(uint16_t) * (size_t)std::max(plan.order.n, 0));
   r.l = plan.lights;
   r.m = plan.materials;
+  r.r = plan.reflect;
   if (plan.jit) err = launch_render_jit(r, plan.sig, plan.nsig, plan.exact, stream);
   if (err == -1)
     err = plan.exact ? launch_render_exact(r, plan.variant, stream)
@@ -1024,6 +1025,95 @@ int sdf_render_materials(const sdf_scene* scene, const sdf_camera* camera,
       m.m[i][3 + c] = materials[i].dif[c];
       m.m[i][6 + c] = materials[i].ref[c];
     }
+  if (schedule) {
+    rc = sdf::schedule_apply(schedule->s, &plan);
+    if (rc != SDF_OK) return rc;
+  }
+  rc = sdf::launch_render_plan(plan, stream);
+  if (rc == SDF_OK && schedule && plan.rows == schedule->s->rows)
+    rc = sdf::schedule_after(schedule->s, stream);
+  return rc;
+}
+
+// the call is sdf_render_materials itself: no bounce, and the composite or
+// layer 0's colour asked for
+static bool reflect_is_materials(const sdf_reflect& r) {
+  return r.bounces == 0 && !(r.flags & SDF_REFLECT_WEIGHT);
+}
+
+int sdf_validate_reflect(const sdf_scene* scene, const sdf_camera* camera,
+                         const sdf_light* lights, int32_t nlights, int32_t light_flags,
+                         const sdf_material* materials, int32_t nmaterials,
+                         const sdf_reflect* reflect, const sdf_params* params,
+                         const sdf_tiling* tiling) {
+  if (!reflect) return SDF_E_INVALID_ARG;
+  if (reflect->bounces < 0 || reflect->bounces > SDF_MAX_BOUNCES) return SDF_E_INVALID_ARG;
+  if (reflect->layer < -1 || reflect->layer > reflect->bounces) return SDF_E_INVALID_ARG;
+  if (reflect->flags & ~SDF_REFLECT_WEIGHT) return SDF_E_INVALID_ARG;
+  if ((reflect->flags & SDF_REFLECT_WEIGHT) && reflect->layer < 0) return SDF_E_INVALID_ARG;
+  if (!std::isfinite(reflect->strength)) return SDF_E_INVALID_ARG;
+  const int rc = sdf_validate_materials(scene, camera, lights, nlights, light_flags, materials,
+                                        nmaterials, params, tiling);
+  if (rc != SDF_OK) return rc;
+  // a reflected layer's colour feeds the next weight and the composite: the
+  // components must be numbers
+  if (reflect->bounces >= 1)
+    for (int i = 0; i < nmaterials; ++i)
+      if (!finite3(materials[i].amb) || !finite3(materials[i].dif) || !finite3(materials[i].ref))
+        return SDF_E_INVALID_ARG;
+  // a stream carries one layer's terms
+  if (!reflect_is_materials(*reflect) && (params->output_format == SDF_FORMAT_TILES ||
+                                          params->output_format == SDF_FORMAT_SHADE32F))
+    return SDF_E_UNSUPPORTED;
+  return SDF_OK;
+}
+
+int sdf_render_reflect(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
+                       int32_t nlights, int32_t light_flags, const sdf_material* materials,
+                       int32_t nmaterials, const sdf_reflect* reflect, const sdf_params* params,
+                       const sdf_tiling* tiling, void* rgba, int32_t* steps,
+                       sdf_schedule* schedule, void* stream) {
+  int rc = sdf_validate_reflect(scene, camera, lights, nlights, light_flags, materials, nmaterials,
+                                reflect, params, tiling);
+  if (rc != SDF_OK) return rc;
+  // no bounce: sdf_render_materials's own path, kernels and bits
+  if (reflect_is_materials(*reflect))
+    return sdf_render_materials(scene, camera, lights, nlights, light_flags, materials, nmaterials,
+                                params, tiling, rgba, steps, schedule, stream);
+  sdf::RenderPlan plan;
+  rc = sdf::make_render_plan(scene, camera, &lights[0], &materials[0], params, tiling, rgba,
+                             steps, &plan);
+  if (rc != SDF_OK) return rc;
+  // lights and materials as sdf_render_materials fills them; the reflect
+  // kernels are lights kernels and fold the table of every primitive scene
+  // (a Mandelbulb's one material is the plan's own)
+  sdf::LightsArgs& l = plan.lights;
+  l.n = nlights;
+  l.flags = light_flags;
+  float la = lights[0].ambient;
+  for (int i = 1; i < nlights; ++i) la = la + lights[i].ambient;
+  l.la = la;
+  for (int i = 0; i < nlights; ++i)
+    for (int c = 0; c < 3; ++c) {
+      l.pos[i][c] = lights[i].pos[c];
+      l.color[i][c] = lights[i].color[c];
+    }
+  if (scene->kind == SDF_SCENE_PRIMITIVES) {
+    sdf::MaterialArgs& m = plan.materials;
+    m.n = nmaterials;
+    for (int i = 0; i < nmaterials; ++i)
+      for (int c = 0; c < 3; ++c) {
+        m.m[i][c] = materials[i].amb[c];
+        m.m[i][3 + c] = materials[i].dif[c];
+        m.m[i][6 + c] = materials[i].ref[c];
+      }
+  }
+  sdf::ReflectArgs& r = plan.reflect;
+  r.on = 1;
+  r.bounces = reflect->bounces;
+  r.strength = reflect->strength;
+  r.layer = reflect->layer;
+  r.weight = (reflect->flags & SDF_REFLECT_WEIGHT) ? 1 : 0;
   if (schedule) {
     rc = sdf::schedule_apply(schedule->s, &plan);
     if (rc != SDF_OK) return rc;

@@ -157,6 +157,20 @@ __device__ __forceinline__ float shade_light(float acc, float md, float mr, floa
   }
 }
 
+// Mirror reflections (sdf_abi.h "Reflections"): layer j's colour C added to a
+// channel's composite with its weight W -- the rounded product added in exact
+// precision, one FMA in fast precision.  (The weights themselves are plain
+// products in both: shade_tint.)
+template <bool EXACT>
+__device__ __forceinline__ float reflect_add(float acc, float w, float c) {
+#pragma clang fp contract(off)
+  if constexpr (EXACT) {
+    return acc + w * c;
+  } else {
+    return __builtin_fmaf(w, c, acc);
+  }
+}
+
 // Per-primitive materials (sdf_abi.h "Materials"): the weight q = RN(RN(h h)
 // 0.5) of a smooth operator's blend from its smooth-min's h, the weight t of
 // the incoming primitive (b < a: it is the nearer one), and one material

@@ -140,7 +140,7 @@ class Renderer:
 
     def render(self, frame: Frame, t: abi.sdf_tiling | None = None, out=None,
                steps=False, stream=None, schedule: "Schedule | None" = None,
-               lights=None, light_flags: int = 0, materials=None):
+               lights=None, light_flags: int = 0, materials=None, reflect=None):
         """Render the rows owned by tiling `t` (None = whole frame).
 
         Returns (rgba[rows, W, 4] float32, steps[rows, W, 2] int32 or None), both
@@ -155,7 +155,11 @@ class Renderer:
         Mandelbulb), blended along the CSG fold at every pixel
         (sdf_render_materials; ``frame.material`` is then ignored, and without
         `lights` the frame is lit by ``frame.light``); ``scenes.palette(n)`` gives
-        n distinct ones."""
+        n distinct ones.
+        `reflect`: an ``abi.sdf_reflect`` or a ``(bounces, strength)`` pair: up to
+        abi.MAX_BOUNCES mirror bounces per pixel, each surface's blended ``ref``
+        times `strength` weighting what it reflects (sdf_render_reflect).  Without
+        `materials` every primitive carries ``frame.material``."""
         torch = self.torch
         rows = buffer_rows(frame.params.height, t)
         w = frame.params.width
@@ -188,6 +192,23 @@ class Renderer:
                     C.c_void_p(rgba.data_ptr()),
                     C.c_void_p(st.data_ptr()) if st is not None else None)
             args = (C.byref(frame.scene), C.byref(frame.camera), C.byref(frame.light), *tail)
+            if reflect is not None:
+                if not isinstance(reflect, abi.sdf_reflect):
+                    bounces, strength = reflect
+                    reflect = abi.sdf_reflect(int(bounces), float(strength), -1, 0)
+                if materials is None:
+                    prims = frame.scene.kind == abi.SCENE_PRIMITIVES
+                    materials = [frame.material] * (frame.scene.count if prims else 1)
+                materials = list(materials)
+                marr = (abi.sdf_material * max(len(materials), 1))(*materials)
+                lights = [frame.light] if lights is None else list(lights)
+                arr = (abi.sdf_light * max(len(lights), 1))(*lights)
+                rc = self.lib.sdf_render_reflect(
+                    C.byref(frame.scene), C.byref(frame.camera), arr, len(lights),
+                    int(light_flags), marr, len(materials), C.byref(reflect), *tail[1:],
+                    schedule.handle if schedule is not None else None, self._stream(stream))
+                abi.check(rc, "sdf_render_reflect")
+                return rgba, st
             if materials is not None:
                 materials = list(materials)
                 marr = (abi.sdf_material * max(len(materials), 1))(*materials)
