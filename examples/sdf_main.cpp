@@ -5,7 +5,7 @@
 // cl->get_tic()/get_toc(), :89/:97) and clean up.  The last frame is written
 // as a PPM instead of being presented in a window (:95-96).
 //
-//   sdf_main [--palette] [--reflect B[,strength]]
+//   sdf_main [--palette] [--reflect B[,strength]] [--sky] [--fog START,END[,r,g,b]]
 //            [width height frames out.ppm scene [samples [lights]]]
 //     scene: ref | csg8 | bulb; samples: 1 (default), 2 or 4 sub-samples per
 //     axis, resolved in the render kernel (single-GPU path only: the frame
@@ -22,6 +22,11 @@
 //     mirror bounces per pixel, every surface's ref times strength (default
 //     1) weighting what it reflects (sdf_render_reflect; single-GPU path
 //     only); without --palette every primitive has the reference's material
+//     --sky (anywhere on the line): rays that leave the scene show sdf::sky(),
+//     the default sky with its sun, instead of shading the far point
+//     --fog START,END[,r,g,b] (anywhere on the line): linear distance fog from
+//     START to END in the sky's horizon colour, or in r,g,b (both:
+//     sdf_render_env, single-GPU path only; without --reflect no bounce)
 //
 // Multi-GPU: launched once per GPU by any launcher that sets RANK,
 // WORLD_SIZE and LOCAL_RANK (e.g. `torchrun --nproc-per-node 8 --no-python
@@ -189,8 +194,9 @@ int main(int argc, char** argv) {
   }
   // --palette and --reflect may stand anywhere: take them out of the
   // positional arguments
-  bool use_palette = false, use_reflect = false;
+  bool use_palette = false, use_reflect = false, use_env = false;
   sdf_reflect reflect = {0, 1.0f, -1, 0};
+  sdf_environment environment = sdf::sky(0);
   {
     int n = 1;
     for (int i = 1; i < argc; ++i) {
@@ -210,6 +216,30 @@ int main(int argc, char** argv) {
           std::fprintf(stderr, "sdf_main: --reflect B[,strength]\n");
           return 1;
         }
+      } else if (std::string(argv[i]) == "--sky") {
+        environment.flags |= SDF_ENV_SKY | SDF_ENV_SUN;
+        use_env = true;
+      } else if (std::string(argv[i]) == "--fog") {
+        // 2 or 5 comma-separated numbers
+        float v[5];
+        int nv = 0;
+        const char* p = i + 1 < argc ? argv[++i] : "";
+        char* end = nullptr;
+        bool ok = true;
+        while (ok && nv < 5) {
+          v[nv] = std::strtof(p, &end);
+          ok = end != p;
+          if (!ok) break;
+          ++nv;
+          if (*end != ',') break;
+          p = end + 1;
+        }
+        if (!ok || *end != '\0' || (nv != 2 && nv != 5)) {
+          std::fprintf(stderr, "sdf_main: --fog START,END[,r,g,b]\n");
+          return 1;
+        }
+        environment = sdf::fog(environment, v[0], v[1], nv == 5 ? v + 2 : nullptr);
+        use_env = true;
       } else {
         argv[n++] = argv[i];
       }
@@ -264,7 +294,7 @@ int main(int argc, char** argv) {
     std::vector<sdf_material> materials;
     if (use_palette)
       materials = sdf::palette(f.scene.kind == SDF_SCENE_PRIMITIVES ? f.scene.count : 1);
-    if ((use_palette || use_reflect) && lights.empty())
+    if ((use_palette || use_reflect || use_env) && lights.empty())
       lights.push_back(f.light);   // the reference's one light
     hipStream_t stream;
     sdf::check_hip(hipStreamCreate(&stream), "hipStreamCreate");
@@ -277,7 +307,8 @@ int main(int argc, char** argv) {
       for (int i = 0; i < frames; ++i) {
         nav.frame(f, i, frames);
         sdf::check_hip(hipEventRecord(t0, stream), "hipEventRecord");
-        if (use_reflect) r.render(f, lights, light_flags, materials, reflect);
+        if (use_env) r.render(f, lights, light_flags, materials, reflect, environment);
+        else if (use_reflect) r.render(f, lights, light_flags, materials, reflect);
         else if (use_palette) r.render(f, lights, light_flags, materials);
         else if (lights.empty()) r.render(f);
         else r.render(f, lights, light_flags);

@@ -254,6 +254,44 @@ inline std::vector<sdf_material> palette(int n, float shininess = 12.0f) {
   return out;
 }
 
+// The default environment of sdf_render_env (the Python package's
+// scenes.sky): a gradient from the horizon up to the zenith and down to the
+// ground, a glow around the sun (its direction normalised in double precision
+// and rounded to float), every colour component in [0, 1]; the fog fields
+// hold the horizon's colour and the range 0 .. 1 until sdf::fog sets them.
+// `flags`: the SDF_ENV_* bits to set.
+inline sdf_environment sky(int32_t flags = SDF_ENV_SKY | SDF_ENV_SUN) {
+  static const float kHorizon[3] = {0.72f, 0.80f, 0.90f}, kZenith[3] = {0.18f, 0.36f, 0.72f},
+                     kGround[3] = {0.30f, 0.27f, 0.24f}, kSunColor[3] = {1.0f, 0.9f, 0.6f};
+  static const double kSunDir[3] = {-0.4, 0.6, 0.7};
+  const double n = std::sqrt((kSunDir[0] * kSunDir[0] + kSunDir[1] * kSunDir[1]) +
+                             kSunDir[2] * kSunDir[2]);
+  sdf_environment e{};
+  for (int c = 0; c < 3; ++c) {
+    e.horizon[c] = e.fog_color[c] = kHorizon[c];
+    e.zenith[c] = kZenith[c];
+    e.ground[c] = kGround[c];
+    e.sun_dir[c] = static_cast<float>(kSunDir[c] / n);
+    e.sun_color[c] = kSunColor[c];
+  }
+  e.sun_exponent = 64.0f;
+  e.fog_start = 0.0f;
+  e.fog_end = 1.0f;
+  e.flags = flags;
+  return e;
+}
+// `env` with linear distance fog from `start` to `end` switched on, in its
+// present fog colour (the horizon's after sdf::sky) or in `rgb`.
+inline sdf_environment fog(sdf_environment env, float start, float end,
+                           const float* rgb = nullptr) {
+  env.fog_start = start;
+  env.fog_end = end;
+  if (rgb)
+    for (int c = 0; c < 3; ++c) env.fog_color[c] = rgb[c];
+  env.flags |= SDF_ENV_FOG;
+  return env;
+}
+
 // Owns a device framebuffer and renders frames into it on one HIP stream.
 // The buffer holds width x height pixels of up to 16 bytes (any sdf_format).
 class Renderer {
@@ -320,6 +358,23 @@ class Renderer {
                              static_cast<int32_t>(m.size()), &reflect, &f.params, tiling, rgba_,
                              steps, schedule, stream_),
           "sdf_render_reflect");
+  }
+  // The reflect frame with an environment: a sky for the rays that leave the
+  // scene and linear distance fog (sdf_render_env; sdf::sky() and sdf::fog()
+  // make one).  reflect.bounces = 0 is legal: one layer.
+  void render(const Frame& f, const std::vector<sdf_light>& lights, int32_t light_flags,
+              const std::vector<sdf_material>& materials, const sdf_reflect& reflect,
+              const sdf_environment& env, const sdf_tiling* tiling = nullptr,
+              int32_t* steps = nullptr, sdf_schedule* schedule = nullptr) {
+    if (f.params.width != w_ || f.params.height != h_)
+      throw Error(SDF_E_INVALID_ARG, "Renderer: frame size differs from framebuffer");
+    const std::vector<sdf_material> same(
+        f.scene.kind == SDF_SCENE_PRIMITIVES ? static_cast<size_t>(f.scene.count) : 1, f.material);
+    const std::vector<sdf_material>& m = materials.empty() ? same : materials;
+    check(sdf_render_env(&f.scene, &f.camera, lights.data(), static_cast<int32_t>(lights.size()),
+                         light_flags, m.data(), static_cast<int32_t>(m.size()), &reflect, &env,
+                         &f.params, tiling, rgba_, steps, schedule, stream_),
+          "sdf_render_env");
   }
   // Blocking copy of an RGBA32F framebuffer (row 0 = bottom, GL order).
   std::vector<float> download() const {

@@ -79,6 +79,9 @@ extern "C" {
                                    sdf_render_materials, additions likewise;
                                 still 12: sdf_validate_reflect and
                                    sdf_render_reflect (sdf_reflect), additions
+                                   likewise;
+                                still 12: sdf_validate_env and sdf_render_env
+                                   (sdf_environment, SDF_ENV_*), additions
                                    likewise */
 
 /* ---- status codes ------------------------------------------------------ */
@@ -193,6 +196,24 @@ typedef struct {
   int32_t layer;     /* -1: the composite; 0 .. bounces: that layer alone            */
   int32_t flags;     /* SDF_REFLECT_WEIGHT                                          */
 } sdf_reflect;       /* 16 bytes */
+
+/* Environment (sdf_render_env, "Environment" below) */
+#define SDF_ENV_SKY 0x1   /* a missed layer's colour is the sky along its ray      */
+#define SDF_ENV_SUN 0x2   /* with SKY: a glow around sun_dir                        */
+#define SDF_ENV_FOG 0x4   /* linear distance fog on every layer that is not sky     */
+typedef struct {
+  int32_t flags;          /* SDF_ENV_*; 0: sdf_render_reflect itself                 */
+  float horizon[3];       /* SKY: the sky's colour at D.y = 0                        */
+  float zenith[3];        /* SKY: straight up (D.y = 1)                              */
+  float ground[3];        /* SKY: straight down (D.y = -1)                           */
+  float sun_dir[3];       /* SUN: towards the sun, normalised by the caller          */
+  float sun_color[3];     /* SUN: the glow's colour                                  */
+  float sun_exponent;     /* SUN: finite, >= 1; the glow is max(D . sun_dir, 0)^it   */
+  float fog_color[3];     /* FOG                                                     */
+  float fog_start;        /* FOG: no fog up to this march distance                   */
+  float fog_end;          /* FOG: all fog from here on; fog_end - fog_start > 0      */
+  int32_t reserved[2];
+} sdf_environment;        /* 96 bytes */
 
 /* Render flags */
 #define SDF_FLAG_SHADOW     0x1  /* soft shadow march (voxel_fragment.frag:205) */
@@ -431,6 +452,67 @@ typedef struct {
  *   - refraction, Fresnel weighting, glossy reflection and a background colour
  *     for misses are not offered; sdf_render_frames, sdf_render_multi and the
  *     frame driver keep their one layer. */
+
+/* Environment (sdf_render_env: the "Reflections" frame with a sky for the rays
+ * that leave the scene and linear distance fog; everything except `env` means
+ * what it means in sdf_render_reflect; layers, rays (O_j, D_j), d_j, C_j, k_j
+ * and W_j are those of "Reflections"; tests/env_ref.py states it in NumPy over
+ * the planes of that block's reference):
+ *   - miss: layer j is a miss when d_j > max_dist, the comparison that already
+ *     ends a path.  A NaN d_j is not a miss.
+ *   - sky (SDF_ENV_SKY): the colour of a missed layer is sky(D_j) instead of
+ *     C_j, and nothing after the primary march is evaluated for that layer: no
+ *     normal, no ambient occlusion, no material fold, no light.  u = D_j.y, up
+ *     = !(u < 0), t = clamp(up ? u : -u, 0, 1) with the GLSL selects (max(x, 0)
+ *     = x < 0 ? 0 : x, min(x, 1) = 1 < x ? 1 : x), B = up ? zenith : ground, and
+ *     sky[c] = mix(horizon[c], B[c], t) with the "Materials" mix: horizon[c]
+ *     unchanged for t = 0, B[c] for t = 1, else
+ *       exact precision  RN(horizon[c] + RN(t RN(B[c] - horizon[c])))
+ *       fast precision   fma(t, RN(B[c] - horizon[c]), horizon[c])
+ *   - sun (SDF_ENV_SUN, with SKY): g = max(dot(D_j, sun_dir), 0), the dot
+ *     product the left-to-right sum of three rounded products in both
+ *     precisions, sun_dir as given (the caller normalises it); glow = pow(g,
+ *     sun_exponent) as the specular term's power is taken (exact: fp64 pow
+ *     rounded once; fast: exp2(sun_exponent log2(g)) in hardware); then
+ *       exact precision  sky[c] = RN(sky[c] + RN(glow sun_color[c]))
+ *       fast precision   sky[c] = fma(glow, sun_color[c], sky[c])
+ *   - fog (SDF_ENV_FOG) applies to every layer the sky did not replace: every
+ *     hit layer, and every missed layer when SKY is off.  f_j = clamp((fog_end -
+ *     d_j) / RN(fog_end - fog_start), 0, 1), d_j the layer's own march distance
+ *     from O_j; exact precision rounds every operation once with an IEEE
+ *     division, fast precision multiplies by the host's RN(1 / RN(fog_end -
+ *     fog_start)).  C'_j[c] = mix(fog_color[c], C_j[c], f_j) with the mix above,
+ *     so f = 1 leaves the bits of C_j and f = 0 gives the fog colour's.  What
+ *     lies behind a fogged surface is attenuated too: W_(j+1)[c] = RN(RN(W_j[c]
+ *     k_j[c]) f_j) in both precisions (without the flag there is no second
+ *     product), and "all three components of W_(j+1) compare equal to 0" now
+ *     also ends a path that is fully in fog.
+ *   - composite, passes, steps: "Reflections"' composite with C'_j (or the
+ *     sky) in place of C_j and the weights above; layer = j writes that
+ *     layer's final colour, SDF_REFLECT_WEIGHT the weight above; `steps` as
+ *     there, except that under SKY a missed layer counts (primary_j, 0).  Alpha
+ *     is 1; NaNs propagate as the arithmetic says.
+ *   - env NULL or flags = 0 IS sdf_render_reflect: the same kernels, every
+ *     format, the same bits (so with bounces = 0 sdf_render_materials, and so
+ *     on down).  With a flag set bounces = 0 is legal: one layer through the
+ *     env kernel.
+ *   - with a flag set SDF_FORMAT_TILES and SDF_FORMAT_SHADE32F are
+ *     SDF_E_UNSUPPORTED; RGBA16F, RGBA8 and RGB32F convert the colour as usual;
+ *     tilings, SDF_TILING_FRAME_ROWS, schedules and samples = 2 or 4 work as in
+ *     "Reflections".
+ *   - SDF_E_INVALID_ARG (sdf_validate_env, and sdf_render_env before any
+ *     device call): unknown flag bits; SUN without SKY; with SKY a non-finite
+ *     horizon, zenith or ground component; with SUN a non-finite sun_dir or
+ *     sun_color component or a sun_exponent that is not finite and >= 1; with
+ *     FOG a non-finite fog_color, fog_start or fog_end, or den = RN(fog_end -
+ *     fog_start) not greater than 0, or den or RN(1 / den) not finite (a range
+ *     wider than FLT_MAX or of at most 2^-128: the factor could not be
+ *     formed in both precisions); anything sdf_validate_reflect rejects (its
+ *     SDF_E_UNSUPPORTED cases stay SDF_E_UNSUPPORTED).  Fields of a feature
+ *     whose flag is off are ignored.
+ *   - exponential fog (it needs a correctly rounded exp), environment maps or
+ *     textures, per-channel fog, and an environment in sdf_render_frames,
+ *     sdf_render_multi or the frame driver are not offered. */
 
 /* Framebuffer element formats (4 channels R,G,B,A per pixel).
  *   RGBA32F  the shader's float fragment_color (voxel_fragment.frag:12,210).
@@ -673,6 +755,21 @@ int sdf_render_reflect(const sdf_scene* scene, const sdf_camera* camera,
                        const sdf_reflect* reflect, const sdf_params* params,
                        const sdf_tiling* tiling, void* rgba, int32_t* steps,
                        sdf_schedule* schedule, void* stream);
+
+/* sdf_validate_reflect / sdf_render_reflect with an environment ("Environment"
+ * above; env NULL: sdf_render_reflect).  Additions: SDF_ABI_VERSION stays 12,
+ * detect them by the symbol. */
+int sdf_validate_env(const sdf_scene* scene, const sdf_camera* camera,
+                     const sdf_light* lights, int32_t nlights, int32_t light_flags,
+                     const sdf_material* materials, int32_t nmaterials,
+                     const sdf_reflect* reflect, const sdf_environment* env,
+                     const sdf_params* params, const sdf_tiling* tiling);
+int sdf_render_env(const sdf_scene* scene, const sdf_camera* camera,
+                   const sdf_light* lights, int32_t nlights, int32_t light_flags,
+                   const sdf_material* materials, int32_t nmaterials,
+                   const sdf_reflect* reflect, const sdf_environment* env,
+                   const sdf_params* params, const sdf_tiling* tiling, void* rgba,
+                   int32_t* steps, sdf_schedule* schedule, void* stream);
 
 /* Scatter `nparts` packed row-block buffers (part r = rank r's output for
  * tiling {block_rows, r, nparts}), laid out back to back in `parts` with a

@@ -17,6 +17,9 @@ MAX_LIGHTS = 8        # SDF_MAX_LIGHTS (sdf_render_lights)
 LIGHTS_COLOR = 0x1    # SDF_LIGHTS_COLOR: light i's diffuse and specular scaled by its colour
 MAX_BOUNCES = 4       # SDF_MAX_BOUNCES (sdf_render_reflect)
 REFLECT_WEIGHT = 0x1  # SDF_REFLECT_WEIGHT: with layer >= 0, W_layer instead of C_layer
+ENV_SKY = 0x1         # SDF_ENV_SKY: a missed layer's colour is the sky along its ray
+ENV_SUN = 0x2         # SDF_ENV_SUN: with ENV_SKY, a glow around sun_dir
+ENV_FOG = 0x4         # SDF_ENV_FOG: linear distance fog on every layer that is not sky
 
 # status codes
 SDF_OK = 0
@@ -90,6 +93,14 @@ class sdf_reflect(C.Structure):
                 ("flags", C.c_int32)]
 
 
+class sdf_environment(C.Structure):
+    _fields_ = [("flags", C.c_int32), ("horizon", C.c_float * 3), ("zenith", C.c_float * 3),
+                ("ground", C.c_float * 3), ("sun_dir", C.c_float * 3),
+                ("sun_color", C.c_float * 3), ("sun_exponent", C.c_float),
+                ("fog_color", C.c_float * 3), ("fog_start", C.c_float), ("fog_end", C.c_float),
+                ("reserved", C.c_int32 * 2)]
+
+
 class sdf_params(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("max_steps", C.c_int32),
                 ("max_dist", C.c_float), ("eps", C.c_float), ("shadow_k", C.c_float),
@@ -117,7 +128,7 @@ class sdf_driver_config(C.Structure):
 STRUCT_SIZES = {
     "sdf_primitive": 64, "sdf_scene": 8 + 64 * SDF_MAX_PRIMS + 32, "sdf_camera": 88,
     "sdf_light": 32, "sdf_material": 40, "sdf_params": 80, "sdf_tiling": 24,
-    "sdf_driver_config": 36, "sdf_reflect": 16,
+    "sdf_driver_config": 36, "sdf_reflect": 16, "sdf_environment": 96,
 }
 
 # every entry point of include/sdf_abi.h: name -> (restype, argtypes)
@@ -169,6 +180,13 @@ SIGNATURES = {
                                      C.c_int32, _P(sdf_material), C.c_int32, _P(sdf_reflect),
                                      _P(sdf_params), _P(sdf_tiling), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    "sdf_validate_env": (C.c_int, [_P(sdf_scene), _P(sdf_camera), _P(sdf_light), C.c_int32,
+                                   C.c_int32, _P(sdf_material), C.c_int32, _P(sdf_reflect),
+                                   _P(sdf_environment), _P(sdf_params), _P(sdf_tiling)]),
+    "sdf_render_env": (C.c_int, [_P(sdf_scene), _P(sdf_camera), _P(sdf_light), C.c_int32,
+                                 C.c_int32, _P(sdf_material), C.c_int32, _P(sdf_reflect),
+                                 _P(sdf_environment), _P(sdf_params), _P(sdf_tiling), C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "sdf_tiles_decode_checked": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _P(sdf_tiling),
                                            _P(C.c_int64), C.c_int32, C.c_int32, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

@@ -27,6 +27,7 @@ struct RenderPlan {
   LightsArgs lights{};     // sdf_render_lights (n = 0: the one light of `a`)
   MaterialArgs materials{};   // sdf_render_materials (n = 0: the one material of `a`)
   ReflectArgs reflect{};   // sdf_render_reflect (on = 0: one layer, no reflect kernel)
+  EnvArgs env{};           // sdf_render_env (on = 0: no sky, no fog, no env kernel)
 };
 
 // A render schedule (sdf_schedule): the dispatch order of a plan's 8-row

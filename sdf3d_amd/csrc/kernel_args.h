@@ -125,12 +125,27 @@ struct ReflectArgs {
   int32_t weight;   // SDF_REFLECT_WEIGHT: write W_layer instead of C_layer
   int32_t reserved[3];
 };
+// ---- environment (sdf_render_env) -------------------------------------------
+// The uniforms of a missed layer's sky and of the distance fog (render_kernel.inc
+// shade_pixel_env, shade.h env_sky / env_fog): sdf_environment's fields as the
+// host validated them, with the fog's denominator RN(fog_end - fog_start)
+// (exact precision divides by it) and its reciprocal RN(1 / den) (fast
+// precision multiplies).  Fields of a feature whose flag is off are zero and
+// never read.  on = 0: no env kernel, nothing here is read.
+struct EnvArgs {
+  int32_t on;
+  int32_t flags;        // SDF_ENV_*
+  float horizon[3], zenith[3], ground[3];
+  float sun_dir[3], sun_color[3], sun_exponent;
+  float fog_color[3], fog_end, fog_den, fog_inv;
+};
 struct RenderArgs {
   KernelArgs a;   // first: the kernels read it at the start of the segment
   RowOrder o;
   LightsArgs l;   // only RenderArgs has the room (FramesArgs is near 4 KiB)
   MaterialArgs m; // behind the lights: a materials render always has lights (l.n >= 1)
   ReflectArgs r;  // behind the materials: a reflect render has lights, and a table per primitive
+  EnvArgs e;      // behind the reflect block: an env render is a reflect render (bounces >= 0)
 };
 
 // Waves (8x8 tiles side by side) per render workgroup (render_kernel.inc

@@ -1769,11 +1769,22 @@ struct Surface {
 // written out in trace_surface: as a function of its own, fast precision
 // contracted its normalisations' sums of squares in another order, and every
 // fast kernel's rays moved by an ulp.)
+//
+// trace_ray in turn is trace_march, the primary march alone (S.d, S.P, S.tP),
+// and trace_shape, the normal and the occlusion at P (S.N, S.ao): a layer that
+// missed the scene under a sky (shade_pixel_env) stops between the two.
+// SURFACE = false ends trace_surface after the march as well.  (S.cam and
+// S.ray are the caller's to fill in, and trace_ray fills the whole Surface in
+// one place: with the fields written where they arise, one fast TILES kernel
+// allocated two registers of its encoder the other way round.)
 template <class Scene>
 __device__ __forceinline__ void trace_ray(KA& A, const Scene& scene, const V3 cam, const V3 ray,
                                           int& sp, MarchState& mst, Surface& S);
+template <class Scene>
+__device__ __forceinline__ void trace_march(KA& A, const Scene& scene, const V3 cam, const V3 ray,
+                                            int& sp, MarchState& mst, Surface& S);
 
-template <class Scene, class View>
+template <class Scene, class View, bool SURFACE = true>
 __device__ __forceinline__ void trace_surface(KA& A, const Scene& scene, const View& V, int x,
                                               int y, int& sp, MarchState& mst, Surface& S) {
   // quad = ((2x+1)/W - 1, (2y+1)/H - 1)   (voxel_geometry.geom:26-52)
@@ -1800,15 +1811,21 @@ __device__ __forceinline__ void trace_surface(KA& A, const Scene& scene, const V
              m[2] * r0.x + m[6] * r0.y + m[10] * r0.z + m[14] * 0.0f);
   const V3 ray = normalize(r1);
   const V3 cam = mk(V.cam(0), V.cam(1), V.cam(2));
-  trace_ray(A, scene, cam, ray, sp, mst, S);
+  if constexpr (SURFACE) {
+    trace_ray(A, scene, cam, ray, sp, mst, S);
+  } else {
+    trace_march(A, scene, cam, ray, sp, mst, S);
+    S.cam = cam;
+    S.ray = ray;
+  }
 }
 
-// The surface the ray from `cam` along `ray` ends on (S.d: the march's
-// distance, P = cam + ray d).  `mst`: the culling state of a path that starts
+// The point the ray from `cam` along `ray` ends on (S.d: the march's
+// distance, S.P = cam + ray d, S.tP the path length there).  `mst`: the culling state of a path that starts
 // at `cam` (fresh), left at P.
 template <class Scene>
-__device__ __forceinline__ void trace_ray(KA& A, const Scene& scene, const V3 cam, const V3 ray,
-                                          int& sp, MarchState& mst, Surface& S) {
+__device__ __forceinline__ void trace_march(KA& A, const Scene& scene, const V3 cam, const V3 ray,
+                                            int& sp, MarchState& mst, Surface& S) {
   const float max_dist = A.max_dist, eps = A.eps;
 
   // raymarch, :86-103
@@ -1824,6 +1841,18 @@ __device__ __forceinline__ void trace_ray(KA& A, const Scene& scene, const V3 ca
   }
   const V3 P = add(cam, muls(ray, d));  // :196
   const float tP = d * kPathScale;       // path length at P
+  S.P = P;
+  S.tP = tP;
+  S.d = d;
+}
+
+// The normal and the ambient occlusion at the point S.P a march ended on
+// (`mst` its culling state there).
+template <class Scene>
+__device__ __forceinline__ void trace_shape(KA& A, const Scene& scene, MarchState& mst,
+                                            Surface& S) {
+  const V3 P = S.P;
+  const float tP = S.tP;
 
   // normal, :134-155 (central) or tetrahedral
   V3 N;
@@ -1881,13 +1910,25 @@ __device__ __forceinline__ void trace_ray(KA& A, const Scene& scene, const V3 ca
     }
     ao = gclamp(1.0f - A.ao_strength * occ, 0.0f, 1.0f);
   }
-  S.cam = cam;
-  S.P = P;
   S.N = N;
-  S.tP = tP;
   S.ao = ao;
+}
+
+// The surface the ray from `cam` along `ray` ends on: the march, then the
+// normal and the occlusion there.
+template <class Scene>
+__device__ __forceinline__ void trace_ray(KA& A, const Scene& scene, const V3 cam, const V3 ray,
+                                          int& sp, MarchState& mst, Surface& S) {
+  Surface T;
+  trace_march(A, scene, cam, ray, sp, mst, T);
+  trace_shape(A, scene, mst, T);
+  S.cam = cam;
+  S.P = T.P;
+  S.N = T.N;
+  S.tP = T.tP;
+  S.ao = T.ao;
   S.ray = ray;
-  S.d = d;
+  S.d = T.d;
 }
 
 // The terms of the light at Lp for the surface S: dif = clamp(N.L, 0, 1) *
@@ -2211,10 +2252,14 @@ struct ReflectPath {
   int sp = 0, ss = 0;
   bool live = true;
   // layer j is traced: S its surface (S.d its march's distance), C its
-  // colour, mr its blended ref, spj / ssj its counts
+  // colour, mr its blended ref, spj / ssj its counts.  ENV (shade_pixel_env)
+  // with `fog` (SDF_ENV_FOG, a uniform): what lies behind the layer is
+  // attenuated by its fog factor f as well, a second rounded product.
+  template <bool ENV = false>
   __device__ __forceinline__ void layer_done(KA& A, const KARG ReflectArgs& R, int j,
                                              const Surface& S, const float (&C)[3],
-                                             const float (&mr)[3], int spj, int ssj) {
+                                             const float (&mr)[3], int spj, int ssj,
+                                             float f = 1.0f, bool fog = false) {
     const int want = R.layer;
     if (want < 0) {
 #pragma unroll
@@ -2232,7 +2277,12 @@ struct ReflectPath {
     // not off a miss, not off a surface that reflects nothing (a NaN weight
     // is not 0: the path goes on)
 #pragma unroll
-    for (int c = 0; c < 3; c++) W[c] = shade_tint(W[c], shade_tint(R.strength, mr[c]));
+    for (int c = 0; c < 3; c++) {
+      W[c] = shade_tint(W[c], shade_tint(R.strength, mr[c]));
+      if constexpr (ENV) {
+        if (fog) W[c] = shade_tint(W[c], f);
+      }
+    }
     const int last = want >= 0 ? want : R.bounces;
     live = j < last && !(S.d > A.max_dist) && !(W[0] == 0.0f && W[1] == 0.0f && W[2] == 0.0f);
     // the next ray: D mirrored at N (no branch on the sign of N.D), from the
@@ -2283,6 +2333,79 @@ __device__ __forceinline__ float4 shade_pixel_reflect(KA& A, const KARG LightsAr
     float C[3], mr[3];
     reflect_colour<STEPS, FOLD>(A, L, M, scene, V, S, mst, ssj, C, mr);
     path.layer_done(A, R, j, S, C, mr, spj, ssj);
+  }
+  sp = path.sp;
+  ss = path.ss;
+  return make_float4(path.acc[0], path.acc[1], path.acc[2], 1.0f);
+}
+
+// The path above with an environment (sdf_abi.h "Environment").  env_layer is
+// what follows a layer's march: the miss test d_j > max_dist, the comparison
+// that ends the path, stands between trace_march and the surface work.  Under
+// SDF_ENV_SKY a missed lane takes the sky along its ray (shade.h env_sky) and
+// skips the normal, the occlusion taps, the material fold and every light
+// behind a real branch, so a wave whose lanes all miss runs none of them;
+// lanes of a mixed wave idle as ended paths do.  With SDF_ENV_FOG every other
+// layer's colour is moved towards the fog colour by its factor f (env_fog),
+// which also enters the next weight.  A sky layer has no surface: its path
+// ends there (the miss), its ref is 0 and its shadow count 0.
+template <bool STEPS, bool FOLD, class Scene, class View>
+__device__ __forceinline__ void env_layer(KA& A, const KARG LightsArgs& L,
+                                          const KARG MaterialArgs& M,
+                                          const KARG ReflectArgs& R, const KARG EnvArgs& E,
+                                          const Scene& scene, const View& V, int j, Surface& S,
+                                          MarchState& mst, int spj, ReflectPath& path) {
+  const bool fog = (E.flags & SDF_ENV_FOG) != 0;
+  const bool sky = (E.flags & SDF_ENV_SKY) != 0 && S.d > A.max_dist;
+  float C[3], mr[3] = {0.0f, 0.0f, 0.0f};
+  float f = 1.0f;
+  int ssj = 0;
+  if (sky) {
+    const float D[3] = {S.ray.x, S.ray.y, S.ray.z};
+    const float hz[3] = {E.horizon[0], E.horizon[1], E.horizon[2]};
+    const float ze[3] = {E.zenith[0], E.zenith[1], E.zenith[2]};
+    const float gr[3] = {E.ground[0], E.ground[1], E.ground[2]};
+    const float sd[3] = {E.sun_dir[0], E.sun_dir[1], E.sun_dir[2]};
+    const float sc[3] = {E.sun_color[0], E.sun_color[1], E.sun_color[2]};
+    env_sky<SDF_EXACT>(D, hz, ze, gr, (E.flags & SDF_ENV_SUN) != 0, sd, sc, E.sun_exponent, C);
+    S.N = mk(0.0f, 0.0f, 0.0f);
+    S.ao = 1.0f;
+  } else {
+    trace_shape(A, scene, mst, S);
+    reflect_colour<STEPS, FOLD>(A, L, M, scene, V, S, mst, ssj, C, mr);
+    if (fog) {
+      f = env_fog<SDF_EXACT>(S.d, E.fog_end, E.fog_den, E.fog_inv);
+#pragma unroll
+      for (int c = 0; c < 3; c++) C[c] = material_mix<SDF_EXACT>(E.fog_color[c], C[c], f);
+    }
+  }
+  path.template layer_done<true>(A, R, j, S, C, mr, spj, ssj, f, fog);
+}
+
+template <bool STEPS, bool FOLD, class Scene, class View>
+__device__ __forceinline__ float4 shade_pixel_env(KA& A, const KARG LightsArgs& L,
+                                                  const KARG MaterialArgs& M,
+                                                  const KARG ReflectArgs& R,
+                                                  const KARG EnvArgs& E, const Scene& scene,
+                                                  const View& V, int x, int y, int& sp, int& ss) {
+  ReflectPath path;
+  {
+    MarchState mst;
+    Surface S;
+    int spj = 0;
+    trace_surface<Scene, View, false>(A, scene, V, x, y, spj, mst, S);
+    path.D = S.ray;
+    env_layer<STEPS, FOLD>(A, L, M, R, E, scene, V, 0, S, mst, spj, path);
+  }
+#pragma unroll 1
+  for (int j = 1; path.live; j++) {
+    MarchState mst;
+    Surface S;
+    int spj = 0;
+    trace_march(A, scene, path.O, path.D, spj, mst, S);
+    S.cam = path.O;
+    S.ray = path.D;
+    env_layer<STEPS, FOLD>(A, L, M, R, E, scene, V, j, S, mst, spj, path);
   }
   sp = path.sp;
   ss = path.ss;
@@ -2342,13 +2465,16 @@ __device__ __forceinline__ float ssaa_sum(float v, bool four) {
 // REFLECT (with LIGHTS; MATERIALS: the scene has a primitive list to fold
 // over): the pixel's path of mirror bounces (shade_pixel_reflect;
 // render_reflect, instantiations of their own)
+// ENV (with REFLECT): the path with a sky for missed layers and distance fog
+// (shade_pixel_env; render_env, instantiations of their own)
 template <class Scene, bool TILES, bool STEPS, bool SSAA = false, bool LIGHTS = false,
-          bool MATERIALS = false, bool REFLECT = false>
+          bool MATERIALS = false, bool REFLECT = false, bool ENV = false>
 __device__ __forceinline__ void render_body() {
   static_assert(!(TILES && SSAA), "a TILES stream carries shading terms, not colours");
   static_assert(!(TILES && LIGHTS), "a TILES stream carries one light's terms");
   static_assert(LIGHTS || !MATERIALS, "the materials kernels are lights kernels");
   static_assert(LIGHTS || !REFLECT, "the reflect kernels are lights kernels");
+  static_assert(REFLECT || !ENV, "the env kernels are reflect kernels");
   const KARG char* const seg = (const KARG char*)__builtin_amdgcn_kernarg_segment_ptr();
   KA& A = *(KA*)seg;
   const KARG RowOrder& O = *(const KARG RowOrder*)(seg + __builtin_offsetof(RenderArgs, o));
@@ -2412,7 +2538,14 @@ __device__ __forceinline__ void render_body() {
             *(const KARG MaterialArgs*)(seg + __builtin_offsetof(RenderArgs, m));
         const KARG ReflectArgs& R =
             *(const KARG ReflectArgs*)(seg + __builtin_offsetof(RenderArgs, r));
-        c = shade_pixel_reflect<STEPS, MATERIALS>(A, L, M, R, scene, ArgsView{A}, x, y, sp, ss);
+        if constexpr (ENV) {
+          const KARG EnvArgs& E =
+              *(const KARG EnvArgs*)(seg + __builtin_offsetof(RenderArgs, e));
+          c = shade_pixel_env<STEPS, MATERIALS>(A, L, M, R, E, scene, ArgsView{A}, x, y, sp, ss);
+        } else {
+          c = shade_pixel_reflect<STEPS, MATERIALS>(A, L, M, R, scene, ArgsView{A}, x, y, sp,
+                                                    ss);
+        }
       } else if constexpr (MATERIALS) {
         const KARG MaterialArgs& M =
             *(const KARG MaterialArgs*)(seg + __builtin_offsetof(RenderArgs, m));
@@ -2543,6 +2676,20 @@ void render_reflect(RenderArgs args) {
   render_body<Scene, false, STEPS, SSAA, true, FOLD, true>();
 }
 
+// the env instantiations (sdf_render_env): the reflect kernels' path with the
+// miss test between a layer's march and its surface work (shade_pixel_env),
+// at the reflect kernels' occupancy (DESIGN.md, Environment: the register
+// figures)
+#ifndef SDF_ENV_WAVES_PER_EU
+#define SDF_ENV_WAVES_PER_EU SDF_REFLECT_WAVES_PER_EU
+#endif
+template <class Scene, bool STEPS, bool SSAA, bool FOLD>
+__global__ __launch_bounds__(64 * kWgWaves) __attribute__((amdgpu_waves_per_eu(SDF_ENV_WAVES_PER_EU, SDF_ENV_WAVES_PER_EU)))
+void render_env(RenderArgs args) {
+  (void)args;
+  render_body<Scene, false, STEPS, SSAA, true, FOLD, true, true>();
+}
+
 // The persistent frame-sequence kernel (sdf_render_frames): every wave
 // builds its scene registers once, then renders 8x8 tiles (item = frame *
 // tiles_per_frame + tile, row-major), `chunk` consecutive items per
@@ -2645,6 +2792,20 @@ static void launch_scene(const RenderArgs& a, dim3 grid, dim3 block, hipStream_t
       hipLaunchKernelGGL((SDF_NS::render_tiles<S, true, true>), grid, block, 0, s, a);
     else
       hipLaunchKernelGGL((SDF_NS::render_tiles<S, true, false>), grid, block, 0, s, a);
+  } else if (a.e.on) {
+    // a reflect launch with an environment (env_fit)
+    constexpr bool kFold = !SDF_TU_BULB;
+    if (a.a.ss_log2 > 0) {
+      if (a.a.steps)
+        hipLaunchKernelGGL((SDF_NS::render_env<S, true, true, kFold>), grid, block, 0, s, a);
+      else
+        hipLaunchKernelGGL((SDF_NS::render_env<S, false, true, kFold>), grid, block, 0, s, a);
+    } else {
+      if (a.a.steps)
+        hipLaunchKernelGGL((SDF_NS::render_env<S, true, false, kFold>), grid, block, 0, s, a);
+      else
+        hipLaunchKernelGGL((SDF_NS::render_env<S, false, false, kFold>), grid, block, 0, s, a);
+    }
   } else if (a.r.on) {
     // mirror reflections (reflect_fit: lights, and a material table for every
     // scene with a primitive list; never TILES)
@@ -2734,6 +2895,17 @@ static bool reflect_fit(const RenderArgs& r) {
          r.r.bounces <= SDF_MAX_BOUNCES && r.r.layer >= -1 && r.r.layer <= r.r.bounces;
 }
 
+// an environment: a reflect launch (reflect_fit) with known flags, at least
+// one of them, never a glow without a sky, and a fog denominator above 0 (the
+// kernels trust them)
+static bool env_fit(const RenderArgs& r) {
+  if (!r.e.on) return true;
+  const int32_t all = SDF_ENV_SKY | SDF_ENV_SUN | SDF_ENV_FOG;
+  return r.r.on && r.e.flags != 0 && (r.e.flags & ~all) == 0 &&
+         (!(r.e.flags & SDF_ENV_SUN) || (r.e.flags & SDF_ENV_SKY)) &&
+         (!(r.e.flags & SDF_ENV_FOG) || r.e.fog_den > 0.0f);
+}
+
 template <class S>
 static void launch_frames_scene(const FramesArgs& a, int nblocks, hipStream_t s) {
   bool steps = false;
@@ -2749,7 +2921,8 @@ static void launch_frames_scene(const FramesArgs& a, int nblocks, hipStream_t s)
 int SDF_LAUNCH_BULB(const RenderArgs& a, void* stream) {
   const dim3 block = render_block(), grid = render_grid(a.a);
   if (grid.x == 0 || grid.y == 0) return 0;
-  if (!order_fits(a, grid) || !lights_fit(a) || !materials_fit(a) || !reflect_fit(a))
+  if (!order_fits(a, grid) || !lights_fit(a) || !materials_fit(a) || !reflect_fit(a) ||
+      !env_fit(a))
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
@@ -2787,7 +2960,8 @@ int SDF_LAUNCH(const RenderArgs& a, int variant, void* stream) {
   if (variant == kVariantBulb) return SDF_LAUNCH_BULB(a, stream);   // its own unit
   const dim3 block = render_block(), grid = render_grid(a.a);
   if (grid.x == 0 || grid.y == 0) return 0;
-  if (!order_fits(a, grid) || !lights_fit(a) || !materials_fit(a) || !reflect_fit(a))
+  if (!order_fits(a, grid) || !lights_fit(a) || !materials_fit(a) || !reflect_fit(a) ||
+      !env_fit(a))
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   if (a.a.format == SDF_FORMAT_TILES) return launch_variant<true>(a, variant, grid, block, s);

@@ -482,6 +482,7 @@ int launch_render_plan(const RenderPlan& plan, void* stream) {
   r.l = plan.lights;
   r.m = plan.materials;
   r.r = plan.reflect;
+  r.e = plan.env;
   if (plan.jit) err = launch_render_jit(r, plan.sig, plan.nsig, plan.exact, stream);
   if (err == -1)
     err = plan.exact ? launch_render_exact(r, plan.variant, stream)
@@ -1068,20 +1069,16 @@ int sdf_validate_reflect(const sdf_scene* scene, const sdf_camera* camera,
   return SDF_OK;
 }
 
-int sdf_render_reflect(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
-                       int32_t nlights, int32_t light_flags, const sdf_material* materials,
-                       int32_t nmaterials, const sdf_reflect* reflect, const sdf_params* params,
-                       const sdf_tiling* tiling, void* rgba, int32_t* steps,
-                       sdf_schedule* schedule, void* stream) {
-  int rc = sdf_validate_reflect(scene, camera, lights, nlights, light_flags, materials, nmaterials,
-                                reflect, params, tiling);
-  if (rc != SDF_OK) return rc;
-  // no bounce: sdf_render_materials's own path, kernels and bits
-  if (reflect_is_materials(*reflect))
-    return sdf_render_materials(scene, camera, lights, nlights, light_flags, materials, nmaterials,
-                                params, tiling, rgba, steps, schedule, stream);
+// The launch of a validated reflect render through the reflect kernels, or,
+// with `env` (sdf_render_env with a flag set), through the env kernels.
+static int launch_reflect(const sdf_scene* scene, const sdf_camera* camera,
+                          const sdf_light* lights, int32_t nlights, int32_t light_flags,
+                          const sdf_material* materials, int32_t nmaterials,
+                          const sdf_reflect* reflect, const sdf::EnvArgs* env,
+                          const sdf_params* params, const sdf_tiling* tiling, void* rgba,
+                          int32_t* steps, sdf_schedule* schedule, void* stream) {
   sdf::RenderPlan plan;
-  rc = sdf::make_render_plan(scene, camera, &lights[0], &materials[0], params, tiling, rgba,
+  int rc = sdf::make_render_plan(scene, camera, &lights[0], &materials[0], params, tiling, rgba,
                              steps, &plan);
   if (rc != SDF_OK) return rc;
   // lights and materials as sdf_render_materials fills them; the reflect
@@ -1114,6 +1111,7 @@ int sdf_render_reflect(const sdf_scene* scene, const sdf_camera* camera, const s
   r.strength = reflect->strength;
   r.layer = reflect->layer;
   r.weight = (reflect->flags & SDF_REFLECT_WEIGHT) ? 1 : 0;
+  if (env) plan.env = *env;
   if (schedule) {
     rc = sdf::schedule_apply(schedule->s, &plan);
     if (rc != SDF_OK) return rc;
@@ -1122,6 +1120,102 @@ int sdf_render_reflect(const sdf_scene* scene, const sdf_camera* camera, const s
   if (rc == SDF_OK && schedule && plan.rows == schedule->s->rows)
     rc = sdf::schedule_after(schedule->s, stream);
   return rc;
+}
+
+int sdf_render_reflect(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
+                       int32_t nlights, int32_t light_flags, const sdf_material* materials,
+                       int32_t nmaterials, const sdf_reflect* reflect, const sdf_params* params,
+                       const sdf_tiling* tiling, void* rgba, int32_t* steps,
+                       sdf_schedule* schedule, void* stream) {
+  int rc = sdf_validate_reflect(scene, camera, lights, nlights, light_flags, materials, nmaterials,
+                                reflect, params, tiling);
+  if (rc != SDF_OK) return rc;
+  // no bounce: sdf_render_materials's own path, kernels and bits
+  if (reflect_is_materials(*reflect))
+    return sdf_render_materials(scene, camera, lights, nlights, light_flags, materials, nmaterials,
+                                params, tiling, rgba, steps, schedule, stream);
+  return launch_reflect(scene, camera, lights, nlights, light_flags, materials, nmaterials, reflect,
+                        nullptr, params, tiling, rgba, steps, schedule, stream);
+}
+
+// sdf_environment's own rules (sdf_abi.h "Environment"); fields of a feature
+// whose flag is off are not looked at
+static int validate_environment(const sdf_environment& e) {
+  if (e.flags & ~(SDF_ENV_SKY | SDF_ENV_SUN | SDF_ENV_FOG)) return SDF_E_INVALID_ARG;
+  if ((e.flags & SDF_ENV_SUN) && !(e.flags & SDF_ENV_SKY)) return SDF_E_INVALID_ARG;
+  if (e.flags & SDF_ENV_SKY)
+    if (!finite3(e.horizon) || !finite3(e.zenith) || !finite3(e.ground)) return SDF_E_INVALID_ARG;
+  if (e.flags & SDF_ENV_SUN)
+    if (!finite3(e.sun_dir) || !finite3(e.sun_color) || !std::isfinite(e.sun_exponent) ||
+        !(e.sun_exponent >= 1.0f))
+      return SDF_E_INVALID_ARG;
+  if (e.flags & SDF_ENV_FOG) {
+    if (!finite3(e.fog_color) || !std::isfinite(e.fog_start) || !std::isfinite(e.fog_end))
+      return SDF_E_INVALID_ARG;
+    // the kernels divide by den (exact) or multiply by RN(1 / den) (fast):
+    // both must be numbers above 0
+    const float den = e.fog_end - e.fog_start;   // RN: this unit never contracts
+    if (!(den > 0.0f) || !std::isfinite(den) || !std::isfinite(1.0f / den))
+      return SDF_E_INVALID_ARG;
+  }
+  return SDF_OK;
+}
+
+int sdf_validate_env(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
+                     int32_t nlights, int32_t light_flags, const sdf_material* materials,
+                     int32_t nmaterials, const sdf_reflect* reflect, const sdf_environment* env,
+                     const sdf_params* params, const sdf_tiling* tiling) {
+  if (env && env->flags != 0) {
+    const int rc = validate_environment(*env);
+    if (rc != SDF_OK) return rc;
+  }
+  const int rc = sdf_validate_reflect(scene, camera, lights, nlights, light_flags, materials,
+                                      nmaterials, reflect, params, tiling);
+  if (rc != SDF_OK) return rc;
+  // a stream carries one layer's terms, and no sky or fog
+  if (env && env->flags != 0 && (params->output_format == SDF_FORMAT_TILES ||
+                                 params->output_format == SDF_FORMAT_SHADE32F))
+    return SDF_E_UNSUPPORTED;
+  return SDF_OK;
+}
+
+int sdf_render_env(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
+                   int32_t nlights, int32_t light_flags, const sdf_material* materials,
+                   int32_t nmaterials, const sdf_reflect* reflect, const sdf_environment* env,
+                   const sdf_params* params, const sdf_tiling* tiling, void* rgba, int32_t* steps,
+                   sdf_schedule* schedule, void* stream) {
+  // nothing switched on: sdf_render_reflect's own path, kernels and bits
+  if (!env || env->flags == 0)
+    return sdf_render_reflect(scene, camera, lights, nlights, light_flags, materials, nmaterials,
+                              reflect, params, tiling, rgba, steps, schedule, stream);
+  const int rc = sdf_validate_env(scene, camera, lights, nlights, light_flags, materials,
+                                  nmaterials, reflect, env, params, tiling);
+  if (rc != SDF_OK) return rc;
+  // the validated fields of the features that are on; the rest stays zero
+  sdf::EnvArgs e{};
+  e.on = 1;
+  e.flags = env->flags;
+  if (env->flags & SDF_ENV_SKY)
+    for (int c = 0; c < 3; ++c) {
+      e.horizon[c] = env->horizon[c];
+      e.zenith[c] = env->zenith[c];
+      e.ground[c] = env->ground[c];
+    }
+  if (env->flags & SDF_ENV_SUN) {
+    for (int c = 0; c < 3; ++c) {
+      e.sun_dir[c] = env->sun_dir[c];
+      e.sun_color[c] = env->sun_color[c];
+    }
+    e.sun_exponent = env->sun_exponent;
+  }
+  if (env->flags & SDF_ENV_FOG) {
+    for (int c = 0; c < 3; ++c) e.fog_color[c] = env->fog_color[c];
+    e.fog_end = env->fog_end;
+    e.fog_den = env->fog_end - env->fog_start;   // RN, > 0 (validate_environment)
+    e.fog_inv = 1.0f / e.fog_den;
+  }
+  return launch_reflect(scene, camera, lights, nlights, light_flags, materials, nmaterials, reflect,
+                        &e, params, tiling, rgba, steps, schedule, stream);
 }
 
 int sdf_jit_count(void) { return sdf::jit_compiled_count(); }

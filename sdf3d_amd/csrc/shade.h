@@ -194,6 +194,54 @@ __device__ __forceinline__ float material_mix(float m, float mi, float t) {
   return t == 0.0f ? m : (t == 1.0f ? mi : r);
 }
 
+// Environment (sdf_abi.h "Environment"): the sky along a missed layer's ray D,
+// and the linear distance fog of a layer that is not sky.  Every comparison is
+// a GLSL select (the oracle's forms), in both precisions.
+//   sky   u = D.y, up = !(u < 0), t = clamp(up ? u : -u, 0, 1), each channel
+//         material_mix(horizon, up ? zenith : ground, t); `sun`: plus glow x
+//         sun_color by reflect_add, glow = spec_pow(max(D . sun_dir, 0),
+//         sun_exponent), the dot product three rounded products summed left to
+//         right (never fused: the glow is steep in it)
+//   fog   f = clamp((fog_end - d) / den, 0, 1), den = RN(fog_end - fog_start) >
+//         0 from the host: every operation rounded once with the IEEE division
+//         in exact precision, the host's RN(1 / den) multiplied in fast
+//         precision; a channel is material_mix(fog_color, C, f), so f = 1
+//         keeps C's bits and f = 0 gives the fog colour's
+__device__ __forceinline__ float env_clamp01(float x) {
+  const float lo = x < 0.0f ? 0.0f : x;
+  return 1.0f < lo ? 1.0f : lo;
+}
+template <bool EXACT>
+__device__ __forceinline__ void env_sky(const float (&D)[3], const float (&horizon)[3],
+                                        const float (&zenith)[3], const float (&ground)[3],
+                                        bool sun, const float (&sun_dir)[3],
+                                        const float (&sun_color)[3], float sun_exponent,
+                                        float (&sky)[3]) {
+#pragma clang fp contract(off)
+  const float u = D[1];
+  const bool up = !(u < 0.0f);
+  const float t = env_clamp01(up ? u : -u);
+#pragma unroll
+  for (int c = 0; c < 3; c++)
+    sky[c] = material_mix<EXACT>(horizon[c], up ? zenith[c] : ground[c], t);
+  if (sun) {
+    const float dt = (D[0] * sun_dir[0] + D[1] * sun_dir[1]) + D[2] * sun_dir[2];
+    const float g = dt < 0.0f ? 0.0f : dt;
+    const float glow = spec_pow<EXACT>(g, sun_exponent);
+#pragma unroll
+    for (int c = 0; c < 3; c++) sky[c] = reflect_add<EXACT>(sky[c], glow, sun_color[c]);
+  }
+}
+template <bool EXACT>
+__device__ __forceinline__ float env_fog(float d, float fog_end, float den, float inv) {
+#pragma clang fp contract(off)
+  if constexpr (EXACT) {
+    return env_clamp01((fog_end - d) / den);
+  } else {
+    return env_clamp01((fog_end - d) * inv);
+  }
+}
+
 template <bool EXACT>
 __device__ __forceinline__ float4 shade_colour(const ShadeK& K, float ao, float dif, float x) {
   const float spec = spec_pow<EXACT>(x, K.shin);

@@ -140,7 +140,7 @@ class Renderer:
 
     def render(self, frame: Frame, t: abi.sdf_tiling | None = None, out=None,
                steps=False, stream=None, schedule: "Schedule | None" = None,
-               lights=None, light_flags: int = 0, materials=None, reflect=None):
+               lights=None, light_flags: int = 0, materials=None, reflect=None, env=None):
         """Render the rows owned by tiling `t` (None = whole frame).
 
         Returns (rgba[rows, W, 4] float32, steps[rows, W, 2] int32 or None), both
@@ -159,7 +159,10 @@ class Renderer:
         `reflect`: an ``abi.sdf_reflect`` or a ``(bounces, strength)`` pair: up to
         abi.MAX_BOUNCES mirror bounces per pixel, each surface's blended ``ref``
         times `strength` weighting what it reflects (sdf_render_reflect).  Without
-        `materials` every primitive carries ``frame.material``."""
+        `materials` every primitive carries ``frame.material``.
+        `env`: an ``abi.sdf_environment``: a sky for the rays that leave the scene
+        and linear distance fog (sdf_render_env; ``scenes.sky()`` is a default
+        one).  Without `reflect` it is rendered with no bounce."""
         torch = self.torch
         rows = buffer_rows(frame.params.height, t)
         w = frame.params.width
@@ -192,6 +195,8 @@ class Renderer:
                     C.c_void_p(rgba.data_ptr()),
                     C.c_void_p(st.data_ptr()) if st is not None else None)
             args = (C.byref(frame.scene), C.byref(frame.camera), C.byref(frame.light), *tail)
+            if env is not None and reflect is None:
+                reflect = abi.sdf_reflect(0, 1.0, -1, 0)
             if reflect is not None:
                 if not isinstance(reflect, abi.sdf_reflect):
                     bounces, strength = reflect
@@ -203,10 +208,15 @@ class Renderer:
                 marr = (abi.sdf_material * max(len(materials), 1))(*materials)
                 lights = [frame.light] if lights is None else list(lights)
                 arr = (abi.sdf_light * max(len(lights), 1))(*lights)
-                rc = self.lib.sdf_render_reflect(
-                    C.byref(frame.scene), C.byref(frame.camera), arr, len(lights),
-                    int(light_flags), marr, len(materials), C.byref(reflect), *tail[1:],
-                    schedule.handle if schedule is not None else None, self._stream(stream))
+                head = (C.byref(frame.scene), C.byref(frame.camera), arr, len(lights),
+                        int(light_flags), marr, len(materials), C.byref(reflect))
+                sched = schedule.handle if schedule is not None else None
+                if env is not None:
+                    rc = self.lib.sdf_render_env(*head, C.byref(env), *tail[1:], sched,
+                                                 self._stream(stream))
+                    abi.check(rc, "sdf_render_env")
+                    return rgba, st
+                rc = self.lib.sdf_render_reflect(*head, *tail[1:], sched, self._stream(stream))
                 abi.check(rc, "sdf_render_reflect")
                 return rgba, st
             if materials is not None:

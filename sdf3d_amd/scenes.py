@@ -153,6 +153,45 @@ def palette(n: int = 16, shininess: float = 12.0) -> list:
     return out
 
 
+# The default environment (sky()): a clear day.  Colours (r, g, b) in [0, 1].
+SKY_HORIZON = (0.72, 0.80, 0.90)
+SKY_ZENITH = (0.18, 0.36, 0.72)
+SKY_GROUND = (0.30, 0.27, 0.24)
+SKY_SUN_DIR = (-0.4, 0.6, 0.7)      # towards the sun; sky() normalises it
+SKY_SUN_COLOR = (1.0, 0.9, 0.6)
+SKY_SUN_EXPONENT = 64.0
+
+
+def sky(flags: int = abi.ENV_SKY | abi.ENV_SUN, fog=None) -> "abi.sdf_environment":
+    """The default environment of sdf_render_env (Renderer.render(env=)): a
+    gradient from SKY_HORIZON up to SKY_ZENITH and down to SKY_GROUND, and a
+    glow of SKY_SUN_COLOR with exponent SKY_SUN_EXPONENT around SKY_SUN_DIR,
+    which is normalised in fp64 and rounded to fp32.  Every colour component is
+    in [0, 1].  `fog`: ``(start, end)`` or ``(start, end, (r, g, b))`` switches
+    linear distance fog on as well (abi.ENV_FOG), in the horizon's colour unless
+    one is given.  `flags`: the abi.ENV_* bits to set (the fields of the others
+    are filled in all the same, and ignored by the library)."""
+    e = abi.sdf_environment()
+    n = math.sqrt(sum(v * v for v in SKY_SUN_DIR))
+    for c in range(3):
+        e.horizon[c] = SKY_HORIZON[c]
+        e.zenith[c] = SKY_ZENITH[c]
+        e.ground[c] = SKY_GROUND[c]
+        e.sun_dir[c] = SKY_SUN_DIR[c] / n
+        e.sun_color[c] = SKY_SUN_COLOR[c]
+        e.fog_color[c] = SKY_HORIZON[c]
+    e.sun_exponent = SKY_SUN_EXPONENT
+    e.fog_start, e.fog_end = 0.0, 1.0
+    if fog is not None:
+        e.fog_start, e.fog_end = float(fog[0]), float(fog[1])
+        if len(fog) > 2:
+            for c in range(3):
+                e.fog_color[c] = fog[2][c]
+        flags |= abi.ENV_FOG
+    e.flags = int(flags)
+    return e
+
+
 CONFIGS = {
     # name: (width, height, description)
     "C1": (512, 512, "single sphere, 64 max steps, primary + shadow + shading (CPU plumbing)"),
@@ -200,5 +239,5 @@ def config(name: str, width: int | None = None, height: int | None = None,
 
 
 __all__ = ["Frame", "orbit_view", "POSES", "reference", "config", "CONFIGS", "set_view",
-           "set_sphere_only", "set_csg8", "set_mandelbulb", "palette", "PALETTE",
+           "set_sphere_only", "set_csg8", "set_mandelbulb", "palette", "PALETTE", "sky",
            "PRECISION_EXACT", "PRECISION_FAST", "NORMAL_CENTRAL", "NORMAL_TETRA"]
