@@ -6,7 +6,7 @@
 // as a PPM instead of being presented in a window (:95-96).
 //
 //   sdf_main [--palette] [--reflect B[,strength]] [--sky] [--fog START,END[,r,g,b]]
-//            [width height frames out.ppm scene [samples [lights]]]
+//            [--pick X,Y] [width height frames out.ppm scene [samples [lights]]]
 //     scene: ref | csg8 | bulb; samples: 1 (default), 2 or 4 sub-samples per
 //     axis, resolved in the render kernel (single-GPU path only: the frame
 //     driver refuses supersampling)
@@ -27,6 +27,11 @@
 //     --fog START,END[,r,g,b] (anywhere on the line): linear distance fog from
 //     START to END in the sky's horizon colour, or in r,g,b (both:
 //     sdf_render_env, single-GPU path only; without --reflect no bounce)
+//     --pick X,Y (anywhere on the line): after the last frame, what lies under
+//     its pixel X,Y (row 0 = bottom) through that frame's camera, one ray per
+//     pixel (sdf_trace_camera; single-GPU path only), printed as
+//     "pick X,Y: t steps prim nx ny nz" -- prim is the index of the primitive
+//     that owns the hit, -1 when the ray leaves the scene
 //
 // Multi-GPU: launched once per GPU by any launcher that sets RANK,
 // WORLD_SIZE and LOCAL_RANK (e.g. `torchrun --nproc-per-node 8 --no-python
@@ -194,7 +199,8 @@ int main(int argc, char** argv) {
   }
   // --palette and --reflect may stand anywhere: take them out of the
   // positional arguments
-  bool use_palette = false, use_reflect = false, use_env = false;
+  bool use_palette = false, use_reflect = false, use_env = false, use_pick = false;
+  int pick_x = 0, pick_y = 0;
   sdf_reflect reflect = {0, 1.0f, -1, 0};
   sdf_environment environment = sdf::sky(0);
   {
@@ -214,6 +220,14 @@ int main(int argc, char** argv) {
         }
         if (!use_reflect || *end != '\0') {
           std::fprintf(stderr, "sdf_main: --reflect B[,strength]\n");
+          return 1;
+        }
+      } else if (std::string(argv[i]) == "--pick") {
+        char tail = 0;
+        use_pick = i + 1 < argc &&
+                   std::sscanf(argv[++i], "%d,%d%c", &pick_x, &pick_y, &tail) == 2;
+        if (!use_pick) {
+          std::fprintf(stderr, "sdf_main: --pick X,Y\n");
           return 1;
         }
       } else if (std::string(argv[i]) == "--sky") {
@@ -319,6 +333,13 @@ int main(int argc, char** argv) {
         std::printf("frame %d: %.3f ms (%.1f Mpixels/s)\n", i, ms, W * H / (ms * 1e3));
       }
       sdf::write_ppm(out, r.download(), W, H);
+    }
+    if (use_pick) {
+      sdf::Frame q = f;          // the last frame's camera, one ray per pixel
+      q.params.samples = 0;
+      const sdf::Hit h = sdf::pick(q, pick_x, pick_y, stream);
+      std::printf("pick %d,%d: %.9g %d %d %.9g %.9g %.9g\n", pick_x, pick_y, h.t, h.steps, h.prim,
+                  h.normal[0], h.normal[1], h.normal[2]);
     }
     (void)hipEventDestroy(t0);
     (void)hipEventDestroy(t1);

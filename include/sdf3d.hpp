@@ -405,6 +405,66 @@ class Renderer {
   float* rgba_ = nullptr;
 };
 
+// ---- queries (sdf_abi.h "Queries") -------------------------------------------
+// Rays and points asked of a frame's scene with the frame's march parameters,
+// normal mode, precision and dispatch.  Every pointer is device memory;
+// `origins`, `dirs` and `points` hold n x 3 packed floats; any member of `hits`
+// may be null, not all.  Asynchronous on `stream`.
+inline void trace(const Frame& f, const float* origins, const float* dirs, int64_t n,
+                  const sdf_hits& hits, hipStream_t stream = nullptr) {
+  check(sdf_trace(&f.scene, &f.params, origins, dirs, n, &hits, stream), "sdf_trace");
+}
+// The rays sdf_render marches: entry y * width + x is pixel (x, y)'s (row 0 =
+// bottom), so hits.t is a depth map and hits.prim a segmentation map.
+inline void trace_camera(const Frame& f, const sdf_hits& hits, hipStream_t stream = nullptr) {
+  check(sdf_trace_camera(&f.scene, &f.camera, &f.params, &hits, stream), "sdf_trace_camera");
+}
+// The scene's signed distance (and, with `normal`, its normal) at n points.
+inline void sample(const Frame& f, const float* points, int64_t n, float* dist,
+                   float* normal = nullptr, hipStream_t stream = nullptr) {
+  check(sdf_sample(&f.scene, &f.params, points, n, dist, normal, stream), "sdf_sample");
+}
+
+// What lies under pixel (x, y) of the frame (row 0 = bottom): the march's
+// distance and iteration count, the primitive that owns the hit (-1: the ray
+// left the scene) and the normal there.  Blocking; traces the frame's rays
+// with sdf_trace_camera and reads one pixel back.  An interactive host that
+// picks often keeps the maps of trace_camera instead.
+struct Hit {
+  float t;
+  int32_t steps;
+  int32_t prim;
+  float normal[3];
+};
+inline Hit pick(const Frame& f, int x, int y, hipStream_t stream = nullptr) {
+  check_abi();
+  const int w = f.params.width, h = f.params.height;
+  if (x < 0 || y < 0 || x >= w || y >= h) throw Error(SDF_E_INVALID_ARG, "pick: pixel outside the frame");
+  const size_t n = size_t(w) * h, i = size_t(y) * w + x;
+  char* buf = nullptr;
+  check_hip(hipMalloc(reinterpret_cast<void**>(&buf), n * 24), "hipMalloc");
+  sdf_hits hits;
+  hits.t = reinterpret_cast<float*>(buf);
+  hits.steps = reinterpret_cast<int32_t*>(buf + n * 4);
+  hits.prim = reinterpret_cast<int32_t*>(buf + n * 8);
+  hits.normal = reinterpret_cast<float*>(buf + n * 12);
+  Hit out{};
+  const int rc = sdf_trace_camera(&f.scene, &f.camera, &f.params, &hits, stream);
+  hipError_t e = hipSuccess;
+  if (rc == SDF_OK) {
+    const hipMemcpyKind k = hipMemcpyDeviceToHost;
+    e = hipMemcpyAsync(&out.t, hits.t + i, 4, k, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&out.steps, hits.steps + i, 4, k, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&out.prim, hits.prim + i, 4, k, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out.normal, hits.normal + 3 * i, 12, k, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  }
+  (void)hipFree(buf);
+  check(rc, "sdf_trace_camera");
+  check_hip(e, "pick");
+  return out;
+}
+
 // ---- multi-device frames (sdf_comm_* / sdf_driver_*) ------------------------
 
 // One RCCL communicator over `world` processes (one per GPU), created from a

@@ -215,8 +215,17 @@ typedef struct {
   int32_t reserved[2];
 } sdf_environment;        /* 96 bytes */
 
+/* Query outputs (sdf_trace, sdf_trace_camera; "Queries" below): device
+ * pointers, one entry per ray.  Any may be NULL, at least one is not.        */
+typedef struct {
+  float*   t;       /* n floats:  the march's distance d                        */
+  int32_t* steps;   /* n int32:   the march's iteration count                   */
+  float*   normal;  /* 3n floats, packed xyz; NULL: no normal is evaluated      */
+  int32_t* prim;    /* n int32:   the primitive that owns the hit; NULL: none   */
+} sdf_hits;         /* 32 bytes */
+
 /* Render flags */
-#define SDF_FLAG_SHADOW     0x1  /* soft shadow march (voxel_fragment.frag:205) */
+#define SDF_FLAG_SHADOW    0x1  /* soft shadow march (voxel_fragment.frag:205) */
 #define SDF_FLAG_AO         0x2  /* ambient occlusion (extension)               */
 
 typedef enum {
@@ -514,6 +523,80 @@ typedef struct {
  *     textures, per-channel fog, and an environment in sdf_render_frames,
  *     sdf_render_multi or the frame driver are not offered. */
 
+/* Queries (sdf_trace, sdf_trace_camera, sdf_sample: what a render computes on
+ * the way to a colour, asked of the scene directly -- picking, depth, normal
+ * and primitive-id maps, rays of the caller's own camera model, the distance
+ * field on a set of points.  `origins`, `dirs` and `points` are device arrays
+ * of n x 3 packed fp32; every output is defined from the CPU oracle's point
+ * probes, so it can be checked bit for bit (tests/query_ref.py states it in
+ * NumPy).  Exact precision rounds every operation once and fuses nothing;
+ * fast precision uses the hardware reciprocal square root and may contract,
+ * as everywhere else:
+ *   - ray i of sdf_trace: O = origins[i] as given; D = normalize(dirs[i]) with
+ *     the precision's own normalize (exact: the left-to-right sum of three
+ *     rounded products, an IEEE square root and three IEEE divisions, as
+ *     "Reflections" forms D_(j+1)).  The kernel normalises instead of trusting
+ *     the caller: the kernels' culling is proven for |D| <= 1 + 2^-22.
+ *   - march: sdf_render's primary march from O along D with params->max_steps,
+ *     max_dist and eps; its distance d goes to `t`, its iteration count to
+ *     `steps`.
+ *   - miss: d > max_dist, the comparison that ends a reflect path (a NaN d is
+ *     not a miss): `normal` is (0, 0, 0), `prim` is -1, and nothing after the
+ *     march is evaluated for that ray, as for a missed layer under a sky.
+ *   - hit: P = O + D d as the render forms it; `normal` is N at P with
+ *     params->normal_mode and normal_eps.
+ *   - `prim` is the owner fold at P: the primitive list is evaluated once
+ *     more, every primitive, in list order, carrying the scene fold's running
+ *     d (+INF before primitive 0) and an owner w that starts at 0.  For
+ *     primitive i, (a, b) are the pair "Materials" defines for its operator;
+ *     w becomes i when b < a, for hard and smooth operators alike (for a
+ *     smooth one that is the side with the larger blend weight: t = (b < a) ?
+ *     1 - q : q with q <= 1/2); then d advances by the scene fold's combine.
+ *     A tie or a NaN keeps the earlier owner.  A Mandelbulb always gives 0.
+ *   - sdf_trace_camera: entry y * width + x is the ray (O_0, D_0) of pixel
+ *     (x, y) exactly as sdf_render forms it (the default aspect applies, no
+ *     second normalisation), so its `steps` equal sdf_render's steps[..][0]
+ *     for the same scene, camera and params, whatever the flags.  The whole
+ *     frame, one ray per pixel: params->samples > 1 is SDF_E_UNSUPPORTED, and
+ *     there is no tiling.
+ *   - sdf_sample: dist[i] is the scene SDF at points[i]; `normal` (optional)
+ *     the normal there with params->normal_mode and normal_eps.  There is no
+ *     march and no miss.
+ *   - params: max_steps, max_dist, eps, normal_eps, normal_mode, precision and
+ *     dispatch are used (sdf_trace_camera: width and height too); every other
+ *     field is ignored -- a copy with those fields at sdf_defaults' values is
+ *     what is validated.  sdf_validate_query is that check with sdf_validate's
+ *     scene checks; it makes no device call.
+ *   - dispatch follows sdf_render's: a built-in variant when the scene matches
+ *     one, under SDF_DISPATCH_AUTO a run-time specialised query kernel for any
+ *     other primitive list (counted by sdf_jit_count; the generic kernel with
+ *     SDF3D_JIT=0), GENERIC and UNCULLED as there.  In fast precision the
+ *     kernels need not agree to the bit.
+ *   - SDF_E_INVALID_ARG, decided before any device call: scene, params or hits
+ *     NULL; every output pointer NULL; NULL inputs with n > 0; n < 0 or n >
+ *     2^30; anything the validator rejects.  n = 0 is SDF_OK: nothing is
+ *     launched, no buffer is touched and no device is needed.
+ *   - a zero or non-finite direction (a direction whose length is 0, INF or
+ *     NaN: normalize gives D NaN components) marches as the arithmetic of the
+ *     scene spec says, whose min, max and clamp are the GLSL selects (min(x, y)
+ *     = y < x ? y : x, max(x, y) = x < y ? y : x): a select keeps or drops a
+ *     NaN by its position, so a list of hard unions gives t = +INF after one
+ *     step (a miss), a smooth union t = NaN with steps = max_steps (a NaN d is
+ *     not a miss: normal NaN, prim 0), exactly as the CPU oracle does.  The
+ *     kernels route such a ray through a restatement of the scene spec with
+ *     the selects; it costs the other rays of a call nothing.
+ *   - device data: coordinates (origins, points) must be finite and at most
+ *     1e15 in magnitude, what sdf_validate demands of the camera eye: the
+ *     caller's duty, device data cannot be validated on the host.  Outside
+ *     that range the values are unspecified, but the kernel still terminates:
+ *     every loop is bounded by max_steps, and no address or index depends on
+ *     ray data.
+ *   - asynchronous on `stream`.  SDF_ABI_VERSION stays 12: detect the entry
+ *     points by the symbol.
+ *   - occlusion and soft-shadow queries, per-ray distance limits, sorting or
+ *     compacting rays, tilings and several devices, an ambient-occlusion
+ *     output and gradients (autograd) are not offered. */
+
 /* Framebuffer element formats (4 channels R,G,B,A per pixel).
  *   RGBA32F  the shader's float fragment_color (voxel_fragment.frag:12,210).
  *   RGBA16F  IEEE half, round to nearest even.
@@ -770,6 +853,17 @@ int sdf_render_env(const sdf_scene* scene, const sdf_camera* camera,
                    const sdf_reflect* reflect, const sdf_environment* env,
                    const sdf_params* params, const sdf_tiling* tiling, void* rgba,
                    int32_t* steps, sdf_schedule* schedule, void* stream);
+
+/* Ray and point queries ("Queries" above).  Additions: SDF_ABI_VERSION stays
+ * 12, detect them by the symbol.  sdf_validate_query is the host-only check
+ * the three make first (no device call). */
+int sdf_validate_query(const sdf_scene* scene, const sdf_params* params);
+int sdf_trace(const sdf_scene* scene, const sdf_params* params, const float* origins,
+              const float* dirs, int64_t n, const sdf_hits* hits, void* stream);
+int sdf_trace_camera(const sdf_scene* scene, const sdf_camera* camera, const sdf_params* params,
+                     const sdf_hits* hits, void* stream);
+int sdf_sample(const sdf_scene* scene, const sdf_params* params, const float* points, int64_t n,
+               float* dist, float* normal, void* stream);
 
 /* Scatter `nparts` packed row-block buffers (part r = rank r's output for
  * tiling {block_rows, r, nparts}), laid out back to back in `parts` with a

@@ -101,6 +101,12 @@ class sdf_environment(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
+class sdf_hits(C.Structure):
+    """Outputs of sdf_trace / sdf_trace_camera: device pointers, any may be NULL."""
+    _fields_ = [("t", C.c_void_p), ("steps", C.c_void_p), ("normal", C.c_void_p),
+                ("prim", C.c_void_p)]
+
+
 class sdf_params(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("max_steps", C.c_int32),
                 ("max_dist", C.c_float), ("eps", C.c_float), ("shadow_k", C.c_float),
@@ -128,8 +134,9 @@ class sdf_driver_config(C.Structure):
 STRUCT_SIZES = {
     "sdf_primitive": 64, "sdf_scene": 8 + 64 * SDF_MAX_PRIMS + 32, "sdf_camera": 88,
     "sdf_light": 32, "sdf_material": 40, "sdf_params": 80, "sdf_tiling": 24,
-    "sdf_driver_config": 36, "sdf_reflect": 16, "sdf_environment": 96,
+    "sdf_driver_config": 36, "sdf_reflect": 16, "sdf_environment": 96, "sdf_hits": 32,
 }
+MAX_QUERY = 1 << 30   # rays or points of one sdf_trace / sdf_sample call
 
 # every entry point of include/sdf_abi.h: name -> (restype, argtypes)
 _P = C.POINTER
@@ -187,6 +194,13 @@ SIGNATURES = {
                                  C.c_int32, _P(sdf_material), C.c_int32, _P(sdf_reflect),
                                  _P(sdf_environment), _P(sdf_params), _P(sdf_tiling), C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sdf_validate_query": (C.c_int, [_P(sdf_scene), _P(sdf_params)]),
+    "sdf_trace": (C.c_int, [_P(sdf_scene), _P(sdf_params), C.c_void_p, C.c_void_p, C.c_int64,
+                            _P(sdf_hits), C.c_void_p]),
+    "sdf_trace_camera": (C.c_int, [_P(sdf_scene), _P(sdf_camera), _P(sdf_params), _P(sdf_hits),
+                                   C.c_void_p]),
+    "sdf_sample": (C.c_int, [_P(sdf_scene), _P(sdf_params), C.c_void_p, C.c_int64, C.c_void_p,
+                             C.c_void_p, C.c_void_p]),
     "sdf_tiles_decode_checked": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _P(sdf_tiling),
                                            _P(C.c_int64), C.c_int32, C.c_int32, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

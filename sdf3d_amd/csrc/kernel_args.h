@@ -147,6 +147,27 @@ struct RenderArgs {
   ReflectArgs r;  // behind the materials: a reflect render has lights, and a table per primitive
   EnvArgs e;      // behind the reflect block: an env render is a reflect render (bounces >= 0)
 };
+// ---- queries (sdf_trace, sdf_trace_camera, sdf_sample) ------------------------
+// The argument block of the query kernels (render_kernel.inc query_rays /
+// query_camera / query_points), their own: RenderArgs is full (4096 bytes).
+// `a` carries the scene, the march parameters and, for camera rays, the
+// hoisted camera and the frame size; its outputs (rgba, steps) are unused.
+// `in0` holds n x 3 packed floats (ray origins, or the points of a sample),
+// `in1` the ray directions.  Which outputs are written is a uniform branch on
+// their pointers (any may be null, not all).
+enum QueryKind : int32_t { kQueryRays = 0, kQueryCamera = 1, kQueryPoints = 2 };
+struct QueryArgs {
+  KernelArgs a;   // first: the scene evaluators read it at the start of the segment
+  const float* in0;
+  const float* in1;
+  float* t;         // n: the march's distance (points: the scene distance)
+  int32_t* steps;   // n: the march's iteration count
+  float* normal;    // 3 n, packed xyz
+  int32_t* prim;    // n: the owner fold's primitive, -1 on a miss
+  long long n;      // rays or points (camera rays: width * height)
+  int32_t kind;     // QueryKind
+  int32_t reserved;
+};
 
 // Waves (8x8 tiles side by side) per render workgroup (render_kernel.inc
 // render / render_tiles / render_ssaa; the built-in and the run-time
@@ -193,6 +214,7 @@ struct FramesArgs {
 static_assert(sizeof(FramesArgs) <= 4096, "FramesArgs exceeds the 4 KiB kernel-argument limit");
 static_assert(sizeof(KernelArgs) <= 4096, "KernelArgs exceeds the 4 KiB kernel-argument limit");
 static_assert(sizeof(RenderArgs) <= 4096, "RenderArgs exceeds the 4 KiB kernel-argument limit");
+static_assert(sizeof(QueryArgs) <= 4096, "QueryArgs exceeds the 4 KiB kernel-argument limit");
 // Tiles a wave takes per queue request, queues per launch (workgroup b uses
 // queue b % queues, i.e. one per XCD), and the queues' spacing in uint32s:
 // requests on one address serialise at the memory-side atomic unit, so the
@@ -221,6 +243,12 @@ int launch_render_exact_bulb(const RenderArgs& a, void* stream);
 int launch_render_fast_bulb(const RenderArgs& a, void* stream);
 int launch_frames_exact_bulb(const FramesArgs& a, int nblocks, void* stream);
 int launch_frames_fast_bulb(const FramesArgs& a, int nblocks, void* stream);
+// the query kernels (QueryArgs::kind) of each precision; kVariantBulb is
+// forwarded to the Mandelbulb units
+int launch_query_exact(const QueryArgs& q, int variant, void* stream);
+int launch_query_fast(const QueryArgs& q, int variant, void* stream);
+int launch_query_exact_bulb(const QueryArgs& q, void* stream);
+int launch_query_fast_bulb(const QueryArgs& q, void* stream);
 int launch_deinterleave(const void* parts, int nparts, int part_stride_rows, int row_bytes,
                         int height, int block_rows, void* frame, void* stream);
 int launch_heatmap(const int32_t* steps, int count, int which, int max_steps, int format,
@@ -291,6 +319,8 @@ constexpr int kEscapeWindow = 12;   // base widths tried below the widest residu
 constexpr int kEscapeDwords = 72;   // bitstream bound: 3 width bytes + 3 x 12 x 63 bits
 // run-time specialised kernel for a scene signature (jit.cpp); -1 = none
 int launch_render_jit(const RenderArgs& a, const int* sig, int n, bool exact, void* stream);
+// the same for a query (its kind enters the cache key); -1 = none
+int launch_query_jit(const QueryArgs& q, const int* sig, int n, bool exact, void* stream);
 int jit_compiled_count();
 
 // ---- compile-time scene variants ------------------------------------------

@@ -83,12 +83,16 @@
 #define SDF_LAUNCH_FRAMES launch_frames_exact
 #define SDF_LAUNCH_BULB launch_render_exact_bulb
 #define SDF_LAUNCH_FRAMES_BULB launch_frames_exact_bulb
+#define SDF_LAUNCH_QUERY launch_query_exact
+#define SDF_LAUNCH_QUERY_BULB launch_query_exact_bulb
 #else
 #define SDF_NS fast_impl
 #define SDF_LAUNCH launch_render_fast
 #define SDF_LAUNCH_FRAMES launch_frames_fast
 #define SDF_LAUNCH_BULB launch_render_fast_bulb
 #define SDF_LAUNCH_FRAMES_BULB launch_frames_fast_bulb
+#define SDF_LAUNCH_QUERY launch_query_fast
+#define SDF_LAUNCH_QUERY_BULB launch_query_fast_bulb
 #endif
 
 namespace sdf {
@@ -517,6 +521,18 @@ __device__ __forceinline__ void material_step(int op, float d, float v, float k4
   if (__builtin_amdgcn_ballot_w64(t != 0.0f) == 0) return;
 #pragma unroll
   for (int c = 0; c < 9; c++) m[c] = material_mix<SDF_EXACT>(m[c], mi[c], t);
+}
+
+// One primitive of the owner fold (sdf_abi.h "Queries"): with material_step's
+// (a, b) -- the arguments combine hands to min / smin at the running distance
+// d and the primitive's value v -- the primitive takes the surface when
+// b < a, for a hard and a smooth operator alike (a smooth one blends with
+// t = (b < a) ? 1 - q : q, q <= 1/2: the side with the larger weight).  The
+// same comparison in both precisions; a tie or a NaN keeps the earlier owner.
+__device__ __forceinline__ bool owner_step(int op, float d, float v) {
+  const float a = (op == SDF_OP_UNION || op == SDF_OP_SMOOTH_UNION) ? d : -d;
+  const float b = (op == SDF_OP_INTERSECT || op == SDF_OP_SMOOTH_INTERSECT) ? -v : v;
+  return b < a;
 }
 
 // Power-8 Mandelbulb DE, trig-free polynomial form (DESIGN.md Scene spec).
@@ -1164,6 +1180,21 @@ struct GenericScene {
       d = combine(pr.op, d, v, SMIN_K(pr), SMIN_IK(pr), SMIN_SC(pr), SMIN_KSC(pr));
     }
   }
+  // the owner fold at p (owner_step): every primitive, unculled, in list
+  // order, d advanced as eval does; the index of the primitive that owns p
+  __device__ __forceinline__ int owner_fold(V3 p) const {
+    float d = INFINITY;
+    int w = 0;
+    const int n = A.prim_count;
+    for (int i = 0; i < n; i++) {
+      const KARG sdf_primitive& pr = A.prims[i];
+      KF q = pr.p;
+      const float v = prim_sdf(pr.kind, p, q);
+      if (owner_step(pr.op, d, v)) w = i;
+      d = combine(pr.op, d, v, SMIN_K(pr), SMIN_IK(pr), SMIN_SC(pr), SMIN_KSC(pr));
+    }
+    return w;
+  }
 };
 
 // kinds whose value is never -0 (smin<HW>)
@@ -1398,6 +1429,23 @@ struct FixedScene {
                                                 float (&m)[9]) const {
     material_fold_seq(p, M, m, MakeSeq<N>{});
   }
+  // The owner fold at p (owner_step), unrolled like the material fold: every
+  // primitive, unculled, d advanced by the march's own combine (apply).
+  template <int I>
+  __device__ __forceinline__ void owner_fold_step(float& d, int& w, V3 p) const {
+    constexpr int ko = kKO[I];
+    const float v = prim_ct<(ko >> 3)>(p, q[I]);
+    if (owner_step(ko & 7, d, v)) w = I;
+    d = apply<I, 0>(d, v);
+  }
+  template <int... I>
+  __device__ __forceinline__ int owner_fold_seq(V3 p, Seq<I...>) const {
+    float d = INFINITY;
+    int w = 0;
+    (owner_fold_step<I>(d, w, p), ...);
+    return w;
+  }
+  __device__ __forceinline__ int owner_fold(V3 p) const { return owner_fold_seq(p, MakeSeq<N>{}); }
   // Evaluation at a point p reached by a path of length t (see the pixel
   // pipeline: the primary ray, then side trips to the normal / AO taps and the
   // shadow ray).  Bounds are cached along the path: a fresh test at path
@@ -1684,6 +1732,8 @@ struct BulbScene {
     if (m0 > 2.25f) return (fsqrt(m0) - 1.25f) * sc;
     return mandelbulb(q, iters, bail2) * sc;
   }
+  // the one shape owns every point (sdf_abi.h "Queries")
+  __device__ __forceinline__ int owner_fold(V3) const { return 0; }
   // The taps of one batch (normal, AO) in lockstep groups of SDF_BULB_GROUP:
   // each value bit for bit eval(tap(j)).
   template <class T>
@@ -2759,6 +2809,265 @@ void render_frames(FramesArgs args) {
   }
 }
 
+// ---- queries (sdf_abi.h "Queries": sdf_trace, sdf_trace_camera, sdf_sample) --
+// What the render kernels compute on the way to a colour, written out: the
+// primary march's distance and iteration count, and at the point it ends on
+// the normal and the primitive that owns the surface.  The march, the normal
+// and the scene value are trace_march, trace_surface, trace_shape and
+// Scene::eval as the render kernels call them; only the owner fold
+// (owner_step) is the queries' own.  The uniforms ride in a QueryArgs of
+// their own (kernel_args.h): the scene evaluators read its KernelArgs at the
+// start of the kernel-argument segment, as in a render.  Which outputs are
+// written is a uniform branch on their pointers: one kernel per scene, kind
+// and precision serves every selection.  No address depends on ray data, and
+// every loop is bounded by max_steps: a ray outside the working range gives
+// unspecified values, never a fault or a hang.
+//
+// What follows a query ray's march (S: its end, sp: its count, i: its entry).
+// A miss (d > max_dist, the comparison that ends a reflect path; a NaN d is
+// none) evaluates nothing more: normal (0, 0, 0), owner -1 -- behind a real
+// branch, as a missed layer under a sky (env_layer).
+template <class Scene>
+__device__ __forceinline__ void query_store(KA& A, const KARG QueryArgs& Q, const Scene& scene,
+                                            MarchState& mst, Surface& S, int sp, size_t i) {
+  if (Q.t) Q.t[i] = S.d;
+  if (Q.steps) Q.steps[i] = sp;
+  const bool want_n = Q.normal != nullptr, want_w = Q.prim != nullptr;
+  if (!want_n && !want_w) return;
+  V3 N = mk(0.0f, 0.0f, 0.0f);
+  int w = -1;
+  if (!(S.d > A.max_dist)) {
+    if (want_w) w = scene.owner_fold(S.P);
+    if (want_n) {
+      trace_shape(A, scene, mst, S);
+      N = S.N;
+    }
+  }
+  if (want_n) {
+    float* const o = Q.normal + 3 * i;
+    o[0] = N.x;
+    o[1] = N.y;
+    o[2] = N.z;
+  }
+  if (want_w) Q.prim[i] = w;
+}
+
+// ---- a ray whose direction has no finite length (sdf_abi.h "Queries") ---------
+// normalize gives such a direction NaN components (0 / 0, INF / INF), and the
+// ray then marches "as the arithmetic says" -- the arithmetic of the scene spec,
+// whose min, max and clamp are the GLSL selects (y < x ? y : x, x < y ? y : x):
+// a select drops or keeps a NaN operand by its position.  The scene evaluators
+// above are built for sdf_validate's working range, where no NaN occurs, and
+// take hardware minima and maxima, a clamped FMA and the first primitive's
+// value for min(INF, v) there; on a NaN point they give other values.  So a
+// lane with such a direction takes this path instead: the scene spec restated
+// with the selects, operation for operation the CPU oracle's (oracle_core.h
+// scene_sdf, raymarch, normal_central / normal_tetra) over the prepared
+// primitive blocks, whose derived values are the oracle's own fp32 results
+// (sdf_abi.cpp prepare_prims; k = 4 (k/4) exactly).  A cold path: a wave enters
+// it only when one of its lanes has such a direction, and nothing in it is
+// tuned.  Primitive scenes only: the Mandelbulb's evaluator has no hardware
+// minimum on the way and marches a NaN point as the oracle does.
+__device__ __forceinline__ float sel_min(float x, float y) { return y < x ? y : x; }
+__device__ __forceinline__ float sel_max(float x, float y) { return x < y ? y : x; }
+__device__ __forceinline__ float sel_sqrt(float x) { return __builtin_sqrtf(x); }
+__device__ __forceinline__ float sel_length(V3 a) { return sel_sqrt(dot(a, a)); }
+__device__ __forceinline__ V3 sel_normalize(V3 a) {
+  const float l = sel_length(a);
+  return mk(a.x / l, a.y / l, a.z / l);
+}
+__device__ __forceinline__ float sel_box(V3 v, float bx, float by, float bz) {
+  const float qx = fabsf(v.x) - bx, qy = fabsf(v.y) - by, qz = fabsf(v.z) - bz;
+  const float outside = sel_length(mk(sel_max(qx, 0.0f), sel_max(qy, 0.0f), sel_max(qz, 0.0f)));
+  const float inside = sel_min(sel_max(qx, sel_max(qy, qz)), 0.0f);
+  return outside + inside;
+}
+__device__ __forceinline__ float sel_prim(int kind, V3 p, KF q) {
+  const V3 v = sub(p, mk(q[0], q[1], q[2]));
+  switch (kind) {
+    case SDF_PRIM_SPHERE: return sel_length(v) - q[3];
+    case SDF_PRIM_PLANE: return dot(p, mk(q[0], q[1], q[2])) + q[3];
+    case SDF_PRIM_BOX: return sel_box(v, q[3], q[4], q[5]);
+    case SDF_PRIM_ROUND_BOX: return sel_box(v, q[3], q[4], q[5]) - q[6];
+    case SDF_PRIM_TORUS: {
+      const float qx = sel_sqrt(v.x * v.x + v.z * v.z) - q[3];
+      return sel_sqrt(qx * qx + v.y * v.y) - q[4];
+    }
+    case SDF_PRIM_CAPSULE: {
+      const V3 ba = mk(q[3], q[4], q[5]);
+      const float h = sel_min(sel_max(dot(v, ba) / q[7], 0.0f), 1.0f);
+      return sel_length(sub(v, muls(ba, h))) - q[6];
+    }
+    default: {
+      const float dx = sel_sqrt(v.x * v.x + v.z * v.z) - q[3];
+      const float dy = fabsf(v.y) - q[4];
+      const float inside = sel_min(sel_max(dx, dy), 0.0f);
+      const float ox = sel_max(dx, 0.0f), oy = sel_max(dy, 0.0f);
+      return inside + sel_sqrt(ox * ox + oy * oy);
+    }
+  }
+}
+__device__ __forceinline__ float sel_smin(float a, float b, float k) {
+  const float h = sel_max(k - fabsf(a - b), 0.0f) / k;
+  return sel_min(a, b) - h * h * k * 0.25f;
+}
+__device__ __forceinline__ float sel_combine(int op, float d, float v, float k) {
+  switch (op) {
+    case SDF_OP_UNION: return sel_min(d, v);
+    case SDF_OP_SMOOTH_UNION: return sel_smin(d, v, k);
+    case SDF_OP_SUBTRACT: return sel_max(d, -v);
+    case SDF_OP_INTERSECT: return sel_max(d, v);
+    case SDF_OP_SMOOTH_SUBTRACT: return -sel_smin(-d, v, k);
+    default: return -sel_smin(-d, -v, k);
+  }
+}
+// the scene value at p, and (OWNER) the owner fold's primitive beside it
+template <bool OWNER>
+__device__ __forceinline__ float sel_scene(KA& A, V3 p, int& w) {
+  float d = INFINITY;
+  const int n = A.prim_count;
+#pragma unroll 1
+  for (int i = 0; i < n; i++) {
+    const KARG sdf_primitive& pr = A.prims[i];
+    const float v = sel_prim(pr.kind, p, pr.p);
+    if constexpr (OWNER) {
+      if (owner_step(pr.op, d, v)) w = i;
+    }
+    d = sel_combine(pr.op, d, v, 4.0f * SMIN_K(pr));
+  }
+  return d;
+}
+__device__ __forceinline__ float sel_scene(KA& A, V3 p) {
+  int w = 0;
+  return sel_scene<false>(A, p, w);
+}
+// the whole query of one such ray, stored as query_store stores it
+__device__ __forceinline__ void sel_query(KA& A, const KARG QueryArgs& Q, V3 O, V3 D, size_t i) {
+  float d = 0.0f;
+  int sp = 0;
+#pragma unroll 1
+  for (; sp < A.max_steps;) {
+    const float s = sel_scene(A, add(O, muls(D, d)));
+    d += s;
+    sp++;
+    if (d > A.max_dist || s < A.eps) break;
+  }
+  if (Q.t) Q.t[i] = d;
+  if (Q.steps) Q.steps[i] = sp;
+  if (!Q.normal && !Q.prim) return;
+  V3 N = mk(0.0f, 0.0f, 0.0f);
+  int w = -1;
+  if (!(d > A.max_dist)) {
+    const V3 P = add(O, muls(D, d));
+    if (Q.prim) {
+      w = 0;
+      (void)sel_scene<true>(A, P, w);
+    }
+    if (Q.normal) {
+      const float h = A.normal_eps;
+      if (A.normal_mode == SDF_NORMAL_TETRA) {
+        const float f0 = sel_scene(A, mk(P.x + h, P.y - h, P.z - h));
+        const float f1 = sel_scene(A, mk(P.x - h, P.y - h, P.z + h));
+        const float f2 = sel_scene(A, mk(P.x - h, P.y + h, P.z - h));
+        const float f3 = sel_scene(A, mk(P.x + h, P.y + h, P.z + h));
+        N = sel_normalize(mk(f0 - f1 - f2 + f3, -f0 - f1 + f2 + f3, -f0 + f1 - f2 + f3));
+      } else {
+        const float nx = sel_scene(A, mk(P.x + h, P.y, P.z)) - sel_scene(A, mk(P.x - h, P.y, P.z));
+        const float ny = sel_scene(A, mk(P.x, P.y + h, P.z)) - sel_scene(A, mk(P.x, P.y - h, P.z));
+        const float nz = sel_scene(A, mk(P.x, P.y, P.z + h)) - sel_scene(A, mk(P.x, P.y, P.z - h));
+        N = sel_normalize(mk(nx, ny, nz));
+      }
+    }
+  }
+  if (Q.normal) {
+    float* const o = Q.normal + 3 * i;
+    o[0] = N.x;
+    o[1] = N.y;
+    o[2] = N.z;
+  }
+  if (Q.prim) Q.prim[i] = w;
+}
+
+// KIND kQueryRays: lane = ray i of the buffers, a wave 64 consecutive rays
+// (the 12-byte-stride dword loads and stores of a wave cover one contiguous
+// 768-byte span); O as given, D = normalize(dirs[i]) in the precision's own
+// form -- the cached-gap culling is proven for |D| <= 1 + 2^-22 (kPathScale).
+// KIND kQueryCamera: lane = pixel (x, y), waves are the render kernels' 8x8
+// tiles and the ray is trace_surface's, so the march is the render's.
+// KIND kQueryPoints: lane = point i; the scene value by Scene::eval (no path
+// state), the normal from a fresh culling state at path length 0.
+// A ragged last wave (tile) leaves with its lanes beyond n (the frame) idle.
+template <class Scene, int KIND>
+__device__ __forceinline__ void query_body() {
+  const KARG QueryArgs& Q = *(const KARG QueryArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  KA& A = Q.a;
+  if constexpr (KIND == kQueryCamera) {
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int x = blockIdx.x * (8 * kWgWaves) + wave * 8 + (lane & 7);
+    const int y = blockIdx.y * 8 + (lane >> 3);
+    if (x >= A.width || y >= A.height) return;
+    const Scene scene(A);
+    MarchState mst;
+    Surface S;
+    int sp = 0;
+    trace_surface<Scene, ArgsView, false>(A, scene, ArgsView{A}, x, y, sp, mst, S);
+    query_store(A, Q, scene, mst, S, sp, (size_t)y * A.width + x);
+  } else {
+    const long long i = (long long)blockIdx.x * (64 * kWgWaves) + threadIdx.x;
+    if (i >= Q.n) return;
+    const Scene scene(A);
+    const float* const o = Q.in0 + 3 * i;
+    const V3 O = mk(o[0], o[1], o[2]);
+    if constexpr (KIND == kQueryRays) {
+      const float* const r = Q.in1 + 3 * i;
+      const V3 D = normalize(mk(r[0], r[1], r[2]));
+      // a direction without a finite length (D has a NaN or INF component):
+      // the scene spec's own arithmetic (sel_query), and the lane is done
+      const bool odd = !(fabsf(D.x) < INFINITY && fabsf(D.y) < INFINITY && fabsf(D.z) < INFINITY);
+      if (A.scene_kind == SDF_SCENE_PRIMITIVES && __builtin_amdgcn_ballot_w64(odd) != 0) {
+        asm volatile("" ::: "memory");   // a real branch: never if-converted into the march
+        if (odd) {
+          sel_query(A, Q, O, D, (size_t)i);
+          return;
+        }
+      }
+      MarchState mst;
+      Surface S;
+      int sp = 0;
+      trace_march(A, scene, O, D, sp, mst, S);
+      S.cam = O;
+      S.ray = D;
+      query_store(A, Q, scene, mst, S, sp, (size_t)i);
+    } else {
+      if (Q.t) Q.t[i] = scene.eval(O);
+      if (Q.normal) {
+        MarchState mst;
+        Surface S;
+        S.P = O;
+        S.tP = 0.0f;
+        trace_shape(A, scene, mst, S);
+        float* const q = Q.normal + 3 * i;
+        q[0] = S.N.x;
+        q[1] = S.N.y;
+        q[2] = S.N.z;
+      }
+    }
+  }
+}
+
+// the query kernels' occupancy: a march, the normal's taps and the owner fold
+// (no shadow march, no colour)
+#ifndef SDF_QUERY_WAVES_PER_EU
+#define SDF_QUERY_WAVES_PER_EU SDF_WAVES_PER_EU
+#endif
+template <class Scene, int KIND>
+__global__ __launch_bounds__(64 * kWgWaves) __attribute__((amdgpu_waves_per_eu(SDF_QUERY_WAVES_PER_EU, SDF_QUERY_WAVES_PER_EU)))
+void query(QueryArgs args) {
+  (void)args;
+  query_body<Scene, KIND>();
+}
+
 #undef scene_sdf
 #undef DIVK
 #undef SMIN_K
@@ -2915,6 +3224,51 @@ static void launch_frames_scene(const FramesArgs& a, int nblocks, hipStream_t s)
   else
     hipLaunchKernelGGL((SDF_NS::render_frames<S, false>), dim3(nblocks), dim3(256), 0, s, a);
 }
+
+// one launch of scene kernel S for a query: camera rays on the render
+// kernels' grid of 8x8 tiles, buffer rays and points 64 to a wave.  The host
+// (sdf_abi.cpp query_launch) has bounded n, so the grid fits.
+template <class S>
+static int launch_query_scene(const QueryArgs& q, hipStream_t s) {
+  const dim3 block(64 * kWgWaves);
+  (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
+  if (q.kind == kQueryCamera) {
+    const dim3 grid((q.a.width + 8 * kWgWaves - 1) / (8 * kWgWaves), (q.a.height + 7) / 8);
+    if (grid.x == 0 || grid.y == 0) return 0;
+    hipLaunchKernelGGL((SDF_NS::query<S, kQueryCamera>), grid, block, 0, s, q);
+  } else {
+    if (q.n <= 0) return 0;
+    if (q.n > (1ll << 30)) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)((q.n + 64 * kWgWaves - 1) / (64 * kWgWaves)));
+    if (q.kind == kQueryRays)
+      hipLaunchKernelGGL((SDF_NS::query<S, kQueryRays>), grid, block, 0, s, q);
+    else if (q.kind == kQueryPoints)
+      hipLaunchKernelGGL((SDF_NS::query<S, kQueryPoints>), grid, block, 0, s, q);
+    else
+      return (int)hipErrorInvalidValue;
+  }
+  return (int)hipGetLastError();
+}
+
+#if SDF_TU_BULB
+int SDF_LAUNCH_QUERY_BULB(const QueryArgs& q, void* stream) {
+  return launch_query_scene<SDF_NS::BulbScene>(q, (hipStream_t)stream);
+}
+#else
+int SDF_LAUNCH_QUERY(const QueryArgs& q, int variant, void* stream) {
+  if (variant == kVariantBulb) return SDF_LAUNCH_QUERY_BULB(q, stream);   // its own unit
+  hipStream_t s = (hipStream_t)stream;
+  switch (variant) {
+#define SDF_LAUNCH_FIXED(id, ...) \
+  case id:                        \
+    return launch_query_scene<SDF_NS::FixedScene<__VA_ARGS__>>(q, s);
+    SDF_FIXED_VARIANTS(SDF_LAUNCH_FIXED)
+#undef SDF_LAUNCH_FIXED
+    default:
+      return launch_query_scene<SDF_NS::GenericScene>(q, s);
+  }
+}
+#endif
 
 #if SDF_TU_BULB
 // the Mandelbulb scene's launches (called by the other unit's launchers)

@@ -29,6 +29,7 @@ static_assert(sizeof(sdf_material) == 40, "sdf_material layout");
 static_assert(sizeof(sdf_params) == 80, "sdf_params layout");
 static_assert(sizeof(sdf_tiling) == 24, "sdf_tiling layout");
 static_assert(sizeof(sdf_driver_config) == 36, "sdf_driver_config layout");
+static_assert(sizeof(sdf_hits) == 32, "sdf_hits layout");
 
 namespace sdf {
 
@@ -1216,6 +1217,119 @@ int sdf_render_env(const sdf_scene* scene, const sdf_camera* camera, const sdf_l
   }
   return launch_reflect(scene, camera, lights, nlights, light_flags, materials, nmaterials, reflect,
                         &e, params, tiling, rgba, steps, schedule, stream);
+}
+
+// ---- queries (sdf_abi.h "Queries") ------------------------------------------
+namespace {
+constexpr int64_t kMaxQuery = int64_t(1) << 30;
+
+// The params a query is validated and run with: the fields it uses taken from
+// the caller's, every other one at sdf_defaults' value (`frame`: the camera
+// form also uses width and height).
+sdf_params query_params(const sdf_params& p, bool frame) {
+  sdf_params q;
+  sdf_defaults(nullptr, nullptr, nullptr, nullptr, &q, 0, 0);
+  if (frame) {
+    q.width = p.width;
+    q.height = p.height;
+  }
+  q.max_steps = p.max_steps;
+  q.max_dist = p.max_dist;
+  q.eps = p.eps;
+  q.normal_eps = p.normal_eps;
+  q.normal_mode = p.normal_mode;
+  q.precision = p.precision;
+  q.dispatch = p.dispatch;
+  return q;
+}
+
+int validate_query(const sdf_scene* scene, const sdf_camera* camera, const sdf_params& q) {
+  sdf_camera c;
+  sdf_light l;
+  sdf_material m;
+  sdf_defaults(nullptr, &c, &l, &m, nullptr, 0, 0);
+  return sdf_validate(scene, camera ? camera : &c, &l, &m, &q, nullptr);
+}
+
+// One validated query: the render's own plan (scene blocks, culling bounds,
+// hoisted camera, dispatch) with the query's buffers in place of a frame's.
+int query_launch(int kind, const sdf_scene* scene, const sdf_camera* camera, const sdf_params& q,
+                 const float* in0, const float* in1, int64_t n, float* t, int32_t* steps,
+                 float* normal, int32_t* prim, void* stream) {
+  sdf_camera c;
+  sdf_light l;
+  sdf_material m;
+  sdf_defaults(nullptr, &c, &l, &m, nullptr, 0, 0);
+  std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
+  // the plan wants a framebuffer to name; a query has none and reads neither field
+  int dummy = 0;
+  const int rc = sdf::make_render_plan(scene, camera ? camera : &c, &l, &m, &q, nullptr, &dummy,
+                                       nullptr, plan.get());
+  if (rc != SDF_OK) return rc;
+  std::unique_ptr<sdf::QueryArgs> a(new sdf::QueryArgs());
+  a->a = plan->a;
+  a->a.rgba = nullptr;
+  a->a.steps = nullptr;
+  a->in0 = in0;
+  a->in1 = in1;
+  a->t = t;
+  a->steps = steps;
+  a->normal = normal;
+  a->prim = prim;
+  a->n = n;
+  a->kind = kind;
+  a->reserved = 0;
+  int err = -1;
+  if (plan->jit) err = sdf::launch_query_jit(*a, plan->sig, plan->nsig, plan->exact, stream);
+  if (err == -1)
+    err = plan->exact ? sdf::launch_query_exact(*a, plan->variant, stream)
+                      : sdf::launch_query_fast(*a, plan->variant, stream);
+  return err == hipSuccess ? SDF_OK : SDF_E_HIP;
+}
+}  // namespace
+
+int sdf_validate_query(const sdf_scene* scene, const sdf_params* params) {
+  if (!scene || !params) return SDF_E_INVALID_ARG;
+  return validate_query(scene, nullptr, query_params(*params, false));
+}
+
+int sdf_trace(const sdf_scene* scene, const sdf_params* params, const float* origins,
+              const float* dirs, int64_t n, const sdf_hits* hits, void* stream) {
+  if (!scene || !params || !hits) return SDF_E_INVALID_ARG;
+  if (!hits->t && !hits->steps && !hits->normal && !hits->prim) return SDF_E_INVALID_ARG;
+  if (n < 0 || n > kMaxQuery || (n > 0 && (!origins || !dirs))) return SDF_E_INVALID_ARG;
+  const sdf_params q = query_params(*params, false);
+  const int rc = validate_query(scene, nullptr, q);
+  if (rc != SDF_OK) return rc;
+  if (n == 0) return SDF_OK;   // nothing to launch, no device needed
+  return query_launch(sdf::kQueryRays, scene, nullptr, q, origins, dirs, n, hits->t, hits->steps,
+                      hits->normal, hits->prim, stream);
+}
+
+int sdf_trace_camera(const sdf_scene* scene, const sdf_camera* camera, const sdf_params* params,
+                     const sdf_hits* hits, void* stream) {
+  if (!scene || !camera || !params || !hits) return SDF_E_INVALID_ARG;
+  if (!hits->t && !hits->steps && !hits->normal && !hits->prim) return SDF_E_INVALID_ARG;
+  const sdf_params q = query_params(*params, true);
+  const int rc = validate_query(scene, camera, q);
+  if (rc != SDF_OK) return rc;
+  if (params->samples > 1) return SDF_E_UNSUPPORTED;   // one ray per pixel
+  return query_launch(sdf::kQueryCamera, scene, camera, q, nullptr, nullptr,
+                      int64_t(q.width) * q.height, hits->t, hits->steps, hits->normal, hits->prim,
+                      stream);
+}
+
+int sdf_sample(const sdf_scene* scene, const sdf_params* params, const float* points, int64_t n,
+               float* dist, float* normal, void* stream) {
+  if (!scene || !params) return SDF_E_INVALID_ARG;
+  if (!dist && !normal) return SDF_E_INVALID_ARG;
+  if (n < 0 || n > kMaxQuery || (n > 0 && !points)) return SDF_E_INVALID_ARG;
+  const sdf_params q = query_params(*params, false);
+  const int rc = validate_query(scene, nullptr, q);
+  if (rc != SDF_OK) return rc;
+  if (n == 0) return SDF_OK;
+  return query_launch(sdf::kQueryPoints, scene, nullptr, q, points, nullptr, n, dist, nullptr,
+                      normal, nullptr, stream);
 }
 
 int sdf_jit_count(void) { return sdf::jit_compiled_count(); }

@@ -9,6 +9,7 @@ all arithmetic runs in the HIP kernels of ``libsdf3d.so``.
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 from . import abi
 from .scenes import Frame
@@ -90,6 +91,15 @@ def steps_shape(frame: Frame, t: abi.sdf_tiling | None = None) -> tuple[int, int
     S W x S H render's steps under the tiling with block_rows * S."""
     s = samples(frame)
     return (s * buffer_rows(frame.params.height, t), s * frame.params.width, 2)
+
+
+class Hits(NamedTuple):
+    """What ``Renderer.trace`` / ``trace_camera`` return (sdf_hits): device
+    tensors, None for an output that was not asked for."""
+    t: object
+    steps: object
+    normal: object
+    prim: object
 
 
 class Renderer:
@@ -302,6 +312,87 @@ class Renderer:
                 C.byref(frame.params), ptrs, sptrs, self._stream(stream))
         abi.check(rc, "sdf_render_frames")
         return outs
+
+    # ---- queries (sdf_abi.h "Queries") --------------------------------------
+    def _n3(self, x, what: str):
+        torch = self.torch
+        if (not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2
+                or x.shape[1] != 3 or not x.is_contiguous() or x.device != self.device):
+            raise ValueError(f"{what} must be a contiguous float32 (n, 3) tensor on {self.device}")
+        return x
+
+    def _hits(self, shape, t: bool, steps: bool, normal: bool, prim: bool):
+        torch = self.torch
+        if not (t or steps or normal or prim):
+            raise ValueError("a query needs at least one output")
+
+        def new(want, tail, dtype):
+            return torch.empty((*shape, *tail), dtype=dtype, device=self.device) if want else None
+        out = Hits(new(t, (), torch.float32), new(steps, (), torch.int32),
+                   new(normal, (3,), torch.float32), new(prim, (), torch.int32))
+        ptr = [C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None for x in out]
+        return out, abi.sdf_hits(*ptr)
+
+    def trace(self, frame: Frame, origins, dirs, normal: bool = True, prim: bool = True,
+              stream=None, t: bool = True, steps: bool = True) -> "Hits":
+        """March n rays through ``frame.scene`` (sdf_trace): ray i starts at
+        ``origins[i]`` and runs along ``dirs[i]`` (any non-zero length; the
+        kernel normalises) with the frame's max_steps, max_dist, eps, normal
+        mode, precision and dispatch.  `origins` and `dirs` are contiguous
+        float32 (n, 3) tensors on this renderer's device, used in place.
+        Returns ``Hits(t, steps, normal, prim)``: the march's distance (n,), its
+        iteration count (n,) int32, the normal at the hit (n, 3) -- zeros on a
+        miss (t > max_dist) -- and the index of the primitive that owns the
+        hit (n,) int32, -1 on a miss; an output that was not asked for is
+        None.  Asynchronous on `stream`."""
+        o, d = self._n3(origins, "origins"), self._n3(dirs, "dirs")
+        if o.shape != d.shape:
+            raise ValueError("origins and dirs must have the same shape")
+        n = o.shape[0]
+        out, hits = self._hits((n,), t, steps, normal, prim)
+        if n == 0:
+            return out
+        with self._on_device():
+            rc = self.lib.sdf_trace(C.byref(frame.scene), C.byref(frame.params),
+                                    C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), n,
+                                    C.byref(hits), self._stream(stream))
+        abi.check(rc, "sdf_trace")
+        return out
+
+    def trace_camera(self, frame: Frame, normal: bool = True, prim: bool = True, stream=None,
+                     t: bool = True, steps: bool = True) -> "Hits":
+        """``trace`` for the rays ``render`` marches (sdf_trace_camera): entry
+        [y, x] is pixel (x, y)'s ray, so `t` is a depth map, `normal` a normal
+        map and `prim` a segmentation map of the frame, and `steps` equals
+        ``render(..., steps=True)[1][..., 0]``.  Tensors are shaped (H, W) and
+        (H, W, 3).  One ray per pixel: ``frame.params.samples`` > 1 is refused."""
+        p = frame.params
+        out, hits = self._hits((p.height, p.width), t, steps, normal, prim)
+        with self._on_device():
+            rc = self.lib.sdf_trace_camera(C.byref(frame.scene), C.byref(frame.camera),
+                                           C.byref(p), C.byref(hits), self._stream(stream))
+        abi.check(rc, "sdf_trace_camera")
+        return out
+
+    def sample(self, frame: Frame, points, normal: bool = False, stream=None):
+        """The scene's signed distance at n points (sdf_sample): `points` is a
+        contiguous float32 (n, 3) tensor on this renderer's device.  Returns
+        (dist (n,), normal (n, 3) or None), the normal with the frame's normal
+        mode and normal_eps.  Asynchronous on `stream`."""
+        torch = self.torch
+        pts = self._n3(points, "points")
+        n = pts.shape[0]
+        dist = torch.empty((n,), dtype=torch.float32, device=self.device)
+        nrm = torch.empty((n, 3), dtype=torch.float32, device=self.device) if normal else None
+        if n == 0:
+            return dist, nrm
+        with self._on_device():
+            rc = self.lib.sdf_sample(C.byref(frame.scene), C.byref(frame.params),
+                                     C.c_void_p(pts.data_ptr()), n, C.c_void_p(dist.data_ptr()),
+                                     C.c_void_p(nrm.data_ptr()) if normal else None,
+                                     self._stream(stream))
+        abi.check(rc, "sdf_sample")
+        return dist, nrm
 
     def heatmap(self, steps, which: int = 0, max_steps: int = 128, fmt: int = abi.FORMAT_RGBA8,
                 out=None, stream=None):
