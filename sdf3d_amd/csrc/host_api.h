@@ -58,4 +58,53 @@ void plan_set_camera(RenderPlan* plan, const sdf_camera* camera);
 // Enqueue a prepared plan on `stream`.  SDF_OK or SDF_E_HIP.
 int launch_render_plan(const RenderPlan& plan, void* stream);
 
+// ---- the render kernels' launch geometry and argument contract -------------
+// Shared by the built-in launchers of every render unit (render_kernel.inc)
+// and the run-time specialised one (jit.cpp): each refuses with
+// hipErrorInvalidValue what render_args_fit refuses.
+inline dim3 render_block() { return dim3(64 * kWgWaves); }
+inline dim3 render_grid(const KernelArgs& a) {
+  return dim3((a.width + 8 * kWgWaves - 1) / (8 * kWgWaves), (a.rows + 7) / 8);
+}
+// a row order must be a permutation of exactly the grid's rows (the host
+// builds it so, sdf_abi.cpp Schedule); anything else renders in launch order
+inline bool order_fits(const RenderArgs& r, dim3 grid) {
+  return r.o.n == 0 || (r.o.n == (int)grid.y && r.o.n <= kMaxOrderBlocks);
+}
+// several lights: at most SDF_MAX_LIGHTS, and never into a TILES stream
+inline bool lights_fit(const RenderArgs& r) {
+  return r.l.n == 0 || (r.l.n > 0 && r.l.n <= SDF_MAX_LIGHTS && r.a.format != SDF_FORMAT_TILES &&
+                        r.a.format != SDF_FORMAT_SHADE32F);
+}
+// a material per primitive: one per primitive of a primitive scene, with
+// lights (the materials kernels are lights kernels)
+inline bool materials_fit(const RenderArgs& r) {
+  return r.m.n == 0 || (r.m.n == r.a.prim_count && r.m.n <= SDF_MAX_PRIMS && r.l.n > 0 &&
+                        r.a.scene_kind == SDF_SCENE_PRIMITIVES);
+}
+// mirror reflections: a lights launch that is no stream (lights_fit), with a
+// material per primitive exactly when the scene has a primitive list, and
+// uniforms inside the contract's ranges (the loop over the layers trusts them)
+inline bool reflect_fit(const RenderArgs& r) {
+  if (!r.r.on) return true;
+  const bool prims = r.a.scene_kind == SDF_SCENE_PRIMITIVES;
+  return r.l.n > 0 && r.a.format != SDF_FORMAT_TILES && r.a.format != SDF_FORMAT_SHADE32F &&
+         (prims ? r.m.n == r.a.prim_count && r.m.n > 0 : r.m.n == 0) && r.r.bounces >= 0 &&
+         r.r.bounces <= SDF_MAX_BOUNCES && r.r.layer >= -1 && r.r.layer <= r.r.bounces;
+}
+// an environment: a reflect launch (reflect_fit) with known flags, at least
+// one of them, never a glow without a sky, and a fog denominator above 0 (the
+// kernels trust them)
+inline bool env_fit(const RenderArgs& r) {
+  if (!r.e.on) return true;
+  const int32_t all = SDF_ENV_SKY | SDF_ENV_SUN | SDF_ENV_FOG;
+  return r.r.on && r.e.flags != 0 && (r.e.flags & ~all) == 0 &&
+         (!(r.e.flags & SDF_ENV_SUN) || (r.e.flags & SDF_ENV_SKY)) &&
+         (!(r.e.flags & SDF_ENV_FOG) || r.e.fog_den > 0.0f);
+}
+// what a render launch on `grid` may be handed
+inline bool render_args_fit(const RenderArgs& r, dim3 grid) {
+  return order_fits(r, grid) && lights_fit(r) && materials_fit(r) && reflect_fit(r) && env_fit(r);
+}
+
 }  // namespace sdf

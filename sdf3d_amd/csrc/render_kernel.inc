@@ -22,6 +22,10 @@
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #include <math.h>
+
+#include <type_traits>
+
+#include "host_api.h"   // the launchers' grid and argument contract (render_args_fit)
 #else
 // compiled at run time by hipRTC for one scene signature (jit.cpp)
 #define INFINITY __builtin_inff()
@@ -2155,6 +2159,9 @@ __device__ __forceinline__ float4 shade_pixel(KA& A, const Scene& scene, const V
 // sdf_render gives with that light alone.  The count, the colour flag and
 // the lights are uniforms of the kernel-argument segment: one kernel serves
 // every L, and the loop reads scalars.  `ss` sums the lights' shadow counts.
+// (trace_surface plus surface_colour<STEPS, false> below was tried: the same
+// bits and registers, but every render_lights kernel's schedule moved and C4
+// at 1080p ran 1.1-1.5 % slower in both precisions, so the loop stays here.)
 template <bool STEPS, class Scene, class View>
 __device__ __forceinline__ float4 shade_pixel_lights(KA& A, const KARG LightsArgs& L,
                                                      const Scene& scene, const View& V, int x,
@@ -2192,6 +2199,9 @@ __device__ __forceinline__ float4 shade_pixel_lights(KA& A, const KARG LightsArg
 // into the channel sums at once, so only dif and ref (6 values) live across
 // the shadow marches.  trace_surface and light_terms are the shared ones:
 // P, N, ao, (dif_i, x_i) and the step counts are sdf_render_lights's bits.
+// (trace_surface plus surface_colour<STEPS, true> below was tried: the same
+// bits and registers, the fast kernels 1 % faster, but the exact ones 1.1-1.6 %
+// slower on C4 at 1080p, so the fold and the loop stay here.)
 template <bool STEPS, class Scene, class View>
 __device__ __forceinline__ float4 shade_pixel_materials(KA& A, const KARG LightsArgs& L,
                                                         const KARG MaterialArgs& M,
@@ -2234,18 +2244,26 @@ __device__ __forceinline__ float4 shade_pixel_materials(KA& A, const KARG Lights
   return make_float4(acc[0], acc[1], acc[2], 1.0f);
 }
 
-// The pixel's path of mirror bounces (sdf_abi.h "Reflections"): layer j is the
-// materials pipeline above for the fragment whose eye is O_j and whose ray is
-// D_j -- trace_ray, the material fold at P_j (FOLD; a Mandelbulb has the one
-// material of KernelArgs), light_terms per light with the view from O_j, the
-// colour sum C_j -- and the next ray leaves P_j + N_j offset eps, the shadow
-// march's origin, along D_j mirrored at N_j.
+// A surface's colour under the launch's L.n lights (sdf_abi.h "Lights",
+// "Materials"): the ambient part, then every light adds its diffuse and
+// specular to the three channels in index order.  Each light's shadow march
+// starts from a copy of the culling state the single-light kernel has at P,
+// and its terms come from the very light_terms above, so (dif_i, x_i) are the
+// bits sdf_render gives with that light alone.  The count, the colour flag
+// and the lights are uniforms of the kernel-argument segment: one kernel
+// serves every L, and the loop reads scalars.  `ss` sums the lights' shadow
+// counts.
 //
-// reflect_colour is a layer's colour from its surface: shade_pixel_materials's
-// statements after trace_surface, with `mr` (the blended ref) handed back for
-// the weights.
+// FOLD: a material per primitive -- the scene's material fold runs once at P
+// and leaves the surface's blended amb, dif and ref; else the frame's one
+// material (KernelArgs).  The ambient part goes into the channel sums at
+// once, so only dif and ref (6 values) live across the shadow marches.  `mr`
+// (the ref used) is handed back for a reflecting path's weights.
+//
+// It is shade_pixel_materials's (FOLD) and shade_pixel_lights's statements
+// after trace_surface, for the reflect and env kernels' layers.
 template <bool STEPS, bool FOLD, class Scene, class View>
-__device__ __forceinline__ void reflect_colour(KA& A, const KARG LightsArgs& L,
+__device__ __forceinline__ void surface_colour(KA& A, const KARG LightsArgs& L,
                                                const KARG MaterialArgs& M, const Scene& scene,
                                                const View& V, const Surface& S,
                                                const MarchState& mst, int& ss, float (&acc)[3],
@@ -2289,6 +2307,13 @@ __device__ __forceinline__ void reflect_colour(KA& A, const KARG LightsArgs& L,
     }
   }
 }
+
+// The pixel's path of mirror bounces (sdf_abi.h "Reflections"): layer j is the
+// materials pipeline above for the fragment whose eye is O_j and whose ray is
+// D_j -- trace_ray, then surface_colour (FOLD: the material fold at P_j; a
+// Mandelbulb has the one material of KernelArgs) with the view from O_j, the
+// colour sum C_j -- and the next ray leaves P_j + N_j offset eps, the shadow
+// march's origin, along D_j mirrored at N_j.
 
 // What a path carries from layer to layer: the next ray, the weights W_j,
 // the output and the step counts, and whether the lane's path goes on.
@@ -2346,11 +2371,12 @@ struct ReflectPath {
 };
 
 // Layer 0 stands in front of the loop over the reflected layers and is
-// shade_pixel_materials statement for statement -- trace_surface, its eye the
-// uniform camera -- so that fast precision contracts it the way the materials
-// kernels do (layer 0 IS their pixel); the loop's layers take their eye per
-// lane.  (One loop body for every layer, layer 0's eye the camera moved into
-// VGPRs, measured 2-4 % faster, but in fast precision the generic kernel's
+// trace_surface, its eye the uniform camera, then surface_colour, so that
+// fast precision contracts it the way the materials kernels do (layer 0 IS
+// their pixel: tests/test_gpu_reflect.py holds the bits); the loop's layers
+// take their eye per lane.  (One loop body for every layer, layer 0's eye the
+// camera moved into VGPRs, measured 2-4 % faster, but in fast precision the
+// generic kernel's
 // layer 0 then came out a few ulps off sdf_render_materials's: DESIGN.md,
 // Reflections.)  Each layer starts a fresh culling state: the path length a
 // MarchState measures restarts at O_j, which is conservative like the first
@@ -2370,7 +2396,7 @@ __device__ __forceinline__ float4 shade_pixel_reflect(KA& A, const KARG LightsAr
     int spj = 0, ssj = 0;
     trace_surface(A, scene, V, x, y, spj, mst, S);
     float C[3], mr[3];
-    reflect_colour<STEPS, FOLD>(A, L, M, scene, V, S, mst, ssj, C, mr);
+    surface_colour<STEPS, FOLD>(A, L, M, scene, V, S, mst, ssj, C, mr);
     path.D = S.ray;
     path.layer_done(A, R, 0, S, C, mr, spj, ssj);
   }
@@ -2381,7 +2407,7 @@ __device__ __forceinline__ float4 shade_pixel_reflect(KA& A, const KARG LightsAr
     int spj = 0, ssj = 0;
     trace_ray(A, scene, path.O, path.D, spj, mst, S);
     float C[3], mr[3];
-    reflect_colour<STEPS, FOLD>(A, L, M, scene, V, S, mst, ssj, C, mr);
+    surface_colour<STEPS, FOLD>(A, L, M, scene, V, S, mst, ssj, C, mr);
     path.layer_done(A, R, j, S, C, mr, spj, ssj);
   }
   sp = path.sp;
@@ -2422,7 +2448,7 @@ __device__ __forceinline__ void env_layer(KA& A, const KARG LightsArgs& L,
     S.ao = 1.0f;
   } else {
     trace_shape(A, scene, mst, S);
-    reflect_colour<STEPS, FOLD>(A, L, M, scene, V, S, mst, ssj, C, mr);
+    surface_colour<STEPS, FOLD>(A, L, M, scene, V, S, mst, ssj, C, mr);
     if (fog) {
       f = env_fog<SDF_EXACT>(S.d, E.fog_end, E.fog_den, E.fog_inv);
 #pragma unroll
@@ -3092,127 +3118,49 @@ extern "C" int sdf_debug_stats(unsigned long long* out, int n, int reset) {
 }
 #endif
 
-// one launch of scene kernel S: the TILES / plain-format instantiation, and
-// the step-recording one only when the caller asked for step counts
+// The two run-time booleans of a launch -- step counts asked for, and a
+// supersampled frame -- as template arguments: f(steps, ssaa), each a
+// std::bool_constant.
+template <class F>
+static void with_steps_ssaa(const KernelArgs& a, F&& f) {
+  using T = std::true_type;
+  using N = std::false_type;
+  if (a.ss_log2 > 0) a.steps ? f(T{}, T{}) : f(N{}, T{});
+  else a.steps ? f(T{}, N{}) : f(N{}, N{});
+}
+
+// one launch of scene kernel S: its kernel family by the format and by what
+// rides in the arguments (render_args_fit holds for them), and the
+// step-recording instantiation only when the caller asked for step counts
 template <class S, bool TILES>
 static void launch_scene(const RenderArgs& a, dim3 grid, dim3 block, hipStream_t s) {
-  if constexpr (TILES) {
-    if (a.a.steps)
-      hipLaunchKernelGGL((SDF_NS::render_tiles<S, true, true>), grid, block, 0, s, a);
-    else
-      hipLaunchKernelGGL((SDF_NS::render_tiles<S, true, false>), grid, block, 0, s, a);
-  } else if (a.e.on) {
-    // a reflect launch with an environment (env_fit)
-    constexpr bool kFold = !SDF_TU_BULB;
-    if (a.a.ss_log2 > 0) {
-      if (a.a.steps)
-        hipLaunchKernelGGL((SDF_NS::render_env<S, true, true, kFold>), grid, block, 0, s, a);
-      else
-        hipLaunchKernelGGL((SDF_NS::render_env<S, false, true, kFold>), grid, block, 0, s, a);
+  constexpr bool kFold = !SDF_TU_BULB;   // a primitive list to fold materials over
+#define SDF_GO(...) hipLaunchKernelGGL((SDF_NS::__VA_ARGS__), grid, block, 0, s, a)
+  with_steps_ssaa(a.a, [&](auto steps, auto ssaa) {
+    constexpr bool STEPS = decltype(steps)::value, SSAA = decltype(ssaa)::value;
+    if constexpr (TILES) {
+      SDF_GO(render_tiles<S, true, STEPS>);   // never supersampled (sdf_validate)
+    } else if (a.e.on) {
+      // a reflect launch with an environment (env_fit)
+      SDF_GO(render_env<S, STEPS, SSAA, kFold>);
+    } else if (a.r.on) {
+      // mirror reflections (reflect_fit: lights, and a material table for every
+      // scene with a primitive list; never TILES)
+      SDF_GO(render_reflect<S, STEPS, SSAA, kFold>);
+    } else if (a.m.n > 0) {
+      // a material per primitive (materials_fit: never a Mandelbulb, which has
+      // no primitive list to fold over; never TILES)
+      if constexpr (kFold) SDF_GO(render_materials<S, STEPS, SSAA>);
+    } else if (a.l.n > 0) {
+      // several lights (the host refuses TILES with them)
+      SDF_GO(render_lights<S, STEPS, SSAA>);
+    } else if constexpr (SSAA) {
+      SDF_GO(render_ssaa<S, STEPS>);
     } else {
-      if (a.a.steps)
-        hipLaunchKernelGGL((SDF_NS::render_env<S, true, false, kFold>), grid, block, 0, s, a);
-      else
-        hipLaunchKernelGGL((SDF_NS::render_env<S, false, false, kFold>), grid, block, 0, s, a);
+      SDF_GO(render<S, false, STEPS>);
     }
-  } else if (a.r.on) {
-    // mirror reflections (reflect_fit: lights, and a material table for every
-    // scene with a primitive list; never TILES)
-    constexpr bool kFold = !SDF_TU_BULB;
-    if (a.a.ss_log2 > 0) {
-      if (a.a.steps)
-        hipLaunchKernelGGL((SDF_NS::render_reflect<S, true, true, kFold>), grid, block, 0, s, a);
-      else
-        hipLaunchKernelGGL((SDF_NS::render_reflect<S, false, true, kFold>), grid, block, 0, s, a);
-    } else {
-      if (a.a.steps)
-        hipLaunchKernelGGL((SDF_NS::render_reflect<S, true, false, kFold>), grid, block, 0, s, a);
-      else
-        hipLaunchKernelGGL((SDF_NS::render_reflect<S, false, false, kFold>), grid, block, 0, s, a);
-    }
-  } else if (a.m.n > 0) {
-    // a material per primitive (lights_fit: never a Mandelbulb, which has no
-    // primitive list to fold over; never TILES)
-    if constexpr (!SDF_TU_BULB) {
-      if (a.a.ss_log2 > 0) {
-        if (a.a.steps)
-          hipLaunchKernelGGL((SDF_NS::render_materials<S, true, true>), grid, block, 0, s, a);
-        else
-          hipLaunchKernelGGL((SDF_NS::render_materials<S, false, true>), grid, block, 0, s, a);
-      } else {
-        if (a.a.steps)
-          hipLaunchKernelGGL((SDF_NS::render_materials<S, true, false>), grid, block, 0, s, a);
-        else
-          hipLaunchKernelGGL((SDF_NS::render_materials<S, false, false>), grid, block, 0, s, a);
-      }
-    }
-  } else if (a.l.n > 0) {
-    // several lights (the host refuses TILES with them)
-    if (a.a.ss_log2 > 0) {
-      if (a.a.steps)
-        hipLaunchKernelGGL((SDF_NS::render_lights<S, true, true>), grid, block, 0, s, a);
-      else
-        hipLaunchKernelGGL((SDF_NS::render_lights<S, false, true>), grid, block, 0, s, a);
-    } else {
-      if (a.a.steps)
-        hipLaunchKernelGGL((SDF_NS::render_lights<S, true, false>), grid, block, 0, s, a);
-      else
-        hipLaunchKernelGGL((SDF_NS::render_lights<S, false, false>), grid, block, 0, s, a);
-    }
-  } else if (a.a.ss_log2 > 0) {
-    if (a.a.steps)
-      hipLaunchKernelGGL((SDF_NS::render_ssaa<S, true>), grid, block, 0, s, a);
-    else
-      hipLaunchKernelGGL((SDF_NS::render_ssaa<S, false>), grid, block, 0, s, a);
-  } else {
-    if (a.a.steps)
-      hipLaunchKernelGGL((SDF_NS::render<S, false, true>), grid, block, 0, s, a);
-    else
-      hipLaunchKernelGGL((SDF_NS::render<S, false, false>), grid, block, 0, s, a);
-  }
-}
-
-static dim3 render_block() { return dim3(64 * kWgWaves); }
-static dim3 render_grid(const KernelArgs& a) {
-  return dim3((a.width + 8 * kWgWaves - 1) / (8 * kWgWaves), (a.rows + 7) / 8);
-}
-// a row order must be a permutation of exactly the grid's rows (the host
-// builds it so, sdf_abi.cpp Schedule); anything else renders in launch order
-static bool order_fits(const RenderArgs& r, dim3 grid) {
-  return r.o.n == 0 || (r.o.n == (int)grid.y && r.o.n <= kMaxOrderBlocks);
-}
-// several lights: at most SDF_MAX_LIGHTS, and never into a TILES stream
-static bool lights_fit(const RenderArgs& r) {
-  return r.l.n == 0 || (r.l.n > 0 && r.l.n <= SDF_MAX_LIGHTS && r.a.format != SDF_FORMAT_TILES &&
-                        r.a.format != SDF_FORMAT_SHADE32F);
-}
-// a material per primitive: one per primitive of a primitive scene, with
-// lights (the materials kernels are lights kernels)
-static bool materials_fit(const RenderArgs& r) {
-  return r.m.n == 0 || (r.m.n == r.a.prim_count && r.m.n <= SDF_MAX_PRIMS && r.l.n > 0 &&
-                        r.a.scene_kind == SDF_SCENE_PRIMITIVES);
-}
-
-// mirror reflections: a lights launch that is no stream (lights_fit), with a
-// material per primitive exactly when the scene has a primitive list, and
-// uniforms inside the contract's ranges (the loop over the layers trusts them)
-static bool reflect_fit(const RenderArgs& r) {
-  if (!r.r.on) return true;
-  const bool prims = r.a.scene_kind == SDF_SCENE_PRIMITIVES;
-  return r.l.n > 0 && r.a.format != SDF_FORMAT_TILES && r.a.format != SDF_FORMAT_SHADE32F &&
-         (prims ? r.m.n == r.a.prim_count && r.m.n > 0 : r.m.n == 0) && r.r.bounces >= 0 &&
-         r.r.bounces <= SDF_MAX_BOUNCES && r.r.layer >= -1 && r.r.layer <= r.r.bounces;
-}
-
-// an environment: a reflect launch (reflect_fit) with known flags, at least
-// one of them, never a glow without a sky, and a fog denominator above 0 (the
-// kernels trust them)
-static bool env_fit(const RenderArgs& r) {
-  if (!r.e.on) return true;
-  const int32_t all = SDF_ENV_SKY | SDF_ENV_SUN | SDF_ENV_FOG;
-  return r.r.on && r.e.flags != 0 && (r.e.flags & ~all) == 0 &&
-         (!(r.e.flags & SDF_ENV_SUN) || (r.e.flags & SDF_ENV_SKY)) &&
-         (!(r.e.flags & SDF_ENV_FOG) || r.e.fog_den > 0.0f);
+  });
+#undef SDF_GO
 }
 
 template <class S>
@@ -3275,9 +3223,7 @@ int SDF_LAUNCH_QUERY(const QueryArgs& q, int variant, void* stream) {
 int SDF_LAUNCH_BULB(const RenderArgs& a, void* stream) {
   const dim3 block = render_block(), grid = render_grid(a.a);
   if (grid.x == 0 || grid.y == 0) return 0;
-  if (!order_fits(a, grid) || !lights_fit(a) || !materials_fit(a) || !reflect_fit(a) ||
-      !env_fit(a))
-    return (int)hipErrorInvalidValue;
+  if (!render_args_fit(a, grid)) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
   if (a.a.format == SDF_FORMAT_TILES) launch_scene<SDF_NS::BulbScene, true>(a, grid, block, s);
@@ -3314,9 +3260,7 @@ int SDF_LAUNCH(const RenderArgs& a, int variant, void* stream) {
   if (variant == kVariantBulb) return SDF_LAUNCH_BULB(a, stream);   // its own unit
   const dim3 block = render_block(), grid = render_grid(a.a);
   if (grid.x == 0 || grid.y == 0) return 0;
-  if (!order_fits(a, grid) || !lights_fit(a) || !materials_fit(a) || !reflect_fit(a) ||
-      !env_fit(a))
-    return (int)hipErrorInvalidValue;
+  if (!render_args_fit(a, grid)) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   if (a.a.format == SDF_FORMAT_TILES) return launch_variant<true>(a, variant, grid, block, s);
   return launch_variant<false>(a, variant, grid, block, s);

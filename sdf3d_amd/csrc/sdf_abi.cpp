@@ -609,6 +609,49 @@ struct sdf_schedule {
   sdf::Schedule* s;
 };
 
+// The launch of a made plan under `schedule` (null: launch order, no costs):
+// the schedule's order and cost words into the plan, the launch, and the
+// schedule's bookkeeping when the plan has the schedule's rows.
+static int run_plan(sdf::RenderPlan& plan, sdf_schedule* schedule, void* stream) {
+  if (!schedule) return sdf::launch_render_plan(plan, stream);
+  int rc = sdf::schedule_apply(schedule->s, &plan);
+  if (rc != SDF_OK) return rc;
+  rc = sdf::launch_render_plan(plan, stream);
+  if (rc == SDF_OK && plan.rows == schedule->s->rows)
+    rc = sdf::schedule_after(schedule->s, stream);
+  return rc;
+}
+
+// The launch's lights (sdf_render_lights).  The lights kernels serve every
+// L >= 1, one plain light included.
+static void fill_lights(sdf::RenderPlan& plan, const sdf_light* lights, int32_t n, int32_t flags) {
+  sdf::LightsArgs& l = plan.lights;
+  l.n = n;
+  l.flags = flags;
+  // the summed ambient: fp32, index order (this unit is built without
+  // contraction; one light gives its own value)
+  float la = lights[0].ambient;
+  for (int i = 1; i < n; ++i) la = la + lights[i].ambient;
+  l.la = la;
+  for (int i = 0; i < n; ++i)
+    for (int c = 0; c < 3; ++c) {
+      l.pos[i][c] = lights[i].pos[c];
+      l.color[i][c] = lights[i].color[c];
+    }
+}
+
+// The launch's material table, one row per primitive (sdf_render_materials).
+static void fill_materials(sdf::RenderPlan& plan, const sdf_material* materials, int32_t n) {
+  sdf::MaterialArgs& m = plan.materials;
+  m.n = n;
+  for (int i = 0; i < n; ++i)
+    for (int c = 0; c < 3; ++c) {
+      m.m[i][c] = materials[i].amb[c];
+      m.m[i][3 + c] = materials[i].dif[c];
+      m.m[i][6 + c] = materials[i].ref[c];
+    }
+}
+
 extern "C" {
 
 int sdf_abi_version(void) { return SDF_ABI_VERSION; }
@@ -644,14 +687,7 @@ int sdf_render_scheduled(const sdf_scene* scene, const sdf_camera* camera, const
   int rc = sdf::make_render_plan(scene, camera, light, material, params, tiling, rgba, steps,
                                  &plan);
   if (rc != SDF_OK) return rc;
-  if (schedule) {
-    rc = sdf::schedule_apply(schedule->s, &plan);
-    if (rc != SDF_OK) return rc;
-  }
-  rc = sdf::launch_render_plan(plan, stream);
-  if (rc == SDF_OK && schedule && plan.rows == schedule->s->rows)
-    rc = sdf::schedule_after(schedule->s, stream);
-  return rc;
+  return run_plan(plan, schedule, stream);
 }
 
 int sdf_defaults(sdf_scene* scene, sdf_camera* camera, sdf_light* light,
@@ -888,7 +924,7 @@ int sdf_render(const sdf_scene* scene, const sdf_camera* camera, const sdf_light
   const int rc = sdf::make_render_plan(scene, camera, light, material, params, tiling, rgba,
                                        steps, &plan);
   if (rc != SDF_OK) return rc;
-  return sdf::launch_render_plan(plan, stream);
+  return run_plan(plan, nullptr, stream);
 }
 
 int sdf_validate_lights(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
@@ -928,27 +964,8 @@ int sdf_render_lights(const sdf_scene* scene, const sdf_camera* camera, const sd
   rc = sdf::make_render_plan(scene, camera, &lights[0], material, params, tiling, rgba, steps,
                              &plan);
   if (rc != SDF_OK) return rc;
-  sdf::LightsArgs& l = plan.lights;
-  l.n = nlights;
-  l.flags = light_flags;
-  // the summed ambient: fp32, index order (this unit is built without
-  // contraction; one light gives its own value)
-  float la = lights[0].ambient;
-  for (int i = 1; i < nlights; ++i) la = la + lights[i].ambient;
-  l.la = la;
-  for (int i = 0; i < nlights; ++i)
-    for (int c = 0; c < 3; ++c) {
-      l.pos[i][c] = lights[i].pos[c];
-      l.color[i][c] = lights[i].color[c];
-    }
-  if (schedule) {
-    rc = sdf::schedule_apply(schedule->s, &plan);
-    if (rc != SDF_OK) return rc;
-  }
-  rc = sdf::launch_render_plan(plan, stream);
-  if (rc == SDF_OK && schedule && plan.rows == schedule->s->rows)
-    rc = sdf::schedule_after(schedule->s, stream);
-  return rc;
+  fill_lights(plan, lights, nlights, light_flags);
+  return run_plan(plan, schedule, stream);
 }
 
 // amb, dif and ref of two materials byte for byte (the shininess apart)
@@ -1006,35 +1023,11 @@ int sdf_render_materials(const sdf_scene* scene, const sdf_camera* camera,
   rc = sdf::make_render_plan(scene, camera, &lights[0], &materials[0], params, tiling, rgba,
                              steps, &plan);
   if (rc != SDF_OK) return rc;
-  // the lights as sdf_render_lights fills them: the materials kernels are
-  // lights kernels for every L >= 1, one plain light included
-  sdf::LightsArgs& l = plan.lights;
-  l.n = nlights;
-  l.flags = light_flags;
-  float la = lights[0].ambient;
-  for (int i = 1; i < nlights; ++i) la = la + lights[i].ambient;
-  l.la = la;
-  for (int i = 0; i < nlights; ++i)
-    for (int c = 0; c < 3; ++c) {
-      l.pos[i][c] = lights[i].pos[c];
-      l.color[i][c] = lights[i].color[c];
-    }
-  sdf::MaterialArgs& m = plan.materials;
-  m.n = nmaterials;
-  for (int i = 0; i < nmaterials; ++i)
-    for (int c = 0; c < 3; ++c) {
-      m.m[i][c] = materials[i].amb[c];
-      m.m[i][3 + c] = materials[i].dif[c];
-      m.m[i][6 + c] = materials[i].ref[c];
-    }
-  if (schedule) {
-    rc = sdf::schedule_apply(schedule->s, &plan);
-    if (rc != SDF_OK) return rc;
-  }
-  rc = sdf::launch_render_plan(plan, stream);
-  if (rc == SDF_OK && schedule && plan.rows == schedule->s->rows)
-    rc = sdf::schedule_after(schedule->s, stream);
-  return rc;
+  // the materials kernels are lights kernels for every L >= 1, one plain
+  // light included
+  fill_lights(plan, lights, nlights, light_flags);
+  fill_materials(plan, materials, nmaterials);
+  return run_plan(plan, schedule, stream);
 }
 
 // the call is sdf_render_materials itself: no bounce, and the composite or
@@ -1082,30 +1075,10 @@ static int launch_reflect(const sdf_scene* scene, const sdf_camera* camera,
   int rc = sdf::make_render_plan(scene, camera, &lights[0], &materials[0], params, tiling, rgba,
                              steps, &plan);
   if (rc != SDF_OK) return rc;
-  // lights and materials as sdf_render_materials fills them; the reflect
-  // kernels are lights kernels and fold the table of every primitive scene
-  // (a Mandelbulb's one material is the plan's own)
-  sdf::LightsArgs& l = plan.lights;
-  l.n = nlights;
-  l.flags = light_flags;
-  float la = lights[0].ambient;
-  for (int i = 1; i < nlights; ++i) la = la + lights[i].ambient;
-  l.la = la;
-  for (int i = 0; i < nlights; ++i)
-    for (int c = 0; c < 3; ++c) {
-      l.pos[i][c] = lights[i].pos[c];
-      l.color[i][c] = lights[i].color[c];
-    }
-  if (scene->kind == SDF_SCENE_PRIMITIVES) {
-    sdf::MaterialArgs& m = plan.materials;
-    m.n = nmaterials;
-    for (int i = 0; i < nmaterials; ++i)
-      for (int c = 0; c < 3; ++c) {
-        m.m[i][c] = materials[i].amb[c];
-        m.m[i][3 + c] = materials[i].dif[c];
-        m.m[i][6 + c] = materials[i].ref[c];
-      }
-  }
+  // the reflect kernels are lights kernels and fold the table of every
+  // primitive scene (a Mandelbulb's one material is the plan's own)
+  fill_lights(plan, lights, nlights, light_flags);
+  if (scene->kind == SDF_SCENE_PRIMITIVES) fill_materials(plan, materials, nmaterials);
   sdf::ReflectArgs& r = plan.reflect;
   r.on = 1;
   r.bounces = reflect->bounces;
@@ -1113,14 +1086,7 @@ static int launch_reflect(const sdf_scene* scene, const sdf_camera* camera,
   r.layer = reflect->layer;
   r.weight = (reflect->flags & SDF_REFLECT_WEIGHT) ? 1 : 0;
   if (env) plan.env = *env;
-  if (schedule) {
-    rc = sdf::schedule_apply(schedule->s, &plan);
-    if (rc != SDF_OK) return rc;
-  }
-  rc = sdf::launch_render_plan(plan, stream);
-  if (rc == SDF_OK && schedule && plan.rows == schedule->s->rows)
-    rc = sdf::schedule_after(schedule->s, stream);
-  return rc;
+  return run_plan(plan, schedule, stream);
 }
 
 int sdf_render_reflect(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
