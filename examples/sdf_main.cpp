@@ -5,8 +5,9 @@
 // cl->get_tic()/get_toc(), :89/:97) and clean up.  The last frame is written
 // as a PPM instead of being presented in a window (:95-96).
 //
-//   sdf_main [--palette] [--reflect B[,strength]] [--sky] [--fog START,END[,r,g,b]]
-//            [--pick X,Y] [width height frames out.ppm scene [samples [lights]]]
+//   sdf_main [--palette] [--reflect B[,strength]] [--sky [--no-sun]] [--fog START,END[,r,g,b]]
+//            [--pick X,Y] [--projection pinhole|equirect]
+//            [width height frames out.ppm scene [samples [lights]]]
 //     scene: ref | csg8 | bulb; samples: 1 (default), 2 or 4 sub-samples per
 //     axis, resolved in the render kernel (single-GPU path only: the frame
 //     driver refuses supersampling)
@@ -23,7 +24,8 @@
 //     1) weighting what it reflects (sdf_render_reflect; single-GPU path
 //     only); without --palette every primitive has the reference's material
 //     --sky (anywhere on the line): rays that leave the scene show sdf::sky(),
-//     the default sky with its sun, instead of shading the far point
+//     the default sky with its sun, instead of shading the far point; with
+//     --no-sun (anywhere on the line) the sky without the sun's glow
 //     --fog START,END[,r,g,b] (anywhere on the line): linear distance fog from
 //     START to END in the sky's horizon colour, or in r,g,b (both:
 //     sdf_render_env, single-GPU path only; without --reflect no bounce)
@@ -32,6 +34,13 @@
 //     pixel (sdf_trace_camera; single-GPU path only), printed as
 //     "pick X,Y: t steps prim nx ny nz" -- prim is the index of the primitive
 //     that owns the hit, -1 when the ray leaves the scene
+//     --projection pinhole|equirect (anywhere on the line): the frame shaded
+//     from a list of rays (sdf_render_rays; single-GPU path only, one sample
+//     per pixel).  pinhole: the render's own rays from sdf_camera_rays, used
+//     as given (SDF_RAYS_UNIT) -- the frame without the option, bit for bit in
+//     exact precision.  equirect: a full panorama from the camera's place,
+//     longitude across and latitude up, its directions built on the host and
+//     normalised by the kernel
 //
 // Multi-GPU: launched once per GPU by any launcher that sets RANK,
 // WORLD_SIZE and LOCAL_RANK (e.g. `torchrun --nproc-per-node 8 --no-python
@@ -50,6 +59,7 @@
 //   sdf_main --views N
 // prints the first N V_mats of that sequence (no GPU work; the tests compare
 // them with sdf3d_amd.camera.Arcball fed the same script).
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -200,6 +210,8 @@ int main(int argc, char** argv) {
   // --palette and --reflect may stand anywhere: take them out of the
   // positional arguments
   bool use_palette = false, use_reflect = false, use_env = false, use_pick = false;
+  bool no_sun = false;
+  std::string projection;
   int pick_x = 0, pick_y = 0;
   sdf_reflect reflect = {0, 1.0f, -1, 0};
   sdf_environment environment = sdf::sky(0);
@@ -230,9 +242,17 @@ int main(int argc, char** argv) {
           std::fprintf(stderr, "sdf_main: --pick X,Y\n");
           return 1;
         }
+      } else if (std::string(argv[i]) == "--projection") {
+        projection = i + 1 < argc ? argv[++i] : "";
+        if (projection != "pinhole" && projection != "equirect") {
+          std::fprintf(stderr, "sdf_main: --projection pinhole|equirect\n");
+          return 1;
+        }
       } else if (std::string(argv[i]) == "--sky") {
         environment.flags |= SDF_ENV_SKY | SDF_ENV_SUN;
         use_env = true;
+      } else if (std::string(argv[i]) == "--no-sun") {
+        no_sun = true;
       } else if (std::string(argv[i]) == "--fog") {
         // 2 or 5 comma-separated numbers
         float v[5];
@@ -259,6 +279,7 @@ int main(int argc, char** argv) {
       }
     }
     argc = n;
+    if (no_sun) environment.flags &= ~SDF_ENV_SUN;
   }
   const int W = argc > 1 ? std::atoi(argv[1]) : 800;   // main.cpp:4 SX
   const int H = argc > 2 ? std::atoi(argv[2]) : 600;   // main.cpp:5 SY
@@ -308,7 +329,7 @@ int main(int argc, char** argv) {
     std::vector<sdf_material> materials;
     if (use_palette)
       materials = sdf::palette(f.scene.kind == SDF_SCENE_PRIMITIVES ? f.scene.count : 1);
-    if ((use_palette || use_reflect || use_env) && lights.empty())
+    if ((use_palette || use_reflect || use_env || !projection.empty()) && lights.empty())
       lights.push_back(f.light);   // the reference's one light
     hipStream_t stream;
     sdf::check_hip(hipStreamCreate(&stream), "hipStreamCreate");
@@ -318,10 +339,41 @@ int main(int argc, char** argv) {
     {
       sdf::Renderer r(W, H, stream);
       Navigator nav;
+      // --projection: the frame's rays, n x 3 floats of origins and of directions
+      const int64_t n = int64_t(W) * H;
+      float *ray_o = nullptr, *ray_d = nullptr;
+      if (!projection.empty()) {
+        sdf::check_hip(hipMalloc(reinterpret_cast<void**>(&ray_o), size_t(n) * 12), "hipMalloc");
+        sdf::check_hip(hipMalloc(reinterpret_cast<void**>(&ray_d), size_t(n) * 12), "hipMalloc");
+      }
+      if (projection == "equirect") {
+        // pixel (x, y)'s centre: longitude -pi .. pi across (0 looks along -z),
+        // latitude -pi/2 .. pi/2 up; any length will do, the kernel normalises
+        const double pi = 3.14159265358979323846;
+        std::vector<float> d(size_t(n) * 3);
+        for (int y = 0; y < H; ++y)
+          for (int x = 0; x < W; ++x) {
+            const double lon = ((2.0 * x + 1.0) / W - 1.0) * pi;
+            const double lat = ((2.0 * y + 1.0) / H - 1.0) * (pi / 2);
+            float* q = &d[(size_t(y) * W + x) * 3];
+            q[0] = float(std::cos(lat) * std::sin(lon));
+            q[1] = float(std::sin(lat));
+            q[2] = float(-std::cos(lat) * std::cos(lon));
+          }
+        sdf::check_hip(hipMemcpy(ray_d, d.data(), d.size() * 4, hipMemcpyHostToDevice),
+                       "hipMemcpy");
+      }
       for (int i = 0; i < frames; ++i) {
         nav.frame(f, i, frames);
         sdf::check_hip(hipEventRecord(t0, stream), "hipEventRecord");
-        if (use_env) r.render(f, lights, light_flags, materials, reflect, environment);
+        if (!projection.empty()) {
+          // the camera's place per pixel, and for a pinhole the render's own rays
+          const bool pinhole = projection == "pinhole";
+          sdf::camera_rays(f, ray_o, pinhole ? ray_d : nullptr, stream);
+          sdf::render_rays(f, lights, light_flags, materials, use_reflect ? &reflect : nullptr,
+                           use_env ? &environment : nullptr, ray_o, ray_d, n, pinhole,
+                           r.device_rgba(), nullptr, stream);
+        } else if (use_env) r.render(f, lights, light_flags, materials, reflect, environment);
         else if (use_reflect) r.render(f, lights, light_flags, materials, reflect);
         else if (use_palette) r.render(f, lights, light_flags, materials);
         else if (lights.empty()) r.render(f);
@@ -333,6 +385,8 @@ int main(int argc, char** argv) {
         std::printf("frame %d: %.3f ms (%.1f Mpixels/s)\n", i, ms, W * H / (ms * 1e3));
       }
       sdf::write_ppm(out, r.download(), W, H);
+      (void)hipFree(ray_o);
+      (void)hipFree(ray_d);
     }
     if (use_pick) {
       sdf::Frame q = f;          // the last frame's camera, one ray per pixel

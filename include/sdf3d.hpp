@@ -465,6 +465,37 @@ inline Hit pick(const Frame& f, int x, int y, hipStream_t stream = nullptr) {
   return out;
 }
 
+// ---- caller-supplied rays (sdf_abi.h "Rays") -----------------------------------
+// The shading pipeline on rays of the caller's own camera model: ray i of
+// `origins` / `dirs` (device, n x 3 packed floats; `unit`: the directions are
+// unit vectors used as given, SDF_RAYS_UNIT) gives pixel i of `rgba` (device, n
+// pixels of f.params.output_format) and, when non-null, entry i of `steps` (n
+// int2).  An empty `materials` gives every primitive f.material; `reflect` and
+// `env` may be null (no bounce, no environment).  The frame's camera, size and
+// samples play no part.  A wave shades 64 consecutive rays: order them in
+// coherent groups of 64.  Asynchronous on `stream`.
+inline void render_rays(const Frame& f, const std::vector<sdf_light>& lights, int32_t light_flags,
+                        const std::vector<sdf_material>& materials, const sdf_reflect* reflect,
+                        const sdf_environment* env, const float* origins, const float* dirs,
+                        int64_t n, bool unit, void* rgba, int32_t* steps = nullptr,
+                        hipStream_t stream = nullptr) {
+  const std::vector<sdf_material> same(
+      f.scene.kind == SDF_SCENE_PRIMITIVES ? static_cast<size_t>(f.scene.count) : 1, f.material);
+  const std::vector<sdf_material>& m = materials.empty() ? same : materials;
+  const sdf_rays rays = {origins, dirs, n, unit ? SDF_RAYS_UNIT : 0, 0};
+  check(sdf_render_rays(&f.scene, lights.data(), static_cast<int32_t>(lights.size()), light_flags,
+                        m.data(), static_cast<int32_t>(m.size()), reflect, env, &f.params, &rays,
+                        rgba, steps, stream),
+        "sdf_render_rays");
+}
+// The rays sdf_render marches for the frame: entry y * width + x of `origins`
+// and `dirs` (device, width * height x 3 packed floats; either may be null) is
+// pixel (x, y)'s eye and unit direction (row 0 = bottom).
+inline void camera_rays(const Frame& f, float* origins, float* dirs,
+                        hipStream_t stream = nullptr) {
+  check(sdf_camera_rays(&f.camera, &f.params, origins, dirs, stream), "sdf_camera_rays");
+}
+
 // ---- multi-device frames (sdf_comm_* / sdf_driver_*) ------------------------
 
 // One RCCL communicator over `world` processes (one per GPU), created from a

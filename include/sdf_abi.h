@@ -224,6 +224,16 @@ typedef struct {
   int32_t* prim;    /* n int32:   the primitive that owns the hit; NULL: none   */
 } sdf_hits;         /* 32 bytes */
 
+/* Caller-supplied rays (sdf_render_rays; "Rays" below): device pointers.     */
+#define SDF_RAYS_UNIT 0x1   /* dirs are unit vectors, used as given */
+typedef struct {
+  const float* origins;   /* device, n x 3 packed fp32 */
+  const float* dirs;      /* device, n x 3 packed fp32 */
+  int64_t n;
+  int32_t flags;          /* SDF_RAYS_* */
+  int32_t reserved;
+} sdf_rays;               /* 32 bytes */
+
 /* Render flags */
 #define SDF_FLAG_SHADOW    0x1  /* soft shadow march (voxel_fragment.frag:205) */
 #define SDF_FLAG_AO         0x2  /* ambient occlusion (extension)               */
@@ -597,6 +607,70 @@ typedef struct {
  *     compacting rays, tilings and several devices, an ambient-occlusion
  *     output and gradients (autograd) are not offered. */
 
+/* Rays (sdf_render_rays: the shading pipeline of "Environment" on rays of the
+ * caller's own -- an orthographic view, a fisheye, a panorama, a stereo pair,
+ * lens distortion, thin-lens jitter, secondary rays; sdf_camera_rays: the
+ * render's own rays as a starting point).  The rendering counterpart of
+ * "Queries": entry i of the outputs belongs to ray i.
+ *   - ray i has O = origins[i] as given.  Without SDF_RAYS_UNIT, D =
+ *     normalize(dirs[i]) in the precision's own normalize, as "Queries" defines
+ *     it for sdf_trace.  With SDF_RAYS_UNIT, D = dirs[i] unchanged: the caller
+ *     promises |D| <= 1 + 2^-22, the bound the kernels' cached-gap culling is
+ *     proven for (every D of sdf_camera_rays keeps it).  Outside that bound the
+ *     values are unspecified, but the kernel still terminates: every loop is
+ *     bounded by max_steps, and no address depends on ray data.
+ *   - entry i of `rgba` is the "Environment" pixel whose (O_0, D_0) is (O, D);
+ *     with env NULL or env->flags 0 the "Reflections" pixel; with reflect NULL
+ *     that of bounces 0 with layer -1.  Layers, weights, the composite, the
+ *     `layer` passes, SDF_REFLECT_WEIGHT, sky, sun and fog carry over word for
+ *     word; the view vector of layer 0 is normalize(O - P_0).  In exact
+ *     precision the rays of sdf_camera_rays under SDF_RAYS_UNIT therefore give
+ *     sdf_render_env's frame bit for bit.
+ *   - `steps`, when non-null, is n int2 with the sums those blocks define; as
+ *     there, every shadow march then runs to the reference's break.
+ *   - inactive rays: a ray whose D has a component that is not finite -- without
+ *     SDF_RAYS_UNIT a direction whose normalize has one (a length of 0 or NaN,
+ *     an infinite component), with SDF_RAYS_UNIT such a component as given.
+ *     Nothing is marched for it; its output is all-zero, alpha included, so
+ *     alpha 0 is a mask the caller can use (outside a fisheye's image circle,
+ *     say); its steps are (0, 0).  RGB32F has no alpha and writes (0, 0, 0).
+ *     This differs on purpose from sdf_trace, which marches such a ray as the
+ *     oracle does: a shaded NaN path has no reference meaning, and a mask is
+ *     what a custom camera needs.
+ *   - params: every shading and march field is used.  width, height and samples
+ *     play no part: a copy with width / height at sdf_defaults' values is what
+ *     is validated, together with a default camera.  samples > 1 is
+ *     SDF_E_UNSUPPORTED: the caller supplies more rays and averages.
+ *   - formats: RGBA32F, RGBA16F, RGBA8 and RGB32F, n packed pixels.  TILES and
+ *     SHADE32F are SDF_E_UNSUPPORTED.  There is no tiling, no schedule and no
+ *     multi-device form.
+ *   - dispatch follows sdf_render's: a built-in variant when the scene matches
+ *     one, under SDF_DISPATCH_AUTO a run-time specialised rays kernel for any
+ *     other primitive list (counted by sdf_jit_count; the generic kernel with
+ *     SDF3D_JIT=0), GENERIC and UNCULLED as there.
+ *   - SDF_E_INVALID_ARG, decided before any device call: rays, scene or params
+ *     NULL; unknown ray flag bits; n < 0 or n > 2^30; NULL origins, dirs or rgba
+ *     with n > 0; anything sdf_validate_env rejects for these lights,
+ *     materials, reflect and env (its SDF_E_UNSUPPORTED cases stay
+ *     SDF_E_UNSUPPORTED).  sdf_validate_rays is that check without the buffers;
+ *     it makes no device call.  n = 0 is SDF_OK: nothing is launched, no buffer
+ *     is touched and no device is needed.
+ *   - device data: origins must be finite and at most 1e15 in magnitude, the
+ *     caller's duty as under "Queries".
+ *   - a wave shades 64 consecutive rays: order the rays in coherent groups of
+ *     64 (an 8 x 8 tile of an image, say); rays of one wave that go different
+ *     ways wait for each other.
+ *   - sdf_camera_rays: entry y * width + x of `origins` / `dirs` (device,
+ *     width * height x 3 packed fp32) is (O_0, D_0) of pixel (x, y) as sdf_render
+ *     forms them in params->precision; the default aspect applies.  Either
+ *     output may be NULL, not both.  It uses width, height and precision and is
+ *     validated like sdf_trace_camera; samples > 1 is SDF_E_UNSUPPORTED.
+ *   - asynchronous on `stream`.  SDF_ABI_VERSION stays 12: detect the entry
+ *     points by the symbol.
+ *   - supersampling, tilings and schedules, frame sequences and several
+ *     devices, TILES and SHADE32F output, per-ray distance limits, sorting or
+ *     compacting rays and a NaN-marching path for shaded rays are not offered. */
+
 /* Framebuffer element formats (4 channels R,G,B,A per pixel).
  *   RGBA32F  the shader's float fragment_color (voxel_fragment.frag:12,210).
  *   RGBA16F  IEEE half, round to nearest even.
@@ -864,6 +938,22 @@ int sdf_trace_camera(const sdf_scene* scene, const sdf_camera* camera, const sdf
                      const sdf_hits* hits, void* stream);
 int sdf_sample(const sdf_scene* scene, const sdf_params* params, const float* points, int64_t n,
                float* dist, float* normal, void* stream);
+
+/* Shading of caller-supplied rays ("Rays" above).  reflect NULL: no bounce;
+ * env NULL: no environment.  Additions: SDF_ABI_VERSION stays 12, detect them
+ * by the symbol.  sdf_validate_rays is the host-only check sdf_render_rays
+ * makes first (no device call). */
+int sdf_validate_rays(const sdf_scene* scene, const sdf_light* lights, int32_t nlights,
+                      int32_t light_flags, const sdf_material* materials, int32_t nmaterials,
+                      const sdf_reflect* reflect, const sdf_environment* env,
+                      const sdf_params* params, const sdf_rays* rays);
+int sdf_render_rays(const sdf_scene* scene, const sdf_light* lights, int32_t nlights,
+                    int32_t light_flags, const sdf_material* materials, int32_t nmaterials,
+                    const sdf_reflect* reflect, const sdf_environment* env,
+                    const sdf_params* params, const sdf_rays* rays, void* rgba, int32_t* steps,
+                    void* stream);
+int sdf_camera_rays(const sdf_camera* camera, const sdf_params* params, float* origins,
+                    float* dirs, void* stream);
 
 /* Scatter `nparts` packed row-block buffers (part r = rank r's output for
  * tiling {block_rows, r, nparts}), laid out back to back in `parts` with a

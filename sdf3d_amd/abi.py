@@ -20,6 +20,7 @@ REFLECT_WEIGHT = 0x1  # SDF_REFLECT_WEIGHT: with layer >= 0, W_layer instead of 
 ENV_SKY = 0x1         # SDF_ENV_SKY: a missed layer's colour is the sky along its ray
 ENV_SUN = 0x2         # SDF_ENV_SUN: with ENV_SKY, a glow around sun_dir
 ENV_FOG = 0x4         # SDF_ENV_FOG: linear distance fog on every layer that is not sky
+RAYS_UNIT = 0x1       # SDF_RAYS_UNIT: sdf_render_rays uses dirs as given (unit vectors)
 
 # status codes
 SDF_OK = 0
@@ -107,6 +108,12 @@ class sdf_hits(C.Structure):
                 ("prim", C.c_void_p)]
 
 
+class sdf_rays(C.Structure):
+    """The rays of sdf_render_rays: device pointers to n x 3 packed fp32."""
+    _fields_ = [("origins", C.c_void_p), ("dirs", C.c_void_p), ("n", C.c_int64),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class sdf_params(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("max_steps", C.c_int32),
                 ("max_dist", C.c_float), ("eps", C.c_float), ("shadow_k", C.c_float),
@@ -135,6 +142,7 @@ STRUCT_SIZES = {
     "sdf_primitive": 64, "sdf_scene": 8 + 64 * SDF_MAX_PRIMS + 32, "sdf_camera": 88,
     "sdf_light": 32, "sdf_material": 40, "sdf_params": 80, "sdf_tiling": 24,
     "sdf_driver_config": 36, "sdf_reflect": 16, "sdf_environment": 96, "sdf_hits": 32,
+    "sdf_rays": 32,
 }
 MAX_QUERY = 1 << 30   # rays or points of one sdf_trace / sdf_sample call
 
@@ -201,6 +209,15 @@ SIGNATURES = {
                                    C.c_void_p]),
     "sdf_sample": (C.c_int, [_P(sdf_scene), _P(sdf_params), C.c_void_p, C.c_int64, C.c_void_p,
                              C.c_void_p, C.c_void_p]),
+    "sdf_validate_rays": (C.c_int, [_P(sdf_scene), _P(sdf_light), C.c_int32, C.c_int32,
+                                    _P(sdf_material), C.c_int32, _P(sdf_reflect),
+                                    _P(sdf_environment), _P(sdf_params), _P(sdf_rays)]),
+    "sdf_render_rays": (C.c_int, [_P(sdf_scene), _P(sdf_light), C.c_int32, C.c_int32,
+                                  _P(sdf_material), C.c_int32, _P(sdf_reflect),
+                                  _P(sdf_environment), _P(sdf_params), _P(sdf_rays), C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    "sdf_camera_rays": (C.c_int, [_P(sdf_camera), _P(sdf_params), C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
     "sdf_tiles_decode_checked": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _P(sdf_tiling),
                                            _P(C.c_int64), C.c_int32, C.c_int32, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

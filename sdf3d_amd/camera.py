@@ -9,6 +9,10 @@ constant (the reference's `ms_decaytime` / `gmp_decaytime`); a gamepad stick
 inside the deadzone (`gmp_deadzone`) counts as released.  The C++ host API
 (include/sdf3d.hpp sdf::Arcball) computes the same sequence bit for bit
 (tests/test_camera.py runs both).
+
+Below the arcball: two NumPy ray generators, ``ortho_rays`` and
+``equirect_rays``, as worked examples of a camera model of the caller's own for
+``Renderer.render_rays`` (include/sdf_abi.h "Rays").
 """
 from __future__ import annotations
 
@@ -93,3 +97,46 @@ class Arcball:
         m = np.array([[cy, 0.0, sy, self.pan_x], [sp * sy, cp, -sp * cy, self.pan_y],
                       [-cp * sy, sp, cp * cy, 0.0], [0.0, 0.0, 0.0, 1.0]], dtype=np.float64)
         return m.T.reshape(-1).astype(np.float32)
+
+
+# ---- ray generators for Renderer.render_rays (sdf_abi.h "Rays") --------------
+# Worked examples of a camera model of the caller's own: NumPy on the host,
+# float64 arithmetic rounded to float32 once.  Both return (origins, dirs) as
+# float32 (H, W, 3) arrays whose entry [y, x] is pixel (x, y)'s ray, row 0 the
+# bottom row as in a render; dirs are unit vectors to float32 rounding, so the
+# kernel should normalise them (render_rays(..., unit=False)).  Flatten to
+# (H W, 3) for the call; for speed hand the rays over in coherent groups of 64
+# (8 x 8 tiles), not necessarily in this row-major order.
+
+def _pixel_centres(n: int) -> np.ndarray:
+    """(2 i + 1) / n - 1 for i < n: the render's quad coordinate of pixel i."""
+    return (2.0 * np.arange(n, dtype=np.float64) + 1.0) / n - 1.0
+
+
+def ortho_rays(frame, half_height: float):
+    """An orthographic view through the frame's camera: parallel rays along its
+    view direction, starting on the plane through the eye, which spans
+    2 half_height (times the aspect across) in world units."""
+    cam, p = frame.camera, frame.params
+    w, h = p.width, p.height
+    inv = np.linalg.inv(np.array(list(cam.view), dtype=np.float64).reshape(4, 4).T)
+    eye = (inv @ np.array([cam.eye[0], cam.eye[1], cam.eye[2], 1.0]))[:3]
+    right, up, fwd = inv[:3, 0], inv[:3, 1], -inv[:3, 2]
+    aspect = cam.aspect if cam.aspect > 0 else w / h
+    qx, qy = np.meshgrid(_pixel_centres(w), _pixel_centres(h))     # [y, x]
+    o = (eye + (qx * half_height * aspect)[..., None] * right
+         + (qy * half_height)[..., None] * up)
+    d = np.broadcast_to(fwd / np.linalg.norm(fwd), (h, w, 3))
+    return np.ascontiguousarray(o, dtype=np.float32), np.ascontiguousarray(d, dtype=np.float32)
+
+
+def equirect_rays(eye, width: int, height: int):
+    """A full panorama from `eye`: longitude across (-pi at the left edge to pi
+    at the right, 0 looking along -z), latitude up (-pi/2 at the bottom edge to
+    pi/2 at the top), each pixel's ray through its centre."""
+    lon = _pixel_centres(width) * math.pi
+    lat = _pixel_centres(height) * (math.pi / 2)
+    lon, lat = np.meshgrid(lon, lat)                                # [y, x]
+    d = np.stack([np.cos(lat) * np.sin(lon), np.sin(lat), -np.cos(lat) * np.cos(lon)], axis=-1)
+    o = np.broadcast_to(np.asarray(eye, dtype=np.float64).reshape(3), (height, width, 3))
+    return np.ascontiguousarray(o, dtype=np.float32), np.ascontiguousarray(d, dtype=np.float32)

@@ -107,4 +107,27 @@ inline bool render_args_fit(const RenderArgs& r, dim3 grid) {
   return order_fits(r, grid) && lights_fit(r) && materials_fit(r) && reflect_fit(r) && env_fit(r);
 }
 
+// ---- the rays kernels' launch geometry and argument contract ----------------
+// Shared by the built-in launchers (render_kernel.inc launch_rays_scene) and
+// the run-time specialised one (jit.cpp launch_rays_jit).  64 rays to a wave;
+// sdf_render_rays holds n to 2^30, so the grid fits.
+inline dim3 rays_grid(const RaysArgs& q) {
+  return dim3((unsigned)((q.n + 64 * kWgWaves - 1) / (64 * kWgWaves)));
+}
+// what a rays launch may be handed: the rules of a reflect render with (e.on)
+// or without an environment, on a list of at most 2^30 rays with buffers
+inline bool rays_args_fit(const RaysArgs& q) {
+  RenderArgs r{};
+  r.a.format = q.a.format;
+  r.a.prim_count = q.a.prim_count;
+  r.a.scene_kind = q.a.scene_kind;
+  r.l.n = q.l.n;
+  r.m.n = q.m.n;
+  r.r = q.r;
+  r.e = q.e;
+  return q.n > 0 && q.n <= (1ll << 30) && q.in0 && q.in1 && q.a.rgba && q.r.on &&
+         (q.flags & ~SDF_RAYS_UNIT) == 0 && lights_fit(r) && materials_fit(r) && reflect_fit(r) &&
+         env_fit(r);
+}
+
 }  // namespace sdf

@@ -168,6 +168,29 @@ struct QueryArgs {
   int32_t kind;     // QueryKind
   int32_t reserved;
 };
+// ---- caller-supplied rays (sdf_render_rays, sdf_camera_rays) -------------------
+// The argument block of the rays kernels (render_kernel.inc render_rays /
+// render_rays_env / camera_rays), their own: RenderArgs is full, and its
+// RowOrder is of no use to a list of rays.  `a` carries the scene, the march
+// and shading parameters and the outputs (a.rgba: n pixels of a.format,
+// a.steps: n int2 or null; camera_rays: the hoisted camera and the frame
+// size); l, m, r and e are a render's.  `in0` holds n x 3 packed floats (ray
+// origins), `in1` the directions; camera_rays writes through `out0` / `out1`
+// (either may be null).
+struct RaysArgs {
+  KernelArgs a;   // first: the scene evaluators read it at the start of the segment
+  LightsArgs l;
+  MaterialArgs m;
+  ReflectArgs r;  // on = 1 always: no bounce is bounces 0 with layer -1
+  EnvArgs e;      // on = 0: the reflect layers (render_rays), else render_rays_env
+  const float* in0;
+  const float* in1;
+  float* out0;
+  float* out1;
+  long long n;    // rays
+  int32_t flags;  // SDF_RAYS_*
+  int32_t reserved;
+};
 
 // Waves (8x8 tiles side by side) per render workgroup (render_kernel.inc
 // render / render_tiles / render_ssaa; the built-in and the run-time
@@ -215,6 +238,7 @@ static_assert(sizeof(FramesArgs) <= 4096, "FramesArgs exceeds the 4 KiB kernel-a
 static_assert(sizeof(KernelArgs) <= 4096, "KernelArgs exceeds the 4 KiB kernel-argument limit");
 static_assert(sizeof(RenderArgs) <= 4096, "RenderArgs exceeds the 4 KiB kernel-argument limit");
 static_assert(sizeof(QueryArgs) <= 4096, "QueryArgs exceeds the 4 KiB kernel-argument limit");
+static_assert(sizeof(RaysArgs) <= 4096, "RaysArgs exceeds the 4 KiB kernel-argument limit");
 // Tiles a wave takes per queue request, queues per launch (workgroup b uses
 // queue b % queues, i.e. one per XCD), and the queues' spacing in uint32s:
 // requests on one address serialise at the memory-side atomic unit, so the
@@ -249,6 +273,14 @@ int launch_query_exact(const QueryArgs& q, int variant, void* stream);
 int launch_query_fast(const QueryArgs& q, int variant, void* stream);
 int launch_query_exact_bulb(const QueryArgs& q, void* stream);
 int launch_query_fast_bulb(const QueryArgs& q, void* stream);
+// the rays kernels (sdf_render_rays) and the ray generator (sdf_camera_rays) of
+// each precision; kVariantBulb is forwarded to the Mandelbulb units
+int launch_rays_exact(const RaysArgs& q, int variant, void* stream);
+int launch_rays_fast(const RaysArgs& q, int variant, void* stream);
+int launch_rays_exact_bulb(const RaysArgs& q, void* stream);
+int launch_rays_fast_bulb(const RaysArgs& q, void* stream);
+int launch_camera_rays_exact(const RaysArgs& q, void* stream);
+int launch_camera_rays_fast(const RaysArgs& q, void* stream);
 int launch_deinterleave(const void* parts, int nparts, int part_stride_rows, int row_bytes,
                         int height, int block_rows, void* frame, void* stream);
 int launch_heatmap(const int32_t* steps, int count, int which, int max_steps, int format,
@@ -321,6 +353,8 @@ constexpr int kEscapeDwords = 72;   // bitstream bound: 3 width bytes + 3 x 12 x
 int launch_render_jit(const RenderArgs& a, const int* sig, int n, bool exact, void* stream);
 // the same for a query (its kind enters the cache key); -1 = none
 int launch_query_jit(const QueryArgs& q, const int* sig, int n, bool exact, void* stream);
+// the same for sdf_render_rays (steps and env enter the cache key); -1 = none
+int launch_rays_jit(const RaysArgs& q, const int* sig, int n, bool exact, void* stream);
 int jit_compiled_count();
 
 // ---- compile-time scene variants ------------------------------------------

@@ -89,6 +89,9 @@
 #define SDF_LAUNCH_FRAMES_BULB launch_frames_exact_bulb
 #define SDF_LAUNCH_QUERY launch_query_exact
 #define SDF_LAUNCH_QUERY_BULB launch_query_exact_bulb
+#define SDF_LAUNCH_RAYS launch_rays_exact
+#define SDF_LAUNCH_RAYS_BULB launch_rays_exact_bulb
+#define SDF_LAUNCH_CAMERA_RAYS launch_camera_rays_exact
 #else
 #define SDF_NS fast_impl
 #define SDF_LAUNCH launch_render_fast
@@ -97,6 +100,9 @@
 #define SDF_LAUNCH_FRAMES_BULB launch_frames_fast_bulb
 #define SDF_LAUNCH_QUERY launch_query_fast
 #define SDF_LAUNCH_QUERY_BULB launch_query_fast_bulb
+#define SDF_LAUNCH_RAYS launch_rays_fast
+#define SDF_LAUNCH_RAYS_BULB launch_rays_fast_bulb
+#define SDF_LAUNCH_CAMERA_RAYS launch_camera_rays_fast
 #endif
 
 namespace sdf {
@@ -3094,6 +3100,156 @@ void query(QueryArgs args) {
   query_body<Scene, KIND>();
 }
 
+// ---- caller-supplied rays (sdf_abi.h "Rays": sdf_render_rays, sdf_camera_rays) --
+// The path of shade_pixel_reflect (ENV: shade_pixel_env) whose layer 0 is read
+// from memory instead of being formed from (x, y): every layer, the first
+// included, is what those functions' loops run for j >= 1 -- trace_ray and
+// surface_colour, or trace_march and env_layer, the very device functions --
+// from the lane's own eye.  In exact precision nothing is contracted, so the
+// ray of a pixel gives the pixel's bits (tests/test_gpu_rays.py holds them).
+template <bool STEPS, bool FOLD, bool ENV, class Scene, class View>
+__device__ __forceinline__ float4 shade_ray(KA& A, const KARG LightsArgs& L,
+                                            const KARG MaterialArgs& M,
+                                            const KARG ReflectArgs& R, const KARG EnvArgs& E,
+                                            const Scene& scene, const View& V, const V3 O,
+                                            const V3 D, int& sp, int& ss) {
+  ReflectPath path;
+  path.O = O;
+  path.D = D;
+#pragma unroll 1
+  for (int j = 0; path.live; j++) {
+    MarchState mst;
+    Surface S;
+    int spj = 0;
+    if constexpr (ENV) {
+      trace_march(A, scene, path.O, path.D, spj, mst, S);
+      S.cam = path.O;
+      S.ray = path.D;
+      env_layer<STEPS, FOLD>(A, L, M, R, E, scene, V, j, S, mst, spj, path);
+    } else {
+      int ssj = 0;
+      trace_ray(A, scene, path.O, path.D, spj, mst, S);
+      float C[3], mr[3];
+      surface_colour<STEPS, FOLD>(A, L, M, scene, V, S, mst, ssj, C, mr);
+      path.layer_done(A, R, j, S, C, mr, spj, ssj);
+    }
+  }
+  sp = path.sp;
+  ss = path.ss;
+  return make_float4(path.acc[0], path.acc[1], path.acc[2], 1.0f);
+}
+
+// lane = ray i of the buffers, a wave 64 consecutive rays, loaded as query_body
+// loads them; O as given, D = dirs[i] under SDF_RAYS_UNIT (a uniform), else its
+// normalize in the precision's own form.  A ray whose D has a component that
+// is not finite is inactive: it stores its zeros and leaves through a real
+// branch, never if-converted into the march.  A ragged last wave leaves with
+// its lanes beyond n idle.  No address depends on ray data.
+template <class Scene, bool STEPS, bool FOLD, bool ENV>
+__device__ __forceinline__ void rays_body() {
+  const KARG char* const seg = (const KARG char*)__builtin_amdgcn_kernarg_segment_ptr();
+  const KARG RaysArgs& Q = *(const KARG RaysArgs*)seg;
+  KA& A = Q.a;
+  const long long i = (long long)blockIdx.x * (64 * kWgWaves) + threadIdx.x;
+  if (i >= Q.n) return;
+  const float* const o = Q.in0 + 3 * i;
+  const V3 O = mk(o[0], o[1], o[2]);
+  const float* const r = Q.in1 + 3 * i;
+  V3 D = mk(r[0], r[1], r[2]);
+  if (!(Q.flags & SDF_RAYS_UNIT)) D = normalize(D);
+  const bool odd = !(fabsf(D.x) < INFINITY && fabsf(D.y) < INFINITY && fabsf(D.z) < INFINITY);
+  if (__builtin_amdgcn_ballot_w64(odd) != 0) {
+    asm volatile("" ::: "memory");   // a real branch: never if-converted into the march
+    if (odd) {
+      store_pixel(A.format, A.rgba, (size_t)i, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+      if constexpr (STEPS) {
+        if (A.steps) reinterpret_cast<int2*>(A.steps)[i] = make_int2(0, 0);
+      }
+      return;
+    }
+  }
+  const Scene scene(A);
+  const KARG LightsArgs& L = *(const KARG LightsArgs*)(seg + __builtin_offsetof(RaysArgs, l));
+  const KARG MaterialArgs& M = *(const KARG MaterialArgs*)(seg + __builtin_offsetof(RaysArgs, m));
+  const KARG ReflectArgs& R = *(const KARG ReflectArgs*)(seg + __builtin_offsetof(RaysArgs, r));
+  const KARG EnvArgs& E = *(const KARG EnvArgs*)(seg + __builtin_offsetof(RaysArgs, e));
+  int sp = 0, ss = 0;
+  const float4 c = shade_ray<STEPS, FOLD, ENV>(A, L, M, R, E, scene, ArgsView{A}, O, D, sp, ss);
+  store_pixel(A.format, A.rgba, (size_t)i, c);
+  if constexpr (STEPS) {
+    if (A.steps) reinterpret_cast<int2*>(A.steps)[i] = make_int2(sp, ss);
+  }
+}
+
+// the rays instantiations (sdf_render_rays), with and without step recording:
+// render_rays runs the reflect kernels' layers, render_rays_env the env
+// kernels', at the env kernels' occupancy (DESIGN.md, render_rays: the
+// register figures)
+#ifndef SDF_RAYS_WAVES_PER_EU
+#define SDF_RAYS_WAVES_PER_EU SDF_ENV_WAVES_PER_EU
+#endif
+template <class Scene, bool STEPS, bool FOLD>
+__global__ __launch_bounds__(64 * kWgWaves) __attribute__((amdgpu_waves_per_eu(SDF_RAYS_WAVES_PER_EU, SDF_RAYS_WAVES_PER_EU)))
+void render_rays(RaysArgs args) {
+  (void)args;
+  rays_body<Scene, STEPS, FOLD, false>();
+}
+template <class Scene, bool STEPS, bool FOLD>
+__global__ __launch_bounds__(64 * kWgWaves) __attribute__((amdgpu_waves_per_eu(SDF_RAYS_WAVES_PER_EU, SDF_RAYS_WAVES_PER_EU)))
+void render_rays_env(RaysArgs args) {
+  (void)args;
+  rays_body<Scene, STEPS, FOLD, true>();
+}
+
+#if !SDF_TU_BULB && !defined(__HIPCC_RTC__)
+// sdf_camera_rays: (O_0, D_0) of pixel (x, y), entry y * width + x.  The
+// statements are trace_surface's own, restated: lifted out of it into a shared
+// function, fast precision contracted the normalisations' sums of squares in
+// another order and every fast kernel's rays moved by an ulp (see there), so
+// the render kernels keep theirs in place.  Waves are the render's 8x8 tiles;
+// either output may be null (a uniform branch).
+__global__ __launch_bounds__(64 * kWgWaves)
+void camera_rays(RaysArgs args) {
+  (void)args;
+  const KARG RaysArgs& Q = *(const KARG RaysArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  KA& A = Q.a;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int x = blockIdx.x * (8 * kWgWaves) + wave * 8 + (lane & 7);
+  const int y = blockIdx.y * 8 + (lane >> 3);
+  if (x >= A.width || y >= A.height) return;
+#if SDF_EXACT && SDF_EXACT_QDIV
+  const float qx = crm::div_refined((float)(2 * x + 1), (float)A.width, A.inv_width) - 1.0f;
+  const float qy = crm::div_refined((float)(2 * y + 1), (float)A.height, A.inv_height) - 1.0f;
+#elif SDF_EXACT
+  const float qx = (float)(2 * x + 1) / (float)A.width - 1.0f;
+  const float qy = (float)(2 * y + 1) / (float)A.height - 1.0f;
+#else
+  const float qx = (float)(2 * x + 1) * A.inv_width - 1.0f;
+  const float qy = (float)(2 * y + 1) * A.inv_height - 1.0f;
+#endif
+  V3 r0 = normalize(mk(qx * A.aspect, qy, A.focal));
+  KF m = A.inv_view;
+  V3 r1 = mk(m[0] * r0.x + m[4] * r0.y + m[8] * r0.z + m[12] * 0.0f,
+             m[1] * r0.x + m[5] * r0.y + m[9] * r0.z + m[13] * 0.0f,
+             m[2] * r0.x + m[6] * r0.y + m[10] * r0.z + m[14] * 0.0f);
+  const V3 ray = normalize(r1);
+  const size_t i = (size_t)y * A.width + x;
+  if (Q.out0) {
+    float* const q = Q.out0 + 3 * i;
+    q[0] = A.cam[0];
+    q[1] = A.cam[1];
+    q[2] = A.cam[2];
+  }
+  if (Q.out1) {
+    float* const q = Q.out1 + 3 * i;
+    q[0] = ray.x;
+    q[1] = ray.y;
+    q[2] = ray.z;
+  }
+}
+#endif
+
 #undef scene_sdf
 #undef DIVK
 #undef SMIN_K
@@ -3215,6 +3371,59 @@ int SDF_LAUNCH_QUERY(const QueryArgs& q, int variant, void* stream) {
     default:
       return launch_query_scene<SDF_NS::GenericScene>(q, s);
   }
+}
+#endif
+
+// one launch of scene kernel S for sdf_render_rays: 64 rays to a wave, the env
+// kernels when an environment rides in the arguments, the step-recording
+// instantiation only when the caller asked for step counts.  It refuses what
+// the kernels' loops would trust blindly (host_api.h rays_args_fit).
+template <class S>
+static int launch_rays_scene(const RaysArgs& q, hipStream_t s) {
+  constexpr bool kFold = !SDF_TU_BULB;   // a primitive list to fold materials over
+  if (q.n <= 0) return 0;
+  if (!rays_args_fit(q)) return (int)hipErrorInvalidValue;
+  const dim3 block(64 * kWgWaves), grid(rays_grid(q));
+  (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
+#define SDF_GO(...) hipLaunchKernelGGL((SDF_NS::__VA_ARGS__), grid, block, 0, s, q)
+  if (q.e.on) {
+    if (q.a.steps) SDF_GO(render_rays_env<S, true, kFold>);
+    else SDF_GO(render_rays_env<S, false, kFold>);
+  } else {
+    if (q.a.steps) SDF_GO(render_rays<S, true, kFold>);
+    else SDF_GO(render_rays<S, false, kFold>);
+  }
+#undef SDF_GO
+  return (int)hipGetLastError();
+}
+
+#if SDF_TU_BULB
+int SDF_LAUNCH_RAYS_BULB(const RaysArgs& q, void* stream) {
+  return launch_rays_scene<SDF_NS::BulbScene>(q, (hipStream_t)stream);
+}
+#else
+int SDF_LAUNCH_RAYS(const RaysArgs& q, int variant, void* stream) {
+  if (variant == kVariantBulb) return SDF_LAUNCH_RAYS_BULB(q, stream);   // its own unit
+  hipStream_t s = (hipStream_t)stream;
+  switch (variant) {
+#define SDF_LAUNCH_FIXED(id, ...) \
+  case id:                        \
+    return launch_rays_scene<SDF_NS::FixedScene<__VA_ARGS__>>(q, s);
+    SDF_FIXED_VARIANTS(SDF_LAUNCH_FIXED)
+#undef SDF_LAUNCH_FIXED
+    default:
+      return launch_rays_scene<SDF_NS::GenericScene>(q, s);
+  }
+}
+
+// sdf_camera_rays: the render's grid of 8x8 tiles over width x height
+int SDF_LAUNCH_CAMERA_RAYS(const RaysArgs& q, void* stream) {
+  const dim3 block = render_block();
+  const dim3 grid((q.a.width + 8 * kWgWaves - 1) / (8 * kWgWaves), (q.a.height + 7) / 8);
+  if (q.a.width <= 0 || q.a.height <= 0 || (!q.out0 && !q.out1)) return (int)hipErrorInvalidValue;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(SDF_NS::camera_rays, grid, block, 0, (hipStream_t)stream, q);
+  return (int)hipGetLastError();
 }
 #endif
 

@@ -1146,19 +1146,9 @@ int sdf_validate_env(const sdf_scene* scene, const sdf_camera* camera, const sdf
   return SDF_OK;
 }
 
-int sdf_render_env(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
-                   int32_t nlights, int32_t light_flags, const sdf_material* materials,
-                   int32_t nmaterials, const sdf_reflect* reflect, const sdf_environment* env,
-                   const sdf_params* params, const sdf_tiling* tiling, void* rgba, int32_t* steps,
-                   sdf_schedule* schedule, void* stream) {
-  // nothing switched on: sdf_render_reflect's own path, kernels and bits
-  if (!env || env->flags == 0)
-    return sdf_render_reflect(scene, camera, lights, nlights, light_flags, materials, nmaterials,
-                              reflect, params, tiling, rgba, steps, schedule, stream);
-  const int rc = sdf_validate_env(scene, camera, lights, nlights, light_flags, materials,
-                                  nmaterials, reflect, env, params, tiling);
-  if (rc != SDF_OK) return rc;
-  // the validated fields of the features that are on; the rest stays zero
+// A validated environment's uniforms (flags != 0): the fields of the features
+// that are on; the rest stays zero
+static sdf::EnvArgs fill_env(const sdf_environment* env) {
   sdf::EnvArgs e{};
   e.on = 1;
   e.flags = env->flags;
@@ -1181,6 +1171,22 @@ int sdf_render_env(const sdf_scene* scene, const sdf_camera* camera, const sdf_l
     e.fog_den = env->fog_end - env->fog_start;   // RN, > 0 (validate_environment)
     e.fog_inv = 1.0f / e.fog_den;
   }
+  return e;
+}
+
+int sdf_render_env(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
+                   int32_t nlights, int32_t light_flags, const sdf_material* materials,
+                   int32_t nmaterials, const sdf_reflect* reflect, const sdf_environment* env,
+                   const sdf_params* params, const sdf_tiling* tiling, void* rgba, int32_t* steps,
+                   sdf_schedule* schedule, void* stream) {
+  // nothing switched on: sdf_render_reflect's own path, kernels and bits
+  if (!env || env->flags == 0)
+    return sdf_render_reflect(scene, camera, lights, nlights, light_flags, materials, nmaterials,
+                              reflect, params, tiling, rgba, steps, schedule, stream);
+  const int rc = sdf_validate_env(scene, camera, lights, nlights, light_flags, materials,
+                                  nmaterials, reflect, env, params, tiling);
+  if (rc != SDF_OK) return rc;
+  const sdf::EnvArgs e = fill_env(env);
   return launch_reflect(scene, camera, lights, nlights, light_flags, materials, nmaterials, reflect,
                         &e, params, tiling, rgba, steps, schedule, stream);
 }
@@ -1296,6 +1302,123 @@ int sdf_sample(const sdf_scene* scene, const sdf_params* params, const float* po
   if (n == 0) return SDF_OK;
   return query_launch(sdf::kQueryPoints, scene, nullptr, q, points, nullptr, n, dist, nullptr,
                       normal, nullptr, stream);
+}
+
+// ---- caller-supplied rays (sdf_abi.h "Rays") ----------------------------------
+namespace {
+const sdf_reflect kNoBounce = {0, 1.0f, -1, 0};   // reflect NULL: bounces 0, the composite
+
+// The params a rays call is validated and run with: the caller's, with the
+// frame size at sdf_defaults' values (a list of rays has none).
+sdf_params rays_params(const sdf_params& p) {
+  sdf_params d;
+  sdf_defaults(nullptr, nullptr, nullptr, nullptr, &d, 0, 0);
+  sdf_params q = p;
+  q.width = d.width;
+  q.height = d.height;
+  return q;
+}
+
+// One validated sdf_render_rays: the render's own plan (scene blocks, culling
+// bounds, shading parameters, dispatch; its camera and frame size unused) with
+// the lights, the table, the reflect and env uniforms of a reflect launch and
+// the ray buffers in place of a frame's geometry.
+int rays_launch(const sdf_scene* scene, const sdf_light* lights, int32_t nlights,
+                int32_t light_flags, const sdf_material* materials, int32_t nmaterials,
+                const sdf_reflect& reflect, const sdf_environment* env, const sdf_params& q,
+                const sdf_rays& rays, void* rgba, int32_t* steps, void* stream) {
+  sdf_camera c;
+  sdf_defaults(nullptr, &c, nullptr, nullptr, nullptr, 0, 0);
+  std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
+  const int rc = sdf::make_render_plan(scene, &c, &lights[0], &materials[0], &q, nullptr, rgba,
+                                       steps, plan.get());
+  if (rc != SDF_OK) return rc;
+  fill_lights(*plan, lights, nlights, light_flags);
+  if (scene->kind == SDF_SCENE_PRIMITIVES) fill_materials(*plan, materials, nmaterials);
+  std::unique_ptr<sdf::RaysArgs> a(new sdf::RaysArgs());
+  a->a = plan->a;
+  a->l = plan->lights;
+  a->m = plan->materials;
+  a->r.on = 1;
+  a->r.bounces = reflect.bounces;
+  a->r.strength = reflect.strength;
+  a->r.layer = reflect.layer;
+  a->r.weight = (reflect.flags & SDF_REFLECT_WEIGHT) ? 1 : 0;
+  if (env && env->flags != 0) a->e = fill_env(env);
+  a->in0 = rays.origins;
+  a->in1 = rays.dirs;
+  a->n = rays.n;
+  a->flags = rays.flags;
+  int err = -1;
+  if (plan->jit) err = sdf::launch_rays_jit(*a, plan->sig, plan->nsig, plan->exact, stream);
+  if (err == -1)
+    err = plan->exact ? sdf::launch_rays_exact(*a, plan->variant, stream)
+                      : sdf::launch_rays_fast(*a, plan->variant, stream);
+  return err == hipSuccess ? SDF_OK : SDF_E_HIP;
+}
+}  // namespace
+
+int sdf_validate_rays(const sdf_scene* scene, const sdf_light* lights, int32_t nlights,
+                      int32_t light_flags, const sdf_material* materials, int32_t nmaterials,
+                      const sdf_reflect* reflect, const sdf_environment* env,
+                      const sdf_params* params, const sdf_rays* rays) {
+  if (!rays || !scene || !params) return SDF_E_INVALID_ARG;
+  if (rays->flags & ~SDF_RAYS_UNIT) return SDF_E_INVALID_ARG;
+  if (rays->n < 0 || rays->n > kMaxQuery) return SDF_E_INVALID_ARG;
+  if (rays->n > 0 && (!rays->origins || !rays->dirs)) return SDF_E_INVALID_ARG;
+  sdf_camera c;
+  sdf_defaults(nullptr, &c, nullptr, nullptr, nullptr, 0, 0);
+  const sdf_params q = rays_params(*params);
+  const int rc = sdf_validate_env(scene, &c, lights, nlights, light_flags, materials, nmaterials,
+                                  reflect ? reflect : &kNoBounce, env, &q, nullptr);
+  if (rc != SDF_OK) return rc;
+  // the caller supplies more rays and averages; a stream has no list of rays
+  if (q.samples > 1 || q.output_format == SDF_FORMAT_TILES ||
+      q.output_format == SDF_FORMAT_SHADE32F)
+    return SDF_E_UNSUPPORTED;
+  return SDF_OK;
+}
+
+int sdf_render_rays(const sdf_scene* scene, const sdf_light* lights, int32_t nlights,
+                    int32_t light_flags, const sdf_material* materials, int32_t nmaterials,
+                    const sdf_reflect* reflect, const sdf_environment* env,
+                    const sdf_params* params, const sdf_rays* rays, void* rgba, int32_t* steps,
+                    void* stream) {
+  const int rc = sdf_validate_rays(scene, lights, nlights, light_flags, materials, nmaterials,
+                                   reflect, env, params, rays);
+  if (rc != SDF_OK) return rc;
+  if (rays->n == 0) return SDF_OK;   // nothing to launch, no device needed
+  if (!rgba) return SDF_E_INVALID_ARG;
+  return rays_launch(scene, lights, nlights, light_flags, materials, nmaterials,
+                     reflect ? *reflect : kNoBounce, env, rays_params(*params), *rays, rgba, steps,
+                     stream);
+}
+
+int sdf_camera_rays(const sdf_camera* camera, const sdf_params* params, float* origins,
+                    float* dirs, void* stream) {
+  if (!camera || !params || (!origins && !dirs)) return SDF_E_INVALID_ARG;
+  sdf_scene s;
+  sdf_defaults(&s, nullptr, nullptr, nullptr, nullptr, 0, 0);
+  const sdf_params q = query_params(*params, true);
+  const int rc = validate_query(&s, camera, q);
+  if (rc != SDF_OK) return rc;
+  if (params->samples > 1) return SDF_E_UNSUPPORTED;   // one ray per pixel
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return SDF_E_NO_DEVICE;
+  // the hoisted camera and the quad mapping of a render of this frame size
+  std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
+  std::unique_ptr<sdf::RaysArgs> a(new sdf::RaysArgs());
+  plan->a.width = q.width;
+  plan->a.height = q.height;
+  sdf::plan_set_camera(plan.get(), camera);
+  a->a = plan->a;
+  a->a.inv_width = 1.0f / (float)q.width;
+  a->a.inv_height = 1.0f / (float)q.height;
+  a->out0 = origins;
+  a->out1 = dirs;
+  const int err = q.precision == SDF_PRECISION_EXACT ? sdf::launch_camera_rays_exact(*a, stream)
+                                                     : sdf::launch_camera_rays_fast(*a, stream);
+  return err == hipSuccess ? SDF_OK : SDF_E_HIP;
 }
 
 int sdf_jit_count(void) { return sdf::jit_compiled_count(); }

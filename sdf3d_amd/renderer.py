@@ -394,6 +394,83 @@ class Renderer:
         abi.check(rc, "sdf_sample")
         return dist, nrm
 
+    # ---- caller-supplied rays (sdf_abi.h "Rays") ----------------------------
+    def render_rays(self, frame: Frame, origins, dirs, unit: bool = False, out=None,
+                    steps=False, lights=None, light_flags: int = 0, materials=None,
+                    reflect=None, env=None, stream=None):
+        """Shade n rays of the caller's own through ``frame.scene``
+        (sdf_render_rays): ray i starts at ``origins[i]`` and runs along
+        ``dirs[i]`` -- any non-zero length, the kernel normalises; with `unit`
+        (SDF_RAYS_UNIT) the directions are unit vectors used as given, as
+        ``camera_rays`` returns them.  `origins` and `dirs` are contiguous
+        float32 (n, 3) tensors on this renderer's device, used in place.
+        `lights`, `light_flags`, `materials`, `reflect` and `env` are
+        ``render``'s, with its defaults; the frame's camera, size and samples
+        play no part.  Returns (rgba (n, ch) of ``frame.params.output_format``,
+        steps (n, 2) int32 or None).  A ray whose direction has no finite
+        normalisation is inactive: all-zero output, alpha included.  A wave
+        shades 64 consecutive rays, so order them in coherent groups of 64.
+        Asynchronous on `stream`."""
+        torch = self.torch
+        o, d = self._n3(origins, "origins"), self._n3(dirs, "dirs")
+        if o.shape != d.shape:
+            raise ValueError("origins and dirs must have the same shape")
+        n = o.shape[0]
+        fmt = frame.params.output_format
+        if fmt not in (abi.FORMAT_RGBA32F, abi.FORMAT_RGBA16F, abi.FORMAT_RGBA8,
+                       abi.FORMAT_RGB32F):
+            raise ValueError("render_rays writes RGBA32F, RGBA16F, RGBA8 or RGB32F pixels")
+        dt, ch = torch_dtype(fmt), channels(fmt)
+        rgba = torch.empty((n, ch), dtype=dt, device=self.device) if out is None else out
+        if tuple(rgba.shape) != (n, ch) or rgba.dtype != dt or not rgba.is_contiguous() \
+                or rgba.device != self.device:
+            raise ValueError(f"out must be a contiguous {dt} ({n}, {ch}) tensor on {self.device}")
+        st = steps if isinstance(steps, torch.Tensor) else (
+            torch.empty((n, 2), dtype=torch.int32, device=self.device) if steps else None)
+        if st is not None and (tuple(st.shape) != (n, 2) or st.dtype != torch.int32
+                               or not st.is_contiguous() or st.device != self.device):
+            raise ValueError(f"steps must be a contiguous int32 ({n}, 2) tensor on {self.device}")
+        if reflect is not None and not isinstance(reflect, abi.sdf_reflect):
+            bounces, strength = reflect
+            reflect = abi.sdf_reflect(int(bounces), float(strength), -1, 0)
+        if materials is None:
+            prims = frame.scene.kind == abi.SCENE_PRIMITIVES
+            materials = [frame.material] * (frame.scene.count if prims else 1)
+        materials = list(materials)
+        marr = (abi.sdf_material * max(len(materials), 1))(*materials)
+        lights = [frame.light] if lights is None else list(lights)
+        arr = (abi.sdf_light * max(len(lights), 1))(*lights)
+        rays = abi.sdf_rays(o.data_ptr() if n else None, d.data_ptr() if n else None, n,
+                            abi.RAYS_UNIT if unit else 0, 0)
+        with self._on_device():
+            rc = self.lib.sdf_render_rays(
+                C.byref(frame.scene), arr, len(lights), int(light_flags), marr, len(materials),
+                C.byref(reflect) if reflect is not None else None,
+                C.byref(env) if env is not None else None, C.byref(frame.params),
+                C.byref(rays), C.c_void_p(rgba.data_ptr()) if n else None,
+                C.c_void_p(st.data_ptr()) if st is not None and n else None,
+                self._stream(stream))
+        abi.check(rc, "sdf_render_rays")
+        return rgba, st
+
+    def camera_rays(self, frame: Frame, stream=None):
+        """The rays ``render`` marches (sdf_camera_rays): (origins, dirs), each a
+        float32 (H, W, 3) tensor whose entry [y, x] is pixel (x, y)'s eye and
+        unit direction in the frame's precision -- a starting point to perturb,
+        and with ``render_rays(..., unit=True)`` on their (H W, 3) views the
+        frame ``render`` gives.  One ray per pixel: ``frame.params.samples`` > 1
+        is refused.  Asynchronous on `stream`."""
+        torch = self.torch
+        p = frame.params
+        o = torch.empty((p.height, p.width, 3), dtype=torch.float32, device=self.device)
+        d = torch.empty((p.height, p.width, 3), dtype=torch.float32, device=self.device)
+        with self._on_device():
+            rc = self.lib.sdf_camera_rays(C.byref(frame.camera), C.byref(p),
+                                          C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                          self._stream(stream))
+        abi.check(rc, "sdf_camera_rays")
+        return o, d
+
     def heatmap(self, steps, which: int = 0, max_steps: int = 128, fmt: int = abi.FORMAT_RGBA8,
                 out=None, stream=None):
         """Turbo-coloured view of a `steps` tensor (rows, W, 2) from render()."""

@@ -1,0 +1,444 @@
+"""GPU tests of caller-supplied rays (sdf_render_rays, sdf_camera_rays;
+include/sdf_abi.h "Rays"): sdf_camera_rays against tests/query_ref.py bit for
+bit; in exact precision the camera's rays shaded with SDF_RAYS_UNIT against the
+frame renders, colours and steps bit for bit, on every dispatch path and format;
+rays that are no camera's -- the reflected rays of the CPU reference's walk --
+against that reference; the kernel's normalisation; inactive rays; the ray
+count; the run-time compiled kernel; fast precision within the environment
+tests' measured bound; the host program's --projection.
+
+The ray set is a 37 x 23 frame's: 851 rays, 13 full waves and 19 lanes.  Every
+call writes into buffers followed by sentinel rows, which must survive, and
+every case is shaded with and without a steps buffer, which must not change the
+colours."""
+import ctypes as C
+import os
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import env_ref as ER
+import query_ref as QR
+import reflect_ref as RR
+from parity import quantize
+from sdf3d_amd import abi, renderer as R, scenes
+from test_gpu_env import ALL, FAST_BOUND, WEIGHT, fast_case, the_frame, walk_of
+from test_gpu_env import both as frame_both
+from test_gpu_reflect import LIGHTS, mats_of, ndiff
+from test_gpu_ssaa import _guarded, _sentinel, bits, read_ppm, same
+
+pytestmark = pytest.mark.gpu
+
+f32 = np.float32
+EXACT, FAST = abi.PRECISION_EXACT, abi.PRECISION_FAST
+SKY, SUN, FOG = abi.ENV_SKY, abi.ENV_SUN, abi.ENV_FOG
+W, H = ER.SHAPE
+N = W * H
+ROOT = Path(__file__).resolve().parent.parent
+
+
+def test_the_shape():
+    assert (W, H) == (37, 23) and N == 851 == 13 * 64 + 19
+
+
+# ---- helpers ---------------------------------------------------------------------------
+
+def shade(rd, f, O, D, unit, steps=True, **kw):
+    """Renderer.render_rays into sentinel-filled buffers with guard rows behind
+    them, which are checked: (rgba (n, ch), steps (n, 2) or None) as NumPy."""
+    import torch
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=f32).reshape(-1, 3)).to(rd.device)
+    o, d = dev(O), dev(D)
+    n = o.shape[0]
+    fmt = f.params.output_format
+    buf = _guarded(torch, rd.device, (n, R.channels(fmt)), R.torch_dtype(fmt))
+    sbuf = _guarded(torch, rd.device, (n, 2), torch.int32) if steps else None
+    rd.render_rays(f, o, d, unit=unit, out=buf[:n], steps=sbuf[:n] if steps else False, **kw)
+    torch.cuda.synchronize()
+    assert _sentinel(torch, buf[n:]), "colour buffer: entries past the end were written"
+    if steps:
+        assert _sentinel(torch, sbuf[n:]), "steps buffer: entries past the end were written"
+    return buf[:n].cpu().numpy(), (sbuf[:n].cpu().numpy() if steps else None)
+
+
+def both(rd, f, O, D, unit, **kw):
+    a, _ = shade(rd, f, O, D, unit, steps=False, **kw)
+    b, st = shade(rd, f, O, D, unit, steps=True, **kw)
+    assert same(a, b), "calls with and without a steps buffer differ"
+    return a, st
+
+
+def cam_rays(rd, f):
+    o, d = rd.camera_rays(f)
+    rd.torch.cuda.synchronize()
+    return o.cpu().numpy().reshape(-1, 3), d.cpu().numpy().reshape(-1, 3)
+
+
+def shading(f, n, flags, reflect, eflags):
+    """The keyword arguments Renderer.render and Renderer.render_rays share."""
+    return dict(lights=LIGHTS[:n], light_flags=flags, materials=mats_of(f), reflect=reflect,
+                env=None if eflags is None else ER.environment(eflags))
+
+
+# ---- 1. camera rays ------------------------------------------------------------------------
+
+def aspect_frame(prec=EXACT):
+    f = the_frame("C3", 2, prec)
+    f.camera.aspect = 1.25
+    return f
+
+
+@pytest.mark.parametrize("make", [lambda p: the_frame("REF", 0, p), lambda p: the_frame("C3", 2, p),
+                                  aspect_frame], ids=["REF-p0", "C3-p2", "aspect"])
+def test_camera_rays_are_the_renders(renderer, make):
+    o, d = cam_rays(renderer, make(EXACT))
+    wo, wd = QR.camera_rays(make(EXACT))
+    assert o.shape == d.shape == (N, 3)
+    assert same(o, wo) and same(d, wd), (ndiff(o, wo), ndiff(d, wd))
+    for prec in (EXACT, FAST):
+        _, d = cam_rays(renderer, make(prec))
+        length = np.sqrt((d.astype(np.float64) ** 2).sum(axis=1))
+        print(f"precision {prec}: |D| - 1 in [{length.min() - 1:.3e}, {length.max() - 1:.3e}]")
+        assert length.max() <= 1 + 2.0 ** -22          # what SDF_RAYS_UNIT needs
+
+
+def test_camera_rays_null_output_and_samples(renderer):
+    import torch
+    f = the_frame("C3", 2)
+    o, d = cam_rays(renderer, f)
+    lib = renderer.lib
+    for which in (0, 1):
+        buf = _guarded(torch, renderer.device, (N, 3), torch.float32)
+        ptr = C.c_void_p(buf.data_ptr())
+        rc = lib.sdf_camera_rays(C.byref(f.camera), C.byref(f.params), None if which else ptr,
+                                 ptr if which else None, None)
+        torch.cuda.synchronize()
+        assert rc == abi.SDF_OK
+        assert same(buf[:N].cpu().numpy(), d if which else o) and _sentinel(torch, buf[N:])
+    g = f.copy()
+    g.params.samples = 2
+    with pytest.raises(abi.SdfError) as e:
+        renderer.camera_rays(g)
+    assert e.value.code == abi.SDF_E_UNSUPPORTED
+
+
+# ---- 2. parity with the frame renders ------------------------------------------------------
+
+# (frame, pose, dispatch, lights, light flags, bounces, layer, reflect flags, env flags, format)
+A, G, U = abi.DISPATCH_AUTO, abi.DISPATCH_GENERIC, abi.DISPATCH_UNCULLED
+CLR = abi.LIGHTS_COLOR
+F32, F16, U8, RGB = (abi.FORMAT_RGBA32F, abi.FORMAT_RGBA16F, abi.FORMAT_RGBA8, abi.FORMAT_RGB32F)
+PARITY = [
+    ("REF", 0, A, 1, 0, 0, -1, 0, None, F32), ("REF", 0, A, 3, CLR, 2, -1, 0, ALL, RGB),
+    ("C4", 0, A, 3, CLR, 2, -1, 0, ALL, F32), ("C4", 0, A, 1, 0, 0, -1, 0, ALL, F32),
+    ("C4", 0, A, 1, 0, 2, -1, 0, None, F16), ("C4", 0, A, 3, CLR, 2, 1, 0, ALL, F32),
+    ("C4", 0, A, 1, 0, 2, 1, WEIGHT, None, F32), ("C5", 0, A, 1, 0, 2, -1, 0, ALL, F32),
+    ("C5", 0, A, 3, CLR, 0, -1, 0, None, F32), ("EJ", 2, A, 3, CLR, 2, -1, 0, ALL, F32),
+    ("EJ", 2, A, 1, 0, 2, -1, 0, None, F32), ("C3", 2, G, 1, 0, 2, -1, 0, None, U8),
+    ("C3", 2, U, 3, CLR, 0, -1, 0, ALL, F32), ("C3", 2, U, 3, CLR, 2, -1, 0, None, F32),
+]
+
+
+@pytest.mark.parametrize("name,pose,dispatch,n,flags,bounces,layer,rflags,eflags,fmt", PARITY)
+def test_camera_rays_shade_to_the_frame(renderer, name, pose, dispatch, n, flags, bounces, layer,
+                                        rflags, eflags, fmt):
+    """render_rays(camera_rays, unit=True) is Renderer.render flattened, colours
+    and steps bit for bit (exact precision)."""
+    f = the_frame(name, pose, EXACT, dispatch)
+    f.params.output_format = fmt
+    kw = shading(f, n, flags, RR.reflect(bounces, 1.0, layer, rflags), eflags)
+    want, want_st = frame_both(renderer, f, kw["reflect"], kw["env"], kw["materials"],
+                               kw["lights"], flags)
+    o, d = cam_rays(renderer, f)
+    out, st = both(renderer, f, o, d, True, **kw)
+    want = want.reshape(N, -1)
+    print(f"differing words {int((bits(out) != bits(want)).sum())} of {bits(out).size}")
+    assert same(out, want)
+    assert np.array_equal(st, want_st.reshape(N, 2))
+    if bounces == 0 and eflags is None:
+        # reflect NULL is bounces 0 with layer -1, env NULL none
+        kw["reflect"] = None
+        out2, st2 = both(renderer, f, o, d, True, **kw)
+        assert same(out2, out) and np.array_equal(st2, st)
+
+
+# ---- 3. rays that are not camera rays -------------------------------------------------------
+
+OWN_FRAMES = [("REF", 0), ("C3", 2), ("C4", 0), ("C5", 0)]
+_OWN = {}
+
+
+def own_rays(name, pose):
+    """The reflected rays of the CPU reference's walk (2 bounces, strength 1, one
+    light) as a ray set of their own: (O, D, active, walk sliced to layers 1..)."""
+    if (name, pose) not in _OWN:
+        f = the_frame(name, pose)
+        w = walk_of(name, pose, 2, 1, 0)
+        active = w["alive"][:, :, 1].reshape(N)
+        ws = {k: (v[:, :, 1:] if isinstance(v, np.ndarray) else v) for k, v in w.items()}
+        ws["bounces"] = 1
+        # the conditions under which the sliced walk is the ray set's own path:
+        # enough rays, and a path goes on past its first layer exactly where the
+        # walk's does (the weights restart at W = 1, the walk's carry W_1)
+        assert active.mean() >= 0.30, active.mean()
+        with np.errstate(invalid="ignore"):
+            hit = ~(w["d"][:, :, 1] > f32(f.params.max_dist))
+        k1zero = ((f32(1.0) * w["ref"][:, :, 1]).astype(f32) == 0).all(axis=-1)
+        goes_on = w["alive"][:, :, 1] & hit & ~k1zero
+        assert np.array_equal(goes_on, w["alive"][:, :, 2]), int((goes_on != w["alive"][:, :, 2]).sum())
+        _OWN[(name, pose)] = (w["O"][:, :, 1].reshape(N, 3), w["D"][:, :, 1].reshape(N, 3), active, ws)
+    return _OWN[(name, pose)]
+
+
+@pytest.mark.parametrize("eflags", [0, ALL])
+@pytest.mark.parametrize("name,pose", OWN_FRAMES)
+def test_own_rays_equal_the_reference(renderer, name, pose, eflags):
+    """Two calls (the simpler form: normalize need not leave a unit D's bits
+    alone).  The active rays, compacted, with unit=True against the reference:
+    ER.apply on the walk sliced to layers 1.., which recomputes the weights
+    from W = 1, then RR.composite.  Then the whole set with unit=False and a
+    zero direction for every pixel whose path did not reach layer 1: those
+    entries are all-zero, and the others are the first call's wherever
+    normalize leaves D as it is."""
+    f = the_frame(name, pose)
+    O, D, active, ws = own_rays(name, pose)
+    env = ER.environment(eflags)
+    e = ER.apply(f, ws, env)
+    want = RR.composite(e["C"], e["W"], e["alive"]).reshape(N, 4)
+    want_st = e["steps"].sum(axis=2).astype(np.int32).reshape(N, 2)
+    assert np.isfinite(want).all()
+    kw = dict(lights=LIGHTS[:1], materials=mats_of(f), reflect=RR.reflect(1, 1.0), env=env)
+    out, st = both(renderer, f, O[active], D[active], True, **kw)
+    print(f"{int(active.sum())} of {N} rays active; differing words {ndiff(out, want[active])}")
+    assert same(out, want[active]) and np.array_equal(st, want_st[active])
+    out2, st2 = both(renderer, f, O, np.where(active[:, None], D, f32(0.0)), False, **kw)
+    assert (bits(out2[~active]) == 0).all() and (st2[~active] == 0).all()
+    kept = active & (bits(QR.normalize(D)) == bits(D)).reshape(N, -1).all(axis=1)
+    print(f"normalize leaves {int(kept.sum())} of {int(active.sum())} active directions as they are")
+    assert kept.any()
+    assert same(out2[kept], want[kept]) and np.array_equal(st2[kept], want_st[kept])
+    assert (out2[active][:, 3] == 1).all()
+
+
+# ---- 4. normalisation ------------------------------------------------------------------------
+
+def test_the_kernel_normalises(renderer):
+    """Directions scaled by factors in [0.1, 10] with unit=False give the bits of
+    unit=True on query_ref.normalize of them (exact precision)."""
+    f = the_frame("C4", 0)
+    O, D, active, _ = own_rays("C4", 0)
+    rng = np.random.default_rng(11)
+    scaled = (D[active] * rng.uniform(0.1, 10.0, int(active.sum()))[:, None].astype(f32)).astype(f32)
+    kw = shading(f, 3, CLR, RR.reflect(2, 1.0), ALL)
+    out, st = both(renderer, f, O[active], scaled, False, **kw)
+    want, want_st = both(renderer, f, O[active], QR.normalize(scaled), True, **kw)
+    assert same(out, want) and np.array_equal(st, want_st)
+    assert np.abs(out[:, :3]).max() > 0.1
+
+
+# ---- 5. inactive rays ------------------------------------------------------------------------
+
+ODD_AT = [3, 64, 127, 200, 333, 500, 849, 850]    # first, last and inner lanes of several waves
+
+
+@pytest.mark.parametrize("unit", [False, True])
+def test_inactive_rays(renderer, unit):
+    """query_ref.odd_rays' directions among the camera's rays: all-zero output
+    and steps (0, 0) in every format, and the other rays of their waves keep
+    the bits of a call without them.  A ray is inactive when its D has a
+    component that is not finite: without SDF_RAYS_UNIT every odd direction
+    (normalize gives NaN), with it all but the zero direction, which is finite
+    as given -- that ray is marched, and left out of both comparisons."""
+    f = the_frame("C4", 0)
+    o, d = cam_rays(renderer, f)
+    _, odd = QR.odd_rays()
+    assert len(odd) == len(ODD_AT)
+    d2 = d.copy()
+    d2[ODD_AT] = odd
+    idx = np.array(ODD_AT)
+    inactive = idx if not unit else idx[~np.isfinite(odd).all(axis=1)]
+    assert len(inactive) == (8 if not unit else 7)
+    rest = np.setdiff1d(np.arange(N), idx)
+    for fmt in (F32, F16, U8, RGB):
+        g = f.copy()
+        g.params.output_format = fmt
+        kw = shading(g, 3, CLR, RR.reflect(2, 1.0), ALL)
+        clean, clean_st = both(renderer, g, o, d, unit, **kw)
+        out, st = both(renderer, g, o, d2, unit, **kw)
+        assert (bits(out[inactive]) == 0).all() and (st[inactive] == 0).all(), fmt
+        assert same(out[rest], clean[rest]) and np.array_equal(st[rest], clean_st[rest]), fmt
+        assert (clean_st[:, 0] > 0).all()
+        # without an environment, and with no bounce asked for
+        kw = shading(g, 1, 0, None, None)
+        out, st = both(renderer, g, o, d2, unit, **kw)
+        assert (bits(out[inactive]) == 0).all() and (st[inactive] == 0).all(), fmt
+
+
+# ---- 6. the ray count ------------------------------------------------------------------------
+
+def test_the_first_n_results_do_not_depend_on_n(renderer):
+    import torch
+    f = the_frame("C4", 0)
+    o, d = cam_rays(renderer, f)
+    kw = shading(f, 3, CLR, RR.reflect(2, 1.0), ALL)
+    full, full_st = both(renderer, f, o, d, True, **kw)
+    for n in (1, 63, 64, 65):
+        out, st = both(renderer, f, o[:n], d[:n], True, **kw)
+        assert same(out, full[:n]) and np.array_equal(st, full_st[:n]), n
+    # n = 0 touches nothing (shade checks the whole of both buffers: all guard)
+    out, st = both(renderer, f, o[:0], d[:0], True, **kw)
+    assert out.shape == (0, 4) and st.shape == (0, 2)
+    rays = abi.sdf_rays(None, None, 0, 0, 0)
+    marr = (abi.sdf_material * 8)(*kw["materials"])
+    larr = (abi.sdf_light * 3)(*kw["lights"])
+    buf = _guarded(torch, renderer.device, (4, 4), torch.float32)
+    rc = renderer.lib.sdf_render_rays(C.byref(f.scene), larr, 3, CLR, marr, 8, None, None,
+                                      C.byref(f.params), C.byref(rays),
+                                      C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr()), None)
+    torch.cuda.synchronize()
+    assert rc == abi.SDF_OK and _sentinel(torch, buf)
+
+
+# ---- 7. the run-time compiled kernel ---------------------------------------------------------
+
+def rays_scene(prec=EXACT):
+    """cylinder, plane, capsule (smooth union): no built-in variant, and a
+    signature no other test file uses, so SDF_DISPATCH_AUTO compiles its rays
+    kernel at run time."""
+    f = scenes.config("C3", W, H, precision=prec, pose=2)
+    C.memset(C.addressof(f.scene.prims), 0, C.sizeof(f.scene.prims))
+    f.scene.count = 3
+    scenes._prim(f.scene, 0, abi.PRIM_CYLINDER, abi.OP_UNION, 0.0, -0.4, 0.25, 0.1, 0.18, 0.25)
+    scenes._prim(f.scene, 1, abi.PRIM_PLANE, abi.OP_UNION, 0.0, 0.0, 1.0, 0.0, 0.0)
+    scenes._prim(f.scene, 2, abi.PRIM_CAPSULE, abi.OP_SMOOTH_UNION, 0.08, 0.3, 0.1, 0.1, 0.7, 0.35,
+                 0.0, 0.08)
+    f.params.dispatch = abi.DISPATCH_AUTO
+    return f
+
+
+def jit_case():
+    f = rays_scene()
+    return f, shading(f, 2, CLR, RR.reflect(2, 0.75), ALL)
+
+
+CHILD = """
+import sys
+import numpy as np
+sys.path[:0] = [{root!r}, {tests!r}]
+import torch
+import test_gpu_rays as T
+from sdf3d_amd import Renderer
+rd = Renderer("cuda:0")
+f, kw = T.jit_case()
+o, d = T.cam_rays(rd, f)
+out, st = T.both(rd, f, o, d, True, **kw)
+assert rd.lib.sdf_jit_count() == 0
+np.save({out!r}, out)
+np.save({st!r}, st)
+"""
+
+
+def test_runtime_specialised_scene_compiles_one_kernel(renderer, tmp_path):
+    f, kw = jit_case()
+    jit = os.environ.get("SDF3D_JIT") != "0"
+    count = renderer.lib.sdf_jit_count
+    o, d = cam_rays(renderer, f)
+    want, want_st = frame_both(renderer, f, kw["reflect"], kw["env"], kw["materials"], kw["lights"],
+                               CLR)                       # compiles the scene's render kernels
+    before = count()
+    out, _ = shade(renderer, f, o, d, True, steps=False, **kw)
+    assert count() - before == (1 if jit else 0)           # one rays kernel on first use
+    for r, ef in ((RR.reflect(0, 1.0), SKY), (RR.reflect(3, 0.5, 2), FOG), (RR.reflect(2, 0.75), ALL)):
+        again, _ = shade(renderer, f, o, d, True, steps=False, **dict(kw, reflect=r,
+                                                                       env=ER.environment(ef)))
+        assert count() - before == (1 if jit else 0)       # none on the second
+    assert same(out, again) and same(out, want.reshape(N, 4))
+    # step recording and no environment are instantiations of their own
+    out2, st = shade(renderer, f, o, d, True, steps=True, **kw)
+    assert same(out2, out) and np.array_equal(st, want_st.reshape(N, 2))
+    shade(renderer, f, o, d, True, steps=False, **dict(kw, env=None))
+    assert count() - before == (3 if jit else 0)
+    # the generic kernel in a child process gives the same bits
+    paths = dict(root=str(ROOT), tests=str(ROOT / "tests"), out=str(tmp_path / "out.npy"),
+                 st=str(tmp_path / "st.npy"))
+    r = subprocess.run([sys.executable, "-c", CHILD.format(**paths)], capture_output=True,
+                       text=True, timeout=300, env=dict(os.environ, SDF3D_JIT="0"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert same(np.load(paths["out"]), out) and np.array_equal(np.load(paths["st"]), st)
+
+
+# ---- 8. fast precision -----------------------------------------------------------------------
+
+def own_layers(rd, f, o, d, bounces, env, mats, lights):
+    """The rays kernel's own per-layer steps [N, J, 2] and the layers it traced
+    [N, J], by `layer` passes (test_gpu_env.own_layers for a list of rays)."""
+    Ss = []
+    for j in range(bounces + 1):
+        kw = dict(lights=lights, materials=mats, env=env)
+        cj, sj = both(rd, f, o, d, True, reflect=RR.reflect(bounces, 1.0, j), **kw)
+        wj, wsj = both(rd, f, o, d, True, reflect=RR.reflect(bounces, 1.0, j, WEIGHT), **kw)
+        assert np.array_equal(sj, wsj)
+        assert (cj[:, 3] == 1).all() and (wj[:, 3] == 1).all()
+        dead = sj[:, 0] == 0
+        assert (bits(cj[dead, :3]) == 0).all() and (bits(wj[dead, :3]) == 0).all()
+        assert (sj[dead] == 0).all()
+        Ss.append(sj)
+    Sj = np.stack(Ss, axis=1)
+    return Sj, Sj[..., 0] > 0
+
+
+def rays_fast_deviation(rd, name, bounces):
+    """test_gpu_env.fast_deviation with the frame shaded from its camera rays."""
+    f, mats = fast_case(name)
+    lights, env = [LIGHTS[0]], ER.environment(ALL)
+    o, d = cam_rays(rd, f)
+    Sj, alive = own_layers(rd, f, o, d, bounces, env, mats, lights)
+    out, st = both(rd, f, o, d, True, lights=lights, materials=mats,
+                   reflect=RR.reflect(bounces, 1.0), env=env)
+    assert np.array_equal(st, Sj.sum(axis=1))
+    J = bounces + 1
+    return ER.fast_deviation(f, mats, lights, env, bounces, out.reshape(H, W, 4),
+                             Sj.reshape(H, W, J, 2), alive.reshape(H, W, J))
+
+
+@pytest.mark.parametrize("bounces", [1, 2])
+@pytest.mark.parametrize("name", ["C4", "C3", "REF"])
+def test_fast_is_near_the_reference(renderer, name, bounces):
+    """The fast composite of the camera's rays with SKY | SUN | FOG against the
+    reference replayed at the kernel's own per-layer step counts, taken by
+    `layer` passes: within test_gpu_env.FAST_BOUND, the project's measured bound
+    for this arithmetic on these rays, with at most ER.BOUNDARY_SHARE of the
+    frame left out."""
+    dev, left_out, pixels = rays_fast_deviation(renderer, name, bounces)
+    print(f"{name} bounces {bounces}: largest deviation {dev:.3e}, {left_out} of {pixels} rays "
+          f"left out; bound {FAST_BOUND:.3e}")
+    assert left_out <= ER.BOUNDARY_SHARE * pixels
+    assert dev <= FAST_BOUND
+
+
+# ---- 9. the C++ host program -----------------------------------------------------------------
+
+def test_cpp_host_program_projection_option(renderer, tmp_path):
+    exe = ROOT / "sdf3d_amd" / "bin" / "sdf_main"
+    assert exe.exists(), "build() must produce sdf3d_amd/bin/sdf_main"
+    tail = ["--sky", "--fog", "1,4", "--reflect", "2", str(W), str(H), "2"]
+    plain, pin, pano = (tmp_path / n for n in ("plain.ppm", "pinhole.ppm", "equirect.ppm"))
+    for out, opt in ((plain, []), (pin, ["--projection", "pinhole"])):
+        r = subprocess.run([str(exe), *opt, *tail, str(out), "csg8"], capture_output=True, text=True,
+                           timeout=120)
+        assert r.returncode == 0, r.stderr
+    assert read_ppm(plain).shape == (H, W, 3)
+    assert plain.read_bytes() == pin.read_bytes()
+    assert len(np.unique(read_ppm(plain).reshape(-1, 3), axis=0)) > 50
+    # a panorama under the sky without its sun: the top row looks at the zenith
+    r = subprocess.run([str(exe), "--projection", "equirect", "--sky", "--no-sun", str(W), str(H), "2",
+                        str(pano), "csg8"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    img = read_ppm(pano)
+    assert img.shape == (H, W, 3)
+    zenith = quantize(np.array([[[*scenes.SKY_ZENITH, 1.0]]], dtype=f32), U8)[0, 0, :3].astype(int)
+    assert np.abs(img[0].astype(int) - zenith).max() <= 1, (img[0], zenith)
+    assert r.stdout.count("frame ") == 2
