@@ -7,6 +7,7 @@
 //
 //   sdf_main [--palette] [--reflect B[,strength]] [--sky [--no-sun]] [--fog START,END[,r,g,b]]
 //            [--pick X,Y] [--projection pinhole|equirect]
+//            [--mesh FILE.obj --grid x0,y0,z0,x1,y1,z1,N]
 //            [width height frames out.ppm scene [samples [lights]]]
 //     scene: ref | csg8 | bulb; samples: 1 (default), 2 or 4 sub-samples per
 //     axis, resolved in the render kernel (single-GPU path only: the frame
@@ -41,6 +42,11 @@
 //     exact precision.  equirect: a full panorama from the camera's place,
 //     longitude across and latitude up, its directions built on the host and
 //     normalised by the kernel
+//     --mesh FILE.obj --grid x0,y0,z0,x1,y1,z1,N (anywhere on the line): after
+//     the last frame, the scene's surface inside the box from (x0,y0,z0) to
+//     (x1,y1,z1), N cells per axis, as a triangle mesh with normals in a
+//     Wavefront OBJ file (sdf::extract_mesh: sdf_mesh_count and sdf_mesh_emit;
+//     single-GPU path only)
 //
 // Multi-GPU: launched once per GPU by any launcher that sets RANK,
 // WORLD_SIZE and LOCAL_RANK (e.g. `torchrun --nproc-per-node 8 --no-python
@@ -211,7 +217,9 @@ int main(int argc, char** argv) {
   // positional arguments
   bool use_palette = false, use_reflect = false, use_env = false, use_pick = false;
   bool no_sun = false;
-  std::string projection;
+  std::string projection, mesh_path;
+  double box[6] = {0, 0, 0, 0, 0, 0};
+  int mesh_n = 0;
   int pick_x = 0, pick_y = 0;
   sdf_reflect reflect = {0, 1.0f, -1, 0};
   sdf_environment environment = sdf::sky(0);
@@ -240,6 +248,20 @@ int main(int argc, char** argv) {
                    std::sscanf(argv[++i], "%d,%d%c", &pick_x, &pick_y, &tail) == 2;
         if (!use_pick) {
           std::fprintf(stderr, "sdf_main: --pick X,Y\n");
+          return 1;
+        }
+      } else if (std::string(argv[i]) == "--mesh") {
+        mesh_path = i + 1 < argc ? argv[++i] : "";
+        if (mesh_path.empty()) {
+          std::fprintf(stderr, "sdf_main: --mesh FILE.obj\n");
+          return 1;
+        }
+      } else if (std::string(argv[i]) == "--grid") {
+        char tail = 0;
+        if (!(i + 1 < argc && std::sscanf(argv[++i], "%lf,%lf,%lf,%lf,%lf,%lf,%d%c", &box[0], &box[1],
+                                          &box[2], &box[3], &box[4], &box[5], &mesh_n, &tail) == 7 &&
+              mesh_n >= 1)) {
+          std::fprintf(stderr, "sdf_main: --grid x0,y0,z0,x1,y1,z1,N\n");
           return 1;
         }
       } else if (std::string(argv[i]) == "--projection") {
@@ -279,6 +301,10 @@ int main(int argc, char** argv) {
       }
     }
     argc = n;
+    if (mesh_path.empty() != (mesh_n == 0)) {
+      std::fprintf(stderr, "sdf_main: --mesh FILE.obj needs --grid x0,y0,z0,x1,y1,z1,N and vice versa\n");
+      return 1;
+    }
     if (no_sun) environment.flags &= ~SDF_ENV_SUN;
   }
   const int W = argc > 1 ? std::atoi(argv[1]) : 800;   // main.cpp:4 SX
@@ -394,6 +420,14 @@ int main(int argc, char** argv) {
       const sdf::Hit h = sdf::pick(q, pick_x, pick_y, stream);
       std::printf("pick %d,%d: %.9g %d %d %.9g %.9g %.9g\n", pick_x, pick_y, h.t, h.steps, h.prim,
                   h.normal[0], h.normal[1], h.normal[2]);
+    }
+    if (!mesh_path.empty()) {
+      const double lo[3] = {box[0], box[1], box[2]}, hi[3] = {box[3], box[4], box[5]};
+      const sdf::Mesh m = sdf::extract_mesh(f, sdf::box_grid(lo, hi, mesh_n), true, false, stream);
+      sdf::write_obj(mesh_path, m);
+      std::printf("mesh: %lld vertices, %lld triangles, %lld of %lld bricks evaluated; wrote %s\n",
+                  (long long)m.counts[0], (long long)m.counts[1], (long long)m.counts[2],
+                  (long long)m.counts[3], mesh_path.c_str());
     }
     (void)hipEventDestroy(t0);
     (void)hipEventDestroy(t1);

@@ -496,6 +496,104 @@ inline void camera_rays(const Frame& f, float* origins, float* dirs,
   check(sdf_camera_rays(&f.camera, &f.params, origins, dirs, stream), "sdf_camera_rays");
 }
 
+// ---- isosurface meshes (sdf_abi.h "Meshes") -----------------------------------
+// The level set f(p) = grid.iso of the frame's scene inside `grid` as an
+// indexed triangle mesh on the host: sdf_mesh_count, buffers sized from its
+// counts, sdf_mesh_emit, and the copies back.  Blocking.  `normals`: one normal
+// per vertex (sdf_sample's); `prims`: the primitive that owns each vertex.
+struct Mesh {
+  std::vector<float> verts;     // 3 per vertex
+  std::vector<int32_t> tris;    // 3 vertex numbers per triangle
+  std::vector<float> normals;   // 3 per vertex, or empty
+  std::vector<int32_t> prims;   // 1 per vertex, or empty
+  int64_t counts[4];            // vertices, triangles, bricks evaluated, bricks in all
+};
+inline Mesh extract_mesh(const Frame& f, const sdf_grid& grid, bool normals = false,
+                         bool prims = false, hipStream_t stream = nullptr) {
+  check_abi();
+  check(sdf_validate_mesh(&f.scene, &f.params, &grid), "sdf_validate_mesh");
+  const int64_t bytes = sdf_mesh_workspace_bytes(&grid);
+  if (bytes < 0) check(static_cast<int>(bytes), "sdf_mesh_workspace_bytes");
+  Mesh m{};
+  char *ws = nullptr, *buf = nullptr;
+  int64_t* counts = nullptr;
+  int rc = SDF_OK;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&ws), size_t(bytes));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&counts), 32);
+  if (e == hipSuccess) {
+    rc = sdf_mesh_count(&f.scene, &f.params, &grid, ws, bytes, counts, stream);
+    if (rc == SDF_OK) e = hipMemcpyAsync(m.counts, counts, 32, hipMemcpyDeviceToHost, stream);
+    if (rc == SDF_OK && e == hipSuccess) e = hipStreamSynchronize(stream);
+  }
+  if (rc == SDF_OK && e == hipSuccess && m.counts[0] > 0) {
+    const size_t nv = size_t(m.counts[0]), nt = size_t(m.counts[1]);
+    // verts | tris | normals | prims, every part a multiple of 4 bytes
+    const size_t ov = 0, ot = ov + nv * 12, on = ot + nt * 12, op = on + (normals ? nv * 12 : 0),
+                 end = op + (prims ? nv * 4 : 0);
+    e = hipMalloc(reinterpret_cast<void**>(&buf), end);
+    if (e == hipSuccess) {
+      sdf_mesh_out out{};
+      out.verts = reinterpret_cast<float*>(buf + ov);
+      out.max_verts = m.counts[0];
+      out.tris = nt ? reinterpret_cast<int32_t*>(buf + ot) : nullptr;
+      out.max_tris = m.counts[1];
+      out.normal = normals ? reinterpret_cast<float*>(buf + on) : nullptr;
+      out.prim = prims ? reinterpret_cast<int32_t*>(buf + op) : nullptr;
+      rc = sdf_mesh_emit(&f.scene, &f.params, &grid, ws, bytes, &out, stream);
+      if (rc == SDF_OK) e = hipStreamSynchronize(stream);
+      const hipMemcpyKind k = hipMemcpyDeviceToHost;
+      if (rc == SDF_OK && e == hipSuccess) {
+        m.verts.resize(nv * 3);
+        m.tris.resize(nt * 3);
+        if (normals) m.normals.resize(nv * 3);
+        if (prims) m.prims.resize(nv);
+        e = hipMemcpy(m.verts.data(), buf + ov, nv * 12, k);
+        if (e == hipSuccess && nt) e = hipMemcpy(m.tris.data(), buf + ot, nt * 12, k);
+        if (e == hipSuccess && normals) e = hipMemcpy(m.normals.data(), buf + on, nv * 12, k);
+        if (e == hipSuccess && prims) e = hipMemcpy(m.prims.data(), buf + op, nv * 4, k);
+      }
+    }
+  }
+  (void)hipFree(buf);
+  (void)hipFree(counts);
+  (void)hipFree(ws);
+  check(rc, "sdf_mesh_count / sdf_mesh_emit");
+  check_hip(e, "extract_mesh");
+  return m;
+}
+// The grid of n cells per axis over the box [lo, hi].
+inline sdf_grid box_grid(const double (&lo)[3], const double (&hi)[3], int n, float iso = 0.0f) {
+  sdf_grid g{};
+  for (int c = 0; c < 3; ++c) {
+    g.origin[c] = static_cast<float>(lo[c]);
+    g.cell[c] = static_cast<float>((hi[c] - lo[c]) / n);
+    g.n[c] = n;
+  }
+  g.iso = iso;
+  return g;
+}
+// A Wavefront OBJ file of the mesh: 1-based indices, `vn` lines when the mesh
+// has normals (sdf3d_amd/meshio.py reads it back).
+inline void write_obj(const std::string& path, const Mesh& m) {
+  FILE* fp = std::fopen(path.c_str(), "w");
+  if (!fp) throw Error(SDF_E_INVALID_ARG, "cannot open " + path);
+  const size_t nv = m.verts.size() / 3, nt = m.tris.size() / 3;
+  const bool vn = m.normals.size() == m.verts.size() && nv > 0;
+  std::fprintf(fp, "# %zu vertices, %zu triangles\n", nv, nt);
+  for (size_t i = 0; i < nv; ++i)
+    std::fprintf(fp, "v %.9g %.9g %.9g\n", m.verts[3 * i], m.verts[3 * i + 1], m.verts[3 * i + 2]);
+  if (vn)
+    for (size_t i = 0; i < nv; ++i)
+      std::fprintf(fp, "vn %.9g %.9g %.9g\n", m.normals[3 * i], m.normals[3 * i + 1],
+                   m.normals[3 * i + 2]);
+  for (size_t i = 0; i < nt; ++i) {
+    const int a = m.tris[3 * i] + 1, b = m.tris[3 * i + 1] + 1, c = m.tris[3 * i + 2] + 1;
+    if (vn) std::fprintf(fp, "f %d//%d %d//%d %d//%d\n", a, a, b, b, c, c);
+    else std::fprintf(fp, "f %d %d %d\n", a, b, c);
+  }
+  std::fclose(fp);
+}
+
 // ---- multi-device frames (sdf_comm_* / sdf_driver_*) ------------------------
 
 // One RCCL communicator over `world` processes (one per GPU), created from a

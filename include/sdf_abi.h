@@ -82,6 +82,10 @@ extern "C" {
                                    likewise;
                                 still 12: sdf_validate_env and sdf_render_env
                                    (sdf_environment, SDF_ENV_*), additions
+                                   likewise;
+                                still 12: sdf_validate_mesh, sdf_mesh_count,
+                                   sdf_mesh_emit, sdf_mesh_workspace_bytes
+                                   (sdf_grid, sdf_mesh_out), additions
                                    likewise */
 
 /* ---- status codes ------------------------------------------------------ */
@@ -233,6 +237,23 @@ typedef struct {
   int32_t flags;          /* SDF_RAYS_* */
   int32_t reserved;
 } sdf_rays;               /* 32 bytes */
+
+/* Isosurface meshes (sdf_mesh_count, sdf_mesh_emit; "Meshes" below) */
+#define SDF_MESH_DENSE 0x1          /* evaluate every brick: no distance-bound skipping (cross-check) */
+typedef struct {
+  float origin[3];                  /* lattice point (0,0,0) */
+  float cell[3];                    /* cell size per axis, finite, > 0 */
+  int32_t n[3];                     /* cells per axis, >= 1; (n0+1)(n1+1)(n2+1) <= 2^30 */
+  float iso;                        /* the level set extracted: f(p) = iso (0: the surface; > 0: an offset shell) */
+  int32_t flags;                    /* SDF_MESH_* */
+  int32_t reserved;                 /* 0 */
+} sdf_grid;                         /* 48 bytes */
+typedef struct {
+  float*   verts;   int64_t max_verts;  /* device, 3 floats per vertex */
+  int32_t* tris;    int64_t max_tris;   /* device, 3 vertex indices per triangle */
+  float*   normal;                      /* device, optional, 3 per vertex */
+  int32_t* prim;                        /* device, optional, 1 per vertex */
+} sdf_mesh_out;                         /* 48 bytes */
 
 /* Render flags */
 #define SDF_FLAG_SHADOW    0x1  /* soft shadow march (voxel_fragment.frag:205) */
@@ -671,6 +692,83 @@ typedef struct {
  *     devices, TILES and SHADE32F output, per-ray distance limits, sorting or
  *     compacting rays and a NaN-marching path for shaded rays are not offered. */
 
+/* Meshes (sdf_mesh_count, sdf_mesh_emit: the level set f(p) = iso of the scene
+ * inside a regular grid, as an indexed triangle mesh -- export, printing,
+ * collision, other tools.  Surface nets: one vertex per cell the surface passes
+ * through, one quad per lattice edge it crosses.  Every output is defined from
+ * what sdf_sample returns, so exact precision can be checked bit for bit
+ * (tests/mesh_ref.py states it in NumPy over the CPU oracle).  Axes c = 0, 1, 2;
+ * for an axis a, u = (a + 1) mod 3 and v = (a + 2) mod 3.  Exact precision rounds
+ * every operation once and fuses nothing, divisions are IEEE; fast precision
+ * may contract and use the hardware reciprocal.  Non-finite values propagate as
+ * the arithmetic says:
+ *   - two calls: sdf_mesh_count classifies the grid, fills `workspace` and
+ *     writes counts[0] vertices, counts[1] triangles, counts[2] bricks whose
+ *     lattice was evaluated, counts[3] bricks in all (device, 4 int64).  The
+ *     caller reads them, sizes the buffers, and hands sdf_mesh_emit the same
+ *     scene, params, grid and untouched workspace, ordered after the count;
+ *     emit writes the mesh.  Every store of emit is guarded: vertex v (its
+ *     normal, its prim) is written only if v < max_verts, triangle t only if t <
+ *     max_tris, so an undersized buffer or a stale workspace cannot make emit
+ *     write outside the caller's buffers -- it gets a prefix of the mesh.
+ *   - workspace: device memory, 16-byte aligned, O(bricks) not O(cells).  With
+ *     B_c = ceil(n[c] / 8), B = B_0 B_1 B_2 bricks and C = ceil(B / 1024):
+ *     sdf_mesh_workspace_bytes = 88 B + 24 C (per brick a 512-bit activity
+ *     mask, two 32-bit counts and two 64-bit offsets; per 1024 bricks three
+ *     64-bit sums of the offset scan).  512^3 cells: 23 MB.
+ *   - lattice: point (i0, i1, i2), 0 <= i_c <= n[c], lies at p.c = RN(origin[c] +
+ *     RN((float)i_c cell[c])); w = RN(f(p) - iso), f bit for bit what sdf_sample
+ *     returns for p with this scene, precision and dispatch.  A point is inside
+ *     iff w < 0: a NaN or a zero is outside.
+ *   - cells: cell (i0, i1, i2), 0 <= i_c < n[c], is active when some corner is
+ *     inside and some corner is not.
+ *   - edges: edge e = 4a + s + 2t of a cell (s, t in {0, 1}) runs along a from
+ *     corner A (offset 0 along a, s along u, t along v) to B (offset 1 along a);
+ *     it crosses when inside(A) != inside(B); its parameter is tau = RN(w_A /
+ *     RN(w_A - w_B)), its local point q has q_a = tau, q_u = s, q_v = t.
+ *   - vertex of an active cell: S_c = the fp32 sum of q_c over the crossing edges
+ *     in increasing e, starting at 0; m their number; g_c = RN(S_c / (float)m);
+ *     vertex.c = RN(p_c(corner 000) + RN(g_c cell[c])).
+ *   - order: cells are grouped into bricks of 8 x 8 x 8, brick (b2 B_1 + b1) B_0 +
+ *     b0, local index (l2 8 + l1) 8 + l0; vertices are numbered over the active
+ *     cells in increasing (brick, local) order.
+ *   - triangles: active cells in that same order; for a = 0, 1, 2 the cell's edge
+ *     e = 4a (from corner 000 along a) emits when it crosses and i_u >= 1 and i_v
+ *     >= 1: one quad over the four cells that share it, K0 = cell - e_u - e_v, K1
+ *     = cell - e_v, K2 = cell, K3 = cell - e_u, reversed to (K3, K2, K1, K0) when
+ *     corner 000 is not inside, written as (q0, q1, q2), (q0, q2, q3) in vertex
+ *     numbers.  Normals point out of the inside.  Edges on the grid's border
+ *     emit nothing: a surface that leaves the grid ends in an open rim.
+ *   - normal (optional): what sdf_sample gives at the vertex position
+ *     (normal_mode, normal_eps); prim (optional): the owner fold of "Queries"
+ *     at the vertex, 0 for a Mandelbulb.
+ *   - skipping: a brick whose centre value proves that no lattice point of it
+ *     can change sign (|f(centre) - iso| above the scene's Lipschitz constant
+ *     times half the brick's diagonal, plus a margin for fp32 rounding:
+ *     sdf3d_amd/csrc/mesh_kernel.inc) is not evaluated.  The mesh is bit for bit
+ *     the same with and without it; SDF_MESH_DENSE evaluates every brick.  A
+ *     Mandelbulb, and a grid or scene beyond the proof's range (coordinates or
+ *     parameters above 2^20, n[c] of 2^24 and more), always run dense.
+ *   - params: normal_eps, normal_mode, precision and dispatch are used,
+ *     validated as sdf_validate_query does.  Dispatch follows the queries': a
+ *     built-in variant when the scene matches one, under SDF_DISPATCH_AUTO
+ *     run-time specialised mesh kernels for any other primitive list (two,
+ *     counted by sdf_jit_count; the generic kernel with SDF3D_JIT=0), GENERIC
+ *     and UNCULLED as there.
+ *   - SDF_E_INVALID_ARG, decided before any device call (sdf_validate_mesh is
+ *     that check of scene, params and grid): everything sdf_validate_query
+ *     rejects; grid, workspace or counts NULL; n[c] < 1 or more than 2^30
+ *     lattice points; a cell size that is not finite and > 0; origin, iso or the
+ *     far corner origin + n cell non-finite or beyond 1e15; unknown flags or a
+ *     nonzero reserved; a workspace that is misaligned or smaller than
+ *     sdf_mesh_workspace_bytes; emit: out NULL, verts or tris NULL with a
+ *     positive capacity, a negative capacity.  Capacities of 0 write nothing.
+ *   - asynchronous on `stream`.  SDF_ABI_VERSION stays 12: detect the entry
+ *     points by the symbol.
+ *   - marching cubes tables, sharp-feature (QEF) placement, mesh
+ *     simplification, adaptive grids, several devices and vertex colours are
+ *     not offered. */
+
 /* Framebuffer element formats (4 channels R,G,B,A per pixel).
  *   RGBA32F  the shader's float fragment_color (voxel_fragment.frag:12,210).
  *   RGBA16F  IEEE half, round to nearest even.
@@ -954,6 +1052,19 @@ int sdf_render_rays(const sdf_scene* scene, const sdf_light* lights, int32_t nli
                     void* stream);
 int sdf_camera_rays(const sdf_camera* camera, const sdf_params* params, float* origins,
                     float* dirs, void* stream);
+
+/* Isosurface meshes ("Meshes" above).  Additions: SDF_ABI_VERSION stays 12,
+ * detect them by the symbol.  sdf_validate_mesh is the host-only check both
+ * calls make first (no device call); sdf_mesh_workspace_bytes the size of the
+ * workspace of `grid`, or a negative SDF_E* code. */
+int sdf_validate_mesh(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid);
+int64_t sdf_mesh_workspace_bytes(const sdf_grid* grid);
+int sdf_mesh_count(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
+                   void* workspace, int64_t workspace_bytes, int64_t* counts /* device, 4 */,
+                   void* stream);
+int sdf_mesh_emit(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
+                  void* workspace, int64_t workspace_bytes, const sdf_mesh_out* out,
+                  void* stream);
 
 /* Scatter `nparts` packed row-block buffers (part r = rank r's output for
  * tiling {block_rows, r, nparts}), laid out back to back in `parts` with a

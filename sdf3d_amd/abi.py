@@ -21,6 +21,7 @@ ENV_SKY = 0x1         # SDF_ENV_SKY: a missed layer's colour is the sky along it
 ENV_SUN = 0x2         # SDF_ENV_SUN: with ENV_SKY, a glow around sun_dir
 ENV_FOG = 0x4         # SDF_ENV_FOG: linear distance fog on every layer that is not sky
 RAYS_UNIT = 0x1       # SDF_RAYS_UNIT: sdf_render_rays uses dirs as given (unit vectors)
+MESH_DENSE = 0x1      # SDF_MESH_DENSE: sdf_mesh_count evaluates every brick (no skipping)
 
 # status codes
 SDF_OK = 0
@@ -114,6 +115,18 @@ class sdf_rays(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class sdf_grid(C.Structure):
+    """The lattice of sdf_mesh_count / sdf_mesh_emit: n cells of `cell` from `origin`."""
+    _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float * 3), ("n", C.c_int32 * 3),
+                ("iso", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class sdf_mesh_out(C.Structure):
+    """Outputs of sdf_mesh_emit: device pointers with capacities; normal and prim may be NULL."""
+    _fields_ = [("verts", C.c_void_p), ("max_verts", C.c_int64), ("tris", C.c_void_p),
+                ("max_tris", C.c_int64), ("normal", C.c_void_p), ("prim", C.c_void_p)]
+
+
 class sdf_params(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("max_steps", C.c_int32),
                 ("max_dist", C.c_float), ("eps", C.c_float), ("shadow_k", C.c_float),
@@ -142,7 +155,7 @@ STRUCT_SIZES = {
     "sdf_primitive": 64, "sdf_scene": 8 + 64 * SDF_MAX_PRIMS + 32, "sdf_camera": 88,
     "sdf_light": 32, "sdf_material": 40, "sdf_params": 80, "sdf_tiling": 24,
     "sdf_driver_config": 36, "sdf_reflect": 16, "sdf_environment": 96, "sdf_hits": 32,
-    "sdf_rays": 32,
+    "sdf_rays": 32, "sdf_grid": 48, "sdf_mesh_out": 48,
 }
 MAX_QUERY = 1 << 30   # rays or points of one sdf_trace / sdf_sample call
 
@@ -209,6 +222,12 @@ SIGNATURES = {
                                    C.c_void_p]),
     "sdf_sample": (C.c_int, [_P(sdf_scene), _P(sdf_params), C.c_void_p, C.c_int64, C.c_void_p,
                              C.c_void_p, C.c_void_p]),
+    "sdf_validate_mesh": (C.c_int, [_P(sdf_scene), _P(sdf_params), _P(sdf_grid)]),
+    "sdf_mesh_workspace_bytes": (C.c_int64, [_P(sdf_grid)]),
+    "sdf_mesh_count": (C.c_int, [_P(sdf_scene), _P(sdf_params), _P(sdf_grid), C.c_void_p,
+                                 C.c_int64, C.c_void_p, C.c_void_p]),
+    "sdf_mesh_emit": (C.c_int, [_P(sdf_scene), _P(sdf_params), _P(sdf_grid), C.c_void_p,
+                                C.c_int64, _P(sdf_mesh_out), C.c_void_p]),
     "sdf_validate_rays": (C.c_int, [_P(sdf_scene), _P(sdf_light), C.c_int32, C.c_int32,
                                     _P(sdf_material), C.c_int32, _P(sdf_reflect),
                                     _P(sdf_environment), _P(sdf_params), _P(sdf_rays)]),

@@ -191,6 +191,50 @@ struct RaysArgs {
   int32_t flags;  // SDF_RAYS_*
   int32_t reserved;
 };
+// ---- isosurface meshes (sdf_mesh_count, sdf_mesh_emit) -------------------------
+// The workspace of a mesh extraction (sdf_abi.h "Meshes"), O(bricks): per
+// brick of 8 x 8 x 8 cells its 512-bit activity mask (word l2: the 8 x 8 slice
+// l2, bit l1 * 8 + l0), two counts and two offsets, then the scan's
+// per-chunk sums.  sdf_mesh_workspace_bytes() = end.
+constexpr int kMeshScanChunk = 1024;          // bricks per workgroup of the offset scan
+constexpr uint32_t kMeshEvaluated = 1u << 31; // MeshBrick::nv: the brick's lattice was evaluated
+struct MeshBrick {
+  uint32_t nv;   // vertices (active cells), <= 512; | kMeshEvaluated
+  uint32_t nt;   // triangles, <= 3072
+};
+struct MeshOffset {
+  long long v, t;   // vertices / triangles of the bricks before this one
+};
+struct MeshLayout {
+  size_t mask, brick, offset, sums, end;
+  __host__ __device__ explicit MeshLayout(long long nbricks) {
+    const size_t n = (size_t)nbricks;
+    const size_t chunks = (n + kMeshScanChunk - 1) / kMeshScanChunk;
+    mask = 0;
+    brick = mask + 64 * n;
+    offset = brick + sizeof(MeshBrick) * n;
+    sums = offset + sizeof(MeshOffset) * n;
+    end = sums + 3 * sizeof(long long) * chunks;
+  }
+};
+// The argument block of the mesh kernels (mesh_kernel.inc mesh_count /
+// mesh_emit), their own: RenderArgs is full.  `a` carries the scene and the
+// normal's parameters; its camera, light and outputs are unused.
+struct MeshArgs {
+  KernelArgs a;   // first: the scene evaluators read it at the start of the segment
+  float origin[3], cell[3];
+  int32_t n[3];        // cells per axis
+  int32_t nb[3];       // bricks per axis, ceil(n / 8)
+  float iso;
+  float skip;          // a brick is skipped when |f(centre) - iso| > skip (+INF: never)
+  long long nbricks;
+  unsigned char* ws;   // MeshLayout(nbricks)
+  float* verts;        // emit: 3 per vertex, vertex v stored iff v < max_verts
+  int32_t* tris;       // emit: 3 per triangle, triangle t stored iff t < max_tris
+  float* normal;       // emit, optional: 3 per vertex
+  int32_t* prim;       // emit, optional: 1 per vertex
+  long long max_verts, max_tris;
+};
 
 // Waves (8x8 tiles side by side) per render workgroup (render_kernel.inc
 // render / render_tiles / render_ssaa; the built-in and the run-time
@@ -239,6 +283,7 @@ static_assert(sizeof(KernelArgs) <= 4096, "KernelArgs exceeds the 4 KiB kernel-a
 static_assert(sizeof(RenderArgs) <= 4096, "RenderArgs exceeds the 4 KiB kernel-argument limit");
 static_assert(sizeof(QueryArgs) <= 4096, "QueryArgs exceeds the 4 KiB kernel-argument limit");
 static_assert(sizeof(RaysArgs) <= 4096, "RaysArgs exceeds the 4 KiB kernel-argument limit");
+static_assert(sizeof(MeshArgs) <= 4096, "MeshArgs exceeds the 4 KiB kernel-argument limit");
 // Tiles a wave takes per queue request, queues per launch (workgroup b uses
 // queue b % queues, i.e. one per XCD), and the queues' spacing in uint32s:
 // requests on one address serialise at the memory-side atomic unit, so the
@@ -281,6 +326,15 @@ int launch_rays_exact_bulb(const RaysArgs& q, void* stream);
 int launch_rays_fast_bulb(const RaysArgs& q, void* stream);
 int launch_camera_rays_exact(const RaysArgs& q, void* stream);
 int launch_camera_rays_fast(const RaysArgs& q, void* stream);
+// the mesh kernels of each precision (emit = 0: mesh_count, 1: mesh_emit), one
+// brick per workgroup; kVariantBulb is forwarded to the Mandelbulb units
+int launch_mesh_exact(const MeshArgs& m, int variant, int emit, void* stream);
+int launch_mesh_fast(const MeshArgs& m, int variant, int emit, void* stream);
+int launch_mesh_exact_bulb(const MeshArgs& m, int emit, void* stream);
+int launch_mesh_fast_bulb(const MeshArgs& m, int emit, void* stream);
+// the scan over the bricks' counts (mesh.hip): offsets per brick into the
+// workspace, the totals into counts[0..3] (device)
+int launch_mesh_scan(unsigned char* ws, long long nbricks, long long* counts, void* stream);
 int launch_deinterleave(const void* parts, int nparts, int part_stride_rows, int row_bytes,
                         int height, int block_rows, void* frame, void* stream);
 int launch_heatmap(const int32_t* steps, int count, int which, int max_steps, int format,
@@ -355,6 +409,8 @@ int launch_render_jit(const RenderArgs& a, const int* sig, int n, bool exact, vo
 int launch_query_jit(const QueryArgs& q, const int* sig, int n, bool exact, void* stream);
 // the same for sdf_render_rays (steps and env enter the cache key); -1 = none
 int launch_rays_jit(const RaysArgs& q, const int* sig, int n, bool exact, void* stream);
+// the same for a mesh kernel (count or emit enters the cache key); -1 = none
+int launch_mesh_jit(const MeshArgs& m, const int* sig, int n, bool exact, int emit, void* stream);
 int jit_compiled_count();
 
 // ---- compile-time scene variants ------------------------------------------

@@ -92,6 +92,8 @@
 #define SDF_LAUNCH_RAYS launch_rays_exact
 #define SDF_LAUNCH_RAYS_BULB launch_rays_exact_bulb
 #define SDF_LAUNCH_CAMERA_RAYS launch_camera_rays_exact
+#define SDF_LAUNCH_MESH launch_mesh_exact
+#define SDF_LAUNCH_MESH_BULB launch_mesh_exact_bulb
 #else
 #define SDF_NS fast_impl
 #define SDF_LAUNCH launch_render_fast
@@ -103,6 +105,8 @@
 #define SDF_LAUNCH_RAYS launch_rays_fast
 #define SDF_LAUNCH_RAYS_BULB launch_rays_fast_bulb
 #define SDF_LAUNCH_CAMERA_RAYS launch_camera_rays_fast
+#define SDF_LAUNCH_MESH launch_mesh_fast
+#define SDF_LAUNCH_MESH_BULB launch_mesh_fast_bulb
 #endif
 
 namespace sdf {
@@ -3100,6 +3104,9 @@ void query(QueryArgs args) {
   query_body<Scene, KIND>();
 }
 
+// ---- isosurface meshes (sdf_abi.h "Meshes": sdf_mesh_count, sdf_mesh_emit) -----
+#include "mesh_kernel.inc"
+
 // ---- caller-supplied rays (sdf_abi.h "Rays": sdf_render_rays, sdf_camera_rays) --
 // The path of shade_pixel_reflect (ENV: shade_pixel_env) whose layer 0 is read
 // from memory instead of being formed from (x, y): every layer, the first
@@ -3370,6 +3377,39 @@ int SDF_LAUNCH_QUERY(const QueryArgs& q, int variant, void* stream) {
 #undef SDF_LAUNCH_FIXED
     default:
       return launch_query_scene<SDF_NS::GenericScene>(q, s);
+  }
+}
+#endif
+
+// one launch of scene kernel S for a mesh extraction: one wave per brick,
+// mesh_count or mesh_emit.  The host (sdf_abi.cpp mesh_launch) has bounded the
+// grid, so the bricks fit the launch.
+template <class S>
+static int launch_mesh_scene(const MeshArgs& m, int emit, hipStream_t s) {
+  if (m.nbricks <= 0 || m.nbricks > 0x7fffffffll || !m.ws) return (int)hipErrorInvalidValue;
+  const dim3 block(64), grid((unsigned)m.nbricks);
+  (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
+  if (emit) hipLaunchKernelGGL((SDF_NS::mesh_emit<S>), grid, block, 0, s, m);
+  else hipLaunchKernelGGL((SDF_NS::mesh_count<S>), grid, block, 0, s, m);
+  return (int)hipGetLastError();
+}
+
+#if SDF_TU_BULB
+int SDF_LAUNCH_MESH_BULB(const MeshArgs& m, int emit, void* stream) {
+  return launch_mesh_scene<SDF_NS::BulbScene>(m, emit, (hipStream_t)stream);
+}
+#else
+int SDF_LAUNCH_MESH(const MeshArgs& m, int variant, int emit, void* stream) {
+  if (variant == kVariantBulb) return SDF_LAUNCH_MESH_BULB(m, emit, stream);   // its own unit
+  hipStream_t s = (hipStream_t)stream;
+  switch (variant) {
+#define SDF_LAUNCH_FIXED(id, ...) \
+  case id:                        \
+    return launch_mesh_scene<SDF_NS::FixedScene<__VA_ARGS__>>(m, emit, s);
+    SDF_FIXED_VARIANTS(SDF_LAUNCH_FIXED)
+#undef SDF_LAUNCH_FIXED
+    default:
+      return launch_mesh_scene<SDF_NS::GenericScene>(m, emit, s);
   }
 }
 #endif

@@ -1304,6 +1304,157 @@ int sdf_sample(const sdf_scene* scene, const sdf_params* params, const float* po
                       normal, nullptr, stream);
 }
 
+// ---- isosurface meshes (sdf_abi.h "Meshes") -----------------------------------
+static_assert(sizeof(sdf_grid) == 48, "sdf_grid layout");
+static_assert(sizeof(sdf_mesh_out) == 48, "sdf_mesh_out layout");
+namespace {
+constexpr int64_t kMaxLattice = int64_t(1) << 30;
+
+// The grid's own checks (no scene): sizes, finiteness, the 1e15 range, flags.
+// On success *nbricks is the number of 8 x 8 x 8 bricks.
+int validate_grid(const sdf_grid* g, int64_t* nbricks) {
+  if (!g) return SDF_E_INVALID_ARG;
+  if ((g->flags & ~SDF_MESH_DENSE) || g->reserved != 0) return SDF_E_INVALID_ARG;
+  if (!(std::fabs(g->iso) <= kMaxCoord)) return SDF_E_INVALID_ARG;
+  int64_t points = 1, bricks = 1;
+  for (int c = 0; c < 3; ++c) {
+    if (g->n[c] < 1) return SDF_E_INVALID_ARG;
+    points *= int64_t(g->n[c]) + 1;   // each factor <= 2^31, checked after each product
+    if (points > kMaxLattice) return SDF_E_INVALID_ARG;
+    bricks *= (int64_t(g->n[c]) + 7) / 8;
+    if (!(g->cell[c] > 0.0f) || !std::isfinite(g->cell[c])) return SDF_E_INVALID_ARG;
+    if (!(std::fabs(g->origin[c]) <= kMaxCoord)) return SDF_E_INVALID_ARG;
+    const double far = double(g->origin[c]) + double(g->n[c]) * double(g->cell[c]);
+    if (!(std::fabs(far) <= kMaxCoord)) return SDF_E_INVALID_ARG;
+  }
+  if (nbricks) *nbricks = bricks;
+  return SDF_OK;
+}
+
+int validate_mesh(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
+                  int64_t* nbricks) {
+  if (!scene || !params || !grid) return SDF_E_INVALID_ARG;
+  const int rc = validate_query(scene, nullptr, query_params(*params, false));
+  if (rc != SDF_OK) return rc;
+  return validate_grid(grid, nbricks);
+}
+
+// MeshArgs::skip: L R + 2^-13 V, rounded up, or +INF where the proof
+// (mesh_kernel.inc) does not hold and every brick is evaluated.
+float mesh_skip_bound(const sdf_scene& s, const sdf_grid& g) {
+  if ((g.flags & SDF_MESH_DENSE) || s.kind != SDF_SCENE_PRIMITIVES) return INFINITY;
+  double M = 0, S = 1, L = 1, diag2 = 0;
+  for (int c = 0; c < 3; ++c) {
+    if (int64_t(g.n[c]) + 8 >= (int64_t(1) << 24)) return INFINITY;
+    const double edge = 8.0 * g.cell[c];
+    const double far = double(g.origin[c]) + double(g.n[c]) * g.cell[c];
+    M = std::max(M, std::max(std::fabs(double(g.origin[c])), std::fabs(far)) + edge);
+    diag2 += edge * edge;
+  }
+  for (int i = 0; i < s.count; ++i) {
+    const sdf_primitive& pr = s.prims[i];
+    for (float v : pr.p) S = std::max(S, std::fabs(double(v)));
+    const bool smooth = pr.op == SDF_OP_SMOOTH_UNION || pr.op == SDF_OP_SMOOTH_SUBTRACT ||
+                        pr.op == SDF_OP_SMOOTH_INTERSECT;
+    if (smooth) S = std::max(S, double(pr.k));
+    if (pr.kind == SDF_PRIM_PLANE)
+      L = std::max(L, std::sqrt(double(pr.p[0]) * pr.p[0] + double(pr.p[1]) * pr.p[1] +
+                                double(pr.p[2]) * pr.p[2]));
+  }
+  if (!(M <= 0x1p20 && S <= 0x1p20)) return INFINITY;
+  const double V = 4.0 * (M + S) * S + std::fabs(double(g.iso));
+  const double bound = (L * 0.5 * std::sqrt(diag2) + 0x1p-13 * V) * (1.0 + 0x1p-40);
+  return std::nextafter(float(bound), INFINITY);
+}
+
+// One validated mesh call: the render's own plan (scene blocks, culling
+// bounds, dispatch) with the grid and the mesh buffers; the count is followed
+// by the scan that turns the bricks' counts into offsets and totals.
+int mesh_launch(bool emit, const sdf_scene* scene, const sdf_params* params, const sdf_grid* g,
+                int64_t nbricks, void* workspace, int64_t* counts, const sdf_mesh_out* out,
+                void* stream) {
+  const sdf_params q = query_params(*params, false);
+  sdf_camera c;
+  sdf_light l;
+  sdf_material mt;
+  sdf_defaults(nullptr, &c, &l, &mt, nullptr, 0, 0);
+  std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
+  int dummy = 0;   // the plan wants a framebuffer to name; a mesh has none
+  const int rc = sdf::make_render_plan(scene, &c, &l, &mt, &q, nullptr, &dummy, nullptr, plan.get());
+  if (rc != SDF_OK) return rc;
+  std::unique_ptr<sdf::MeshArgs> m(new sdf::MeshArgs());
+  m->a = plan->a;
+  m->a.rgba = nullptr;
+  m->a.steps = nullptr;
+  for (int i = 0; i < 3; ++i) {
+    m->origin[i] = g->origin[i];
+    m->cell[i] = g->cell[i];
+    m->n[i] = g->n[i];
+    m->nb[i] = (g->n[i] + 7) / 8;
+  }
+  m->iso = g->iso;
+  m->skip = mesh_skip_bound(*scene, *g);
+  m->nbricks = nbricks;
+  m->ws = static_cast<unsigned char*>(workspace);
+  if (emit) {
+    m->verts = out->verts;
+    m->tris = out->tris;
+    m->normal = out->normal;
+    m->prim = out->prim;
+    m->max_verts = out->max_verts;
+    m->max_tris = out->max_tris;
+  }
+  int err = -1;
+  if (plan->jit)
+    err = sdf::launch_mesh_jit(*m, plan->sig, plan->nsig, plan->exact, emit ? 1 : 0, stream);
+  if (err == -1)
+    err = plan->exact ? sdf::launch_mesh_exact(*m, plan->variant, emit ? 1 : 0, stream)
+                      : sdf::launch_mesh_fast(*m, plan->variant, emit ? 1 : 0, stream);
+  if (err == hipSuccess && !emit) err = sdf::launch_mesh_scan(m->ws, nbricks, (long long*)counts, stream);
+  return err == hipSuccess ? SDF_OK : SDF_E_HIP;
+}
+
+// the workspace a call was handed: present, aligned, large enough
+bool mesh_workspace_fits(const void* workspace, int64_t bytes, int64_t nbricks) {
+  return workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
+         bytes >= (int64_t)sdf::MeshLayout(nbricks).end;
+}
+}  // namespace
+
+int sdf_validate_mesh(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid) {
+  return validate_mesh(scene, params, grid, nullptr);
+}
+
+int64_t sdf_mesh_workspace_bytes(const sdf_grid* grid) {
+  int64_t nbricks = 0;
+  const int rc = validate_grid(grid, &nbricks);
+  if (rc != SDF_OK) return rc;
+  return (int64_t)sdf::MeshLayout(nbricks).end;
+}
+
+int sdf_mesh_count(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
+                   void* workspace, int64_t workspace_bytes, int64_t* counts, void* stream) {
+  int64_t nbricks = 0;
+  const int rc = validate_mesh(scene, params, grid, &nbricks);
+  if (rc != SDF_OK) return rc;
+  if (!counts || !mesh_workspace_fits(workspace, workspace_bytes, nbricks)) return SDF_E_INVALID_ARG;
+  return mesh_launch(false, scene, params, grid, nbricks, workspace, counts, nullptr, stream);
+}
+
+int sdf_mesh_emit(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
+                  void* workspace, int64_t workspace_bytes, const sdf_mesh_out* out,
+                  void* stream) {
+  int64_t nbricks = 0;
+  const int rc = validate_mesh(scene, params, grid, &nbricks);
+  if (rc != SDF_OK) return rc;
+  if (!out || !mesh_workspace_fits(workspace, workspace_bytes, nbricks)) return SDF_E_INVALID_ARG;
+  if (out->max_verts < 0 || out->max_tris < 0) return SDF_E_INVALID_ARG;
+  if ((out->max_verts > 0 && !out->verts) || (out->max_tris > 0 && !out->tris))
+    return SDF_E_INVALID_ARG;
+  if (out->max_verts == 0 && out->max_tris == 0) return SDF_OK;   // nothing may be written
+  return mesh_launch(true, scene, params, grid, nbricks, workspace, nullptr, out, stream);
+}
+
 // ---- caller-supplied rays (sdf_abi.h "Rays") ----------------------------------
 namespace {
 const sdf_reflect kNoBounce = {0, 1.0f, -1, 0};   // reflect NULL: bounces 0, the composite

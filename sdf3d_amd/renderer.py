@@ -102,6 +102,30 @@ class Hits(NamedTuple):
     prim: object
 
 
+class Mesh(NamedTuple):
+    """What ``Renderer.mesh`` returns: device tensors; `normal` and `prim` are
+    None when not asked for; `counts` is the host copy of sdf_mesh_count's four
+    numbers (vertices, triangles, bricks evaluated, bricks in all)."""
+    verts: object
+    tris: object
+    normal: object
+    prim: object
+    counts: tuple
+
+
+def grid(origin, cell, n, iso: float = 0.0, dense: bool = False) -> abi.sdf_grid:
+    """The sdf_grid of n cells of size `cell` from `origin`; a scalar `cell` or
+    `n` is used for all three axes."""
+    cell = (cell,) * 3 if isinstance(cell, (int, float)) else tuple(cell)
+    n = (n,) * 3 if isinstance(n, int) else tuple(n)
+    g = abi.sdf_grid()
+    for c in range(3):
+        g.origin[c], g.cell[c], g.n[c] = float(origin[c]), float(cell[c]), int(n[c])
+    g.iso = float(iso)
+    g.flags = abi.MESH_DENSE if dense else 0
+    return g
+
+
 class Renderer:
     """Renders frames on one HIP device through ``sdf_render``."""
 
@@ -393,6 +417,50 @@ class Renderer:
                                      self._stream(stream))
         abi.check(rc, "sdf_sample")
         return dist, nrm
+
+    # ---- isosurface meshes (sdf_abi.h "Meshes") -----------------------------
+    def mesh(self, frame: Frame, origin, cell, n, iso: float = 0.0, normal: bool = False,
+             prim: bool = False, dense: bool = False, stream=None) -> "Mesh":
+        """The level set ``f(p) = iso`` of ``frame.scene`` inside the grid of
+        `n` cells of size `cell` from `origin`, as an indexed triangle mesh
+        (sdf_mesh_count, then sdf_mesh_emit into buffers sized from its counts;
+        the host waits for the counts in between).  Returns ``Mesh(verts (nv, 3)
+        float32, tris (nt, 3) int32, normal (nv, 3) or None, prim (nv,) int32 or
+        None, counts)``.  `dense` evaluates every brick (SDF_MESH_DENSE); the
+        mesh is the same either way."""
+        torch = self.torch
+        g = grid(origin, cell, n, iso, dense)
+        nbytes = int(self.lib.sdf_mesh_workspace_bytes(C.byref(g)))
+        if nbytes < 0:
+            abi.check(nbytes, "sdf_mesh_workspace_bytes")
+        abi.check(self.lib.sdf_validate_mesh(C.byref(frame.scene), C.byref(frame.params),
+                                             C.byref(g)), "sdf_validate_mesh")
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+        counts = torch.empty((4,), dtype=torch.int64, device=self.device)
+        with self._on_device():
+            rc = self.lib.sdf_mesh_count(C.byref(frame.scene), C.byref(frame.params), C.byref(g),
+                                         C.c_void_p(ws.data_ptr()), nbytes,
+                                         C.c_void_p(counts.data_ptr()), self._stream(stream))
+            abi.check(rc, "sdf_mesh_count")
+            # the copy is ordered behind the count only on the stream it ran on
+            if stream is not None:
+                torch.cuda.synchronize(self.device)
+            nv, nt, evaluated, bricks = (int(x) for x in counts.cpu().tolist())
+            verts = torch.empty((nv, 3), dtype=torch.float32, device=self.device)
+            tris = torch.empty((nt, 3), dtype=torch.int32, device=self.device)
+            nrm = torch.empty((nv, 3), dtype=torch.float32, device=self.device) if normal else None
+            own = torch.empty((nv,), dtype=torch.int32, device=self.device) if prim else None
+
+            def ptr(x):
+                return C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None
+            out = abi.sdf_mesh_out(ptr(verts), nv, ptr(tris), nt, ptr(nrm), ptr(own))
+            rc = self.lib.sdf_mesh_emit(C.byref(frame.scene), C.byref(frame.params), C.byref(g),
+                                        C.c_void_p(ws.data_ptr()), nbytes, C.byref(out),
+                                        self._stream(stream))
+            abi.check(rc, "sdf_mesh_emit")
+            if stream is not None:
+                stream.synchronize()   # the workspace is released on return
+        return Mesh(verts, tris, nrm, own, (nv, nt, evaluated, bricks))
 
     # ---- caller-supplied rays (sdf_abi.h "Rays") ----------------------------
     def render_rays(self, frame: Frame, origins, dirs, unit: bool = False, out=None,
