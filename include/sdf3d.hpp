@@ -18,6 +18,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -494,6 +495,38 @@ inline void render_rays(const Frame& f, const std::vector<sdf_light>& lights, in
 inline void camera_rays(const Frame& f, float* origins, float* dirs,
                         hipStream_t stream = nullptr) {
   check(sdf_camera_rays(&f.camera, &f.params, origins, dirs, stream), "sdf_camera_rays");
+}
+
+// ---- gradients (sdf_abi.h "Gradients") -----------------------------------------
+// The scene function's analytic gradients at n points (device, n x 3 packed
+// floats) with the weights `upstream` (device, n; null: every weight 1).  Returns
+// the 256 parameter sums, row i the sixteen slots of sdf_primitive i (2: k, 4 +
+// j: p[j]); `dist` (device, n) and `grad_points` (device, 3 n: weight x df/dp) are
+// written when non-null.  Allocates its own workspace.  Blocking.
+inline std::array<float, 16 * SDF_MAX_PRIMS> sample_grad(
+    const Frame& f, const float* points, int64_t n, const float* upstream = nullptr,
+    float* dist = nullptr, float* grad_points = nullptr, hipStream_t stream = nullptr) {
+  check_abi();
+  check(sdf_validate_grad(&f.scene, &f.params), "sdf_validate_grad");
+  const int64_t bytes = sdf_grad_workspace_bytes(n);
+  if (bytes < 0) check(static_cast<int>(bytes), "sdf_grad_workspace_bytes");
+  std::array<float, 16 * SDF_MAX_PRIMS> sums{};
+  if (n == 0) return sums;
+  char* buf = nullptr;   // the sums, then the workspace (16-byte aligned: 1024 bytes in)
+  int rc = SDF_OK;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf), sizeof(sums) + size_t(bytes));
+  if (e == hipSuccess) {
+    const sdf_grad_out out = {dist, grad_points, reinterpret_cast<float*>(buf)};
+    rc = sdf_sample_grad(&f.scene, &f.params, points, n, upstream, &out, buf + sizeof(sums), bytes,
+                         stream);
+    if (rc == SDF_OK)
+      e = hipMemcpyAsync(sums.data(), buf, sizeof(sums), hipMemcpyDeviceToHost, stream);
+    if (rc == SDF_OK && e == hipSuccess) e = hipStreamSynchronize(stream);
+  }
+  (void)hipFree(buf);
+  check(rc, "sdf_sample_grad");
+  check_hip(e, "sample_grad");
+  return sums;
 }
 
 // ---- isosurface meshes (sdf_abi.h "Meshes") -----------------------------------

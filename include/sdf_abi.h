@@ -86,7 +86,10 @@ extern "C" {
                                 still 12: sdf_validate_mesh, sdf_mesh_count,
                                    sdf_mesh_emit, sdf_mesh_workspace_bytes
                                    (sdf_grid, sdf_mesh_out), additions
-                                   likewise */
+                                   likewise;
+                                still 12: sdf_validate_grad, sdf_sample_grad,
+                                   sdf_grad_workspace_bytes (sdf_grad_out),
+                                   additions likewise */
 
 /* ---- status codes ------------------------------------------------------ */
 #define SDF_OK               0
@@ -254,6 +257,13 @@ typedef struct {
   float*   normal;                      /* device, optional, 3 per vertex */
   int32_t* prim;                        /* device, optional, 1 per vertex */
 } sdf_mesh_out;                         /* 48 bytes */
+
+/* Gradients (sdf_sample_grad; "Gradients" below) */
+typedef struct {
+  float* dist;         /* device, n, optional: f(p_i)                                   */
+  float* grad_points;  /* device, 3n packed, optional: g_i * df/dp at p_i               */
+  float* grad_prims;   /* device, SDF_MAX_PRIMS * 16 floats, optional (layout below)    */
+} sdf_grad_out;        /* 24 bytes; at least one pointer non-NULL */
 
 /* Render flags */
 #define SDF_FLAG_SHADOW    0x1  /* soft shadow march (voxel_fragment.frag:205) */
@@ -625,8 +635,8 @@ typedef struct {
  *   - asynchronous on `stream`.  SDF_ABI_VERSION stays 12: detect the entry
  *     points by the symbol.
  *   - occlusion and soft-shadow queries, per-ray distance limits, sorting or
- *     compacting rays, tilings and several devices, an ambient-occlusion
- *     output and gradients (autograd) are not offered. */
+ *     compacting rays, tilings and several devices and an ambient-occlusion
+ *     output are not offered; gradients are sdf_sample_grad ("Gradients"). */
 
 /* Rays (sdf_render_rays: the shading pipeline of "Environment" on rays of the
  * caller's own -- an orthographic view, a fisheye, a panorama, a stereo pair,
@@ -768,6 +778,65 @@ typedef struct {
  *   - marching cubes tables, sharp-feature (QEF) placement, mesh
  *     simplification, adaptive grids, several devices and vertex colours are
  *     not offered. */
+
+/* Gradients (sdf_sample_grad: how the scene function f changes with the points
+ * and with the scene's own parameters -- fitting primitives to a point cloud,
+ * recovering a scene from depths, optimising a CSG design; sdf3d_amd/autograd.py
+ * puts torch.autograd on top).  Primitive scenes only.  With g_i = upstream[i]
+ * (1 when upstream is NULL):
+ *   - dist[i] = f(points[i]): in exact precision bit for bit what sdf_sample
+ *     writes (the same evaluators run).
+ *   - grad_points[i] = g_i grad_p f(p_i): the analytic gradient of the scene
+ *     spec, not the finite-difference normal, and not normalised.
+ *   - grad_prims is float[SDF_MAX_PRIMS][16], the sixteen 4-byte slots of
+ *     sdf_primitive: slot 2 = sum_i g_i df/dk, slot 4 + j = sum_i g_i df/dp[j], with
+ *     respect to the PUBLIC fields (a round box's half extents and r, a capsule's
+ *     end points a and b, the blend radius k).  Slots 0, 1 and 3 (kind, op,
+ *     reserved), every parameter slot the kind does not use, the k of a hard
+ *     operator and every primitive >= scene->count are written as 0: all 256
+ *     floats are written by every call with n > 0.
+ *   - the derivative is that of the scene spec's operation sequence, as
+ *     reverse-mode differentiation gives it.  A select (min, max, clamp, abs)
+ *     passes the adjoint to the operand the forward comparison took (min(x, y) =
+ *     y < x ? y : x, max(x, y) = x < y ? y : x, |x|' = -1 for x < 0, else 1); on an
+ *     exact tie either one-sided derivative may come out.  A square root's
+ *     derivative uses a guarded reciprocal, 1 / len for len > 0 and 0 otherwise
+ *     (inside a box, on a torus' or cylinder's axis, at a sphere's centre), so
+ *     finite points, a finite upstream and a validated scene give finite outputs.
+ *   - the fold: with (a, b) the pair "Materials" defines for primitive i's
+ *     operator and m the min or smooth-min, the running value is m(d, v) for the
+ *     unions, -m(-d, v) for the subtractions, -m(-d, -v) for the intersections.
+ *     Hard: m_a = (b < a) ? 0 : 1, m_b = 1 - m_a, m_k = 0.  Smooth, with the
+ *     smooth-min's h as the material fold forms it in the request's precision:
+ *     m_a = (b < a) ? h/2 : 1 - h/2, m_b = 1 - m_a, m_k = h h / 4 - h / 2.  d = +-INF
+ *     before primitive 0 gives h = 0 and no NaN.
+ *   - precision: exact rounds every operation once, fuses nothing and divides
+ *     and takes square roots as IEEE does; fast may contract and uses the
+ *     hardware reciprocal, reciprocal square root and square root.
+ *   - grad_prims is deterministic: no floating-point atomics; the lanes' terms
+ *     are summed across each wave, the waves' sums per workgroup in fp64, and
+ *     the workgroups' rows (fp32, in `workspace`) in index order in fp64, rounded
+ *     once.  The order depends on n only: equal inputs give equal bits.
+ *   - workspace: device memory, 16-byte aligned, sdf_grad_workspace_bytes(n) =
+ *     1024 min(ceil(n / 256), 1024) bytes (at most 1 MiB: the launch is
+ *     grid-stride over a capped grid); needed only with grad_prims.
+ *   - dispatch: always the generic kernel evaluating every primitive (an
+ *     optimisation loop changes the parameters every call, and the backward pass
+ *     needs every primitive's value); params->dispatch is validated and
+ *     otherwise ignored, nothing is compiled at run time and sdf_jit_count does
+ *     not move.  params are used as sdf_sample uses them.
+ *   - SDF_E_INVALID_ARG, decided before any device call (sdf_validate_grad is
+ *     that check of scene and params): everything sdf_validate_query rejects;
+ *     out NULL or all three of its pointers NULL; NULL points with n > 0; n < 0 or
+ *     n > 2^30; grad_prims with a NULL, misaligned or undersized workspace (n > 0).
+ *     SDF_E_UNSUPPORTED: a Mandelbulb scene.  n = 0 is SDF_OK: nothing is
+ *     launched, no buffer is touched and no device is needed.
+ *   - device data: points as under "Queries"; no address or loop bound depends
+ *     on them.  Asynchronous on `stream`.  SDF_ABI_VERSION stays 12: detect the
+ *     entry points by the symbol.
+ *   - second derivatives, gradients of shaded colours, gradients through the
+ *     Mandelbulb, per-point (unreduced) parameter gradients and several devices
+ *     are not offered. */
 
 /* Framebuffer element formats (4 channels R,G,B,A per pixel).
  *   RGBA32F  the shader's float fragment_color (voxel_fragment.frag:12,210).
@@ -1065,6 +1134,17 @@ int sdf_mesh_count(const sdf_scene* scene, const sdf_params* params, const sdf_g
 int sdf_mesh_emit(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
                   void* workspace, int64_t workspace_bytes, const sdf_mesh_out* out,
                   void* stream);
+
+/* Gradients ("Gradients" above).  Additions: SDF_ABI_VERSION stays 12, detect
+ * them by the symbol.  sdf_validate_grad is the host-only check of scene and
+ * params (no device call); sdf_grad_workspace_bytes the size of the workspace for
+ * n points (0 for n = 0), or a negative SDF_E* code. */
+int sdf_validate_grad(const sdf_scene* scene, const sdf_params* params);
+int64_t sdf_grad_workspace_bytes(int64_t n);
+int sdf_sample_grad(const sdf_scene* scene, const sdf_params* params, const float* points,
+                    int64_t n, const float* upstream /* device, n; NULL: every g_i = 1 */,
+                    const sdf_grad_out* out, void* workspace, int64_t workspace_bytes,
+                    void* stream);
 
 /* Scatter `nparts` packed row-block buffers (part r = rank r's output for
  * tiling {block_rows, r, nparts}), laid out back to back in `parts` with a

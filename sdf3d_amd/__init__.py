@@ -4,13 +4,14 @@ Drop-in replacement for the device programs of ezorzin/SDF3D
 (Code/shader/voxel_fragment.frag et al.): a hand-written HIP kernel for
 gfx950 behind the C-ABI in include/sdf_abi.h.  This package holds the ctypes
 binding (abi), the scene/camera presets (scenes), the host-side renderer
-(renderer), OBJ mesh files (meshio), the multi-device frame driver (multigpu) and the algorithmic
+(renderer), OBJ mesh files (meshio), the torch.autograd layer over sdf_sample_grad
+(autograd, imported on demand: it needs torch), the multi-device frame driver (multigpu) and the algorithmic
 cost model used for roofline accounting (costmodel).
 """
 from . import abi, scenes
 from .abi import SdfError, load_library
-from .renderer import Mesh, Renderer, owned_rows, tiling
+from .renderer import Grad, Mesh, Renderer, owned_rows, tiling
 from .scenes import CONFIGS, Frame, config, orbit_view, reference
 
-__all__ = ["abi", "scenes", "SdfError", "load_library", "Mesh", "Renderer", "owned_rows", "tiling",
+__all__ = ["abi", "scenes", "SdfError", "load_library", "Grad", "Mesh", "Renderer", "owned_rows", "tiling",
            "CONFIGS", "Frame", "config", "orbit_view", "reference"]

@@ -127,6 +127,12 @@ class sdf_mesh_out(C.Structure):
                 ("max_tris", C.c_int64), ("normal", C.c_void_p), ("prim", C.c_void_p)]
 
 
+class sdf_grad_out(C.Structure):
+    """Outputs of sdf_sample_grad: device pointers, any may be NULL (not all);
+    grad_prims holds SDF_MAX_PRIMS x 16 floats, the slots of sdf_primitive."""
+    _fields_ = [("dist", C.c_void_p), ("grad_points", C.c_void_p), ("grad_prims", C.c_void_p)]
+
+
 class sdf_params(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("max_steps", C.c_int32),
                 ("max_dist", C.c_float), ("eps", C.c_float), ("shadow_k", C.c_float),
@@ -155,7 +161,7 @@ STRUCT_SIZES = {
     "sdf_primitive": 64, "sdf_scene": 8 + 64 * SDF_MAX_PRIMS + 32, "sdf_camera": 88,
     "sdf_light": 32, "sdf_material": 40, "sdf_params": 80, "sdf_tiling": 24,
     "sdf_driver_config": 36, "sdf_reflect": 16, "sdf_environment": 96, "sdf_hits": 32,
-    "sdf_rays": 32, "sdf_grid": 48, "sdf_mesh_out": 48,
+    "sdf_rays": 32, "sdf_grid": 48, "sdf_mesh_out": 48, "sdf_grad_out": 24,
 }
 MAX_QUERY = 1 << 30   # rays or points of one sdf_trace / sdf_sample call
 
@@ -228,6 +234,11 @@ SIGNATURES = {
                                  C.c_int64, C.c_void_p, C.c_void_p]),
     "sdf_mesh_emit": (C.c_int, [_P(sdf_scene), _P(sdf_params), _P(sdf_grid), C.c_void_p,
                                 C.c_int64, _P(sdf_mesh_out), C.c_void_p]),
+    "sdf_validate_grad": (C.c_int, [_P(sdf_scene), _P(sdf_params)]),
+    "sdf_grad_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "sdf_sample_grad": (C.c_int, [_P(sdf_scene), _P(sdf_params), C.c_void_p, C.c_int64,
+                                  C.c_void_p, _P(sdf_grad_out), C.c_void_p, C.c_int64,
+                                  C.c_void_p]),
     "sdf_validate_rays": (C.c_int, [_P(sdf_scene), _P(sdf_light), C.c_int32, C.c_int32,
                                     _P(sdf_material), C.c_int32, _P(sdf_reflect),
                                     _P(sdf_environment), _P(sdf_params), _P(sdf_rays)]),

@@ -235,6 +235,28 @@ struct MeshArgs {
   int32_t* prim;       // emit, optional: 1 per vertex
   long long max_verts, max_tris;
 };
+// ---- gradients (sdf_sample_grad) ------------------------------------------------
+// The argument block of the gradient kernel (grad_kernel.inc sample_grad), its
+// own: `a` carries the prepared scene, nothing else of it is read.  A grid-stride
+// launch of at most kGradMaxBlocks workgroups of kGradBlock lanes; with
+// grad_prims each workgroup writes one row of kGradSlots floats (the layout of
+// grad_prims) to `rows`, the workspace, which grad_reduce sums.
+constexpr int kGradBlock = 256;                  // threads per workgroup (4 waves)
+constexpr int kGradMaxBlocks = 1024;
+constexpr int kGradSlots = 16 * SDF_MAX_PRIMS;   // floats of grad_prims and of a workspace row
+struct GradArgs {
+  KernelArgs a;   // first: the scene evaluators read it at the start of the segment
+  const float* points;
+  const float* upstream;   // n, or null: every g_i = 1
+  float* dist;             // n, optional
+  float* grad_points;      // 3 n, optional
+  float* rows;             // grad_blocks(n) rows of kGradSlots floats, or null (no grad_prims)
+  long long n;
+};
+__host__ __device__ inline long long grad_blocks(long long n) {
+  const long long b = (n + kGradBlock - 1) / kGradBlock;
+  return b < kGradMaxBlocks ? b : kGradMaxBlocks;
+}
 
 // Waves (8x8 tiles side by side) per render workgroup (render_kernel.inc
 // render / render_tiles / render_ssaa; the built-in and the run-time
@@ -284,6 +306,7 @@ static_assert(sizeof(RenderArgs) <= 4096, "RenderArgs exceeds the 4 KiB kernel-a
 static_assert(sizeof(QueryArgs) <= 4096, "QueryArgs exceeds the 4 KiB kernel-argument limit");
 static_assert(sizeof(RaysArgs) <= 4096, "RaysArgs exceeds the 4 KiB kernel-argument limit");
 static_assert(sizeof(MeshArgs) <= 4096, "MeshArgs exceeds the 4 KiB kernel-argument limit");
+static_assert(sizeof(GradArgs) <= 4096, "GradArgs exceeds the 4 KiB kernel-argument limit");
 // Tiles a wave takes per queue request, queues per launch (workgroup b uses
 // queue b % queues, i.e. one per XCD), and the queues' spacing in uint32s:
 // requests on one address serialise at the memory-side atomic unit, so the
@@ -335,6 +358,11 @@ int launch_mesh_fast_bulb(const MeshArgs& m, int emit, void* stream);
 // the scan over the bricks' counts (mesh.hip): offsets per brick into the
 // workspace, the totals into counts[0..3] (device)
 int launch_mesh_scan(unsigned char* ws, long long nbricks, long long* counts, void* stream);
+// the gradient kernel of each precision (primitive scenes only, always the
+// generic unculled evaluator), followed by grad_reduce into `grad_prims` (device,
+// kGradSlots floats) when it and g.rows are set
+int launch_grad_exact(const GradArgs& g, float* grad_prims, void* stream);
+int launch_grad_fast(const GradArgs& g, float* grad_prims, void* stream);
 int launch_deinterleave(const void* parts, int nparts, int part_stride_rows, int row_bytes,
                         int height, int block_rows, void* frame, void* stream);
 int launch_heatmap(const int32_t* steps, int count, int which, int max_steps, int format,

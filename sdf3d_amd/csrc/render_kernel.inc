@@ -94,6 +94,7 @@
 #define SDF_LAUNCH_CAMERA_RAYS launch_camera_rays_exact
 #define SDF_LAUNCH_MESH launch_mesh_exact
 #define SDF_LAUNCH_MESH_BULB launch_mesh_exact_bulb
+#define SDF_LAUNCH_GRAD launch_grad_exact
 #else
 #define SDF_NS fast_impl
 #define SDF_LAUNCH launch_render_fast
@@ -107,6 +108,7 @@
 #define SDF_LAUNCH_CAMERA_RAYS launch_camera_rays_fast
 #define SDF_LAUNCH_MESH launch_mesh_fast
 #define SDF_LAUNCH_MESH_BULB launch_mesh_fast_bulb
+#define SDF_LAUNCH_GRAD launch_grad_fast
 #endif
 
 namespace sdf {
@@ -3107,6 +3109,11 @@ void query(QueryArgs args) {
 // ---- isosurface meshes (sdf_abi.h "Meshes": sdf_mesh_count, sdf_mesh_emit) -----
 #include "mesh_kernel.inc"
 
+// ---- gradients (sdf_abi.h "Gradients": sdf_sample_grad) -------------------------
+#if !SDF_TU_BULB && !defined(__HIPCC_RTC__)
+#include "grad_kernel.inc"
+#endif
+
 // ---- caller-supplied rays (sdf_abi.h "Rays": sdf_render_rays, sdf_camera_rays) --
 // The path of shade_pixel_reflect (ENV: shade_pixel_env) whose layer 0 is read
 // from memory instead of being formed from (x, y): every layer, the first
@@ -3411,6 +3418,27 @@ int SDF_LAUNCH_MESH(const MeshArgs& m, int variant, int emit, void* stream) {
     default:
       return launch_mesh_scene<SDF_NS::GenericScene>(m, emit, s);
   }
+}
+#endif
+
+#if !SDF_TU_BULB
+// sdf_sample_grad: the grid-stride gradient kernel, then the sum of its rows.
+// The host (sdf_abi.cpp sdf_sample_grad) has bounded n and sized g.rows.
+int SDF_LAUNCH_GRAD(const GradArgs& g, float* grad_prims, void* stream) {
+  if (g.n <= 0 || !g.points || (grad_prims != nullptr) != (g.rows != nullptr))
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  const int nblocks = (int)grad_blocks(g.n);
+  const dim3 block(kGradBlock), grid((unsigned)nblocks);
+  (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
+  if (grad_prims) {
+    hipLaunchKernelGGL((SDF_NS::sample_grad<true>), grid, block, 0, s, g);
+    hipLaunchKernelGGL(SDF_NS::grad_reduce, dim3(1), dim3(4 * kGradSlots), 0, s, g.rows, nblocks,
+                       grad_prims);
+  } else {
+    hipLaunchKernelGGL((SDF_NS::sample_grad<false>), grid, block, 0, s, g);
+  }
+  return (int)hipGetLastError();
 }
 #endif
 

@@ -1455,6 +1455,71 @@ int sdf_mesh_emit(const sdf_scene* scene, const sdf_params* params, const sdf_gr
   return mesh_launch(true, scene, params, grid, nbricks, workspace, nullptr, out, stream);
 }
 
+// ---- gradients (sdf_abi.h "Gradients") -----------------------------------------
+static_assert(sizeof(sdf_grad_out) == 24, "sdf_grad_out layout");
+namespace {
+// scene and params of a gradient call: a query's checks, then the Mandelbulb
+int validate_grad(const sdf_scene* scene, const sdf_params* params) {
+  if (!scene || !params) return SDF_E_INVALID_ARG;
+  const int rc = validate_query(scene, nullptr, query_params(*params, false));
+  if (rc != SDF_OK) return rc;
+  return scene->kind == SDF_SCENE_PRIMITIVES ? SDF_OK : SDF_E_UNSUPPORTED;
+}
+int64_t grad_workspace(int64_t n) {
+  return sdf::grad_blocks(n) * int64_t(sdf::kGradSlots) * int64_t(sizeof(float));
+}
+}  // namespace
+
+int sdf_validate_grad(const sdf_scene* scene, const sdf_params* params) {
+  return validate_grad(scene, params);
+}
+
+int64_t sdf_grad_workspace_bytes(int64_t n) {
+  if (n < 0 || n > kMaxQuery) return SDF_E_INVALID_ARG;
+  return grad_workspace(n);
+}
+
+int sdf_sample_grad(const sdf_scene* scene, const sdf_params* params, const float* points,
+                    int64_t n, const float* upstream, const sdf_grad_out* out, void* workspace,
+                    int64_t workspace_bytes, void* stream) {
+  if (!scene || !params || !out) return SDF_E_INVALID_ARG;
+  if (!out->dist && !out->grad_points && !out->grad_prims) return SDF_E_INVALID_ARG;
+  if (n < 0 || n > kMaxQuery || (n > 0 && !points)) return SDF_E_INVALID_ARG;
+  // n = 0 needs no workspace (sdf_grad_workspace_bytes(0) = 0)
+  if (out->grad_prims && n > 0 &&
+      (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0 ||
+       workspace_bytes < grad_workspace(n)))
+    return SDF_E_INVALID_ARG;
+  const int rc = validate_grad(scene, params);
+  if (rc != SDF_OK) return rc;
+  if (n == 0) return SDF_OK;   // nothing to launch, no device needed
+  // the render's own plan for the prepared scene blocks; always the generic,
+  // unculled evaluator (the dispatch was validated and is otherwise ignored)
+  sdf_params q = query_params(*params, false);
+  q.dispatch = SDF_DISPATCH_UNCULLED;
+  sdf_camera c;
+  sdf_light l;
+  sdf_material m;
+  sdf_defaults(nullptr, &c, &l, &m, nullptr, 0, 0);
+  std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
+  int dummy = 0;   // the plan wants a framebuffer to name; a gradient has none
+  const int prc = sdf::make_render_plan(scene, &c, &l, &m, &q, nullptr, &dummy, nullptr, plan.get());
+  if (prc != SDF_OK) return prc;
+  std::unique_ptr<sdf::GradArgs> g(new sdf::GradArgs());
+  g->a = plan->a;
+  g->a.rgba = nullptr;
+  g->a.steps = nullptr;
+  g->points = points;
+  g->upstream = upstream;
+  g->dist = out->dist;
+  g->grad_points = out->grad_points;
+  g->rows = out->grad_prims ? static_cast<float*>(workspace) : nullptr;
+  g->n = n;
+  const int err = plan->exact ? sdf::launch_grad_exact(*g, out->grad_prims, stream)
+                              : sdf::launch_grad_fast(*g, out->grad_prims, stream);
+  return err == hipSuccess ? SDF_OK : SDF_E_HIP;
+}
+
 // ---- caller-supplied rays (sdf_abi.h "Rays") ----------------------------------
 namespace {
 const sdf_reflect kNoBounce = {0, 1.0f, -1, 0};   // reflect NULL: bounces 0, the composite

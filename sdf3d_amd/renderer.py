@@ -113,6 +113,15 @@ class Mesh(NamedTuple):
     counts: tuple
 
 
+class Grad(NamedTuple):
+    """What ``Renderer.sample_grad`` returns (sdf_grad_out): device tensors, None
+    for an output that was not asked for; `grad_prims` is (16, 16), row i the
+    sixteen slots of primitive i."""
+    dist: object
+    grad_points: object
+    grad_prims: object
+
+
 def grid(origin, cell, n, iso: float = 0.0, dense: bool = False) -> abi.sdf_grid:
     """The sdf_grid of n cells of size `cell` from `origin`; a scalar `cell` or
     `n` is used for all three axes."""
@@ -417,6 +426,53 @@ class Renderer:
                                      self._stream(stream))
         abi.check(rc, "sdf_sample")
         return dist, nrm
+
+    # ---- gradients (sdf_abi.h "Gradients") ----------------------------------
+    def sample_grad(self, frame: Frame, points, upstream=None, dist: bool = False,
+                    grad_points: bool = True, grad_prims: bool = True, stream=None) -> "Grad":
+        """The scene function's analytic gradients at n points (sdf_sample_grad):
+        `points` is a contiguous float32 (n, 3) tensor on this renderer's device,
+        `upstream` a contiguous float32 (n,) tensor of weights g there (None:
+        every g_i = 1).  Returns ``Grad(dist (n,), grad_points (n, 3) = g_i
+        df/dp, grad_prims (16, 16))``: row i of `grad_prims` holds, in the slots of
+        ``sdf_primitive`` (2: k, 4 + j: p[j]), the sums over the points of g_i
+        df/d(parameter), zeros elsewhere.  An output that was not asked for is
+        None.  With n = 0 nothing is launched and `grad_prims` is all zero.
+        Asynchronous on `stream`."""
+        torch = self.torch
+        pts = self._n3(points, "points")
+        n = pts.shape[0]
+        if upstream is not None and (
+                not isinstance(upstream, torch.Tensor) or upstream.dtype != torch.float32
+                or tuple(upstream.shape) != (n,) or not upstream.is_contiguous()
+                or upstream.device != self.device):
+            raise ValueError(f"upstream must be a contiguous float32 ({n},) tensor on {self.device}")
+        if not (dist or grad_points or grad_prims):
+            raise ValueError("sample_grad needs at least one output")
+
+        def new(want, shape):
+            return torch.empty(shape, dtype=torch.float32, device=self.device) if want else None
+        out = Grad(new(dist, (n,)), new(grad_points, (n, 3)),
+                   new(grad_prims, (abi.SDF_MAX_PRIMS, 16)))
+        if n == 0:
+            if out.grad_prims is not None:
+                out.grad_prims.zero_()
+            return out
+        nbytes = int(self.lib.sdf_grad_workspace_bytes(n)) if grad_prims else 0
+        if nbytes < 0:
+            abi.check(nbytes, "sdf_grad_workspace_bytes")
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.device) if grad_prims else None
+        go = abi.sdf_grad_out(*[C.c_void_p(x.data_ptr()) if x is not None else None for x in out])
+        with self._on_device():
+            rc = self.lib.sdf_sample_grad(
+                C.byref(frame.scene), C.byref(frame.params), C.c_void_p(pts.data_ptr()), n,
+                C.c_void_p(upstream.data_ptr()) if upstream is not None else None, C.byref(go),
+                C.c_void_p(ws.data_ptr()) if ws is not None else None, nbytes,
+                self._stream(stream))
+        abi.check(rc, "sdf_sample_grad")
+        if ws is not None and stream is not None:
+            ws.record_stream(stream)   # the workspace is in use on `stream` past this call
+        return out
 
     # ---- isosurface meshes (sdf_abi.h "Meshes") -----------------------------
     def mesh(self, frame: Frame, origin, cell, n, iso: float = 0.0, normal: bool = False,

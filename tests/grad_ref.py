@@ -1,0 +1,364 @@
+"""Reference of sdf_sample_grad (sdf_abi.h "Gradients"): the scene spec restated
+in torch and differentiated by torch's CPU autograd.
+
+``scene_value(kinds, ops, theta, points)`` evaluates the primitive list in the
+CPU oracle's operation order (oracle/oracle_core.h) from the PUBLIC parameters:
+`theta` is (count, 16), row i the slots of sdf_primitive i (2: k, 4 + j: p[j]),
+`points` (n, 3); both tensors of one dtype, float64 for the reference and
+float32 for the yardstick of what fp32 arithmetic can give.  Selects are
+``torch.where`` with the GLSL comparisons (min(x, y) = y < x ? y : x, max(x, y) =
+x < y ? y : x, |x| = x < 0 ? -x : x), so autograd passes the adjoint to the
+operand taken; a length is guarded (zero derivative at zero length).
+
+Besides f it returns the per-point kink margin: the smallest |x - y| over every
+select evaluated (min / max operands, clamp bounds, arguments of abs, k - |a - b|
+against 0, the capsule's h against 0 and 1) -- where it is tiny, fp32 and fp64
+may take different branches and the derivatives legitimately differ.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from sdf3d_amd import abi
+
+SMOOTH = (abi.OP_SMOOTH_UNION, abi.OP_SMOOTH_SUBTRACT, abi.OP_SMOOTH_INTERSECT)
+
+
+class _Eval:
+    def __init__(self, n, dtype):
+        self.margin = torch.full((n,), float("inf"), dtype=torch.float64)
+        self.dtype = dtype
+
+    def note(self, x, y):
+        with torch.no_grad():
+            m = (x - y).abs().to(torch.float64)
+            m = torch.where(torch.isnan(m), torch.full_like(m, float("inf")), m)
+            self.margin = torch.minimum(self.margin, m)
+
+    def gmin(self, x, y):
+        x, y = torch.broadcast_tensors(torch.as_tensor(x, dtype=self.dtype),
+                                       torch.as_tensor(y, dtype=self.dtype))
+        self.note(x, y)
+        return torch.where(y < x, y, x)
+
+    def gmax(self, x, y):
+        x, y = torch.broadcast_tensors(torch.as_tensor(x, dtype=self.dtype),
+                                       torch.as_tensor(y, dtype=self.dtype))
+        self.note(x, y)
+        return torch.where(x < y, y, x)
+
+    def gabs(self, x):
+        self.note(x, torch.zeros_like(x))
+        return torch.where(x < 0, -x, x)
+
+    @staticmethod
+    def sqrt(s):
+        """sqrt(s) with derivative 1 / (2 sqrt(s)) for s > 0 and 0 at s = 0."""
+        pos = s > 0
+        return torch.where(pos, torch.sqrt(torch.where(pos, s, torch.ones_like(s))),
+                           torch.zeros_like(s))
+
+    def box_core(self, v, b):
+        q = [self.gabs(v[c]) - b[c] for c in range(3)]
+        o = [self.gmax(q[c], 0.0) for c in range(3)]
+        outside = self.sqrt(o[0] * o[0] + o[1] * o[1] + o[2] * o[2])
+        inside = self.gmin(self.gmax(q[0], self.gmax(q[1], q[2])), 0.0)
+        return outside + inside
+
+    def prim(self, kind, p, q):
+        """p: 3 tensors (n,); q: the 12 public parameters (0-dim tensors)."""
+        if kind == abi.PRIM_PLANE:
+            return p[0] * q[0] + p[1] * q[1] + p[2] * q[2] + q[3]
+        v = [p[c] - q[c] for c in range(3)]
+        if kind == abi.PRIM_SPHERE:
+            return self.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) - q[3]
+        if kind == abi.PRIM_BOX:
+            return self.box_core(v, [q[3], q[4], q[5]])
+        if kind == abi.PRIM_ROUND_BOX:
+            r = q[6]
+            return self.box_core(v, [q[3] - r, q[4] - r, q[5] - r]) - r
+        if kind == abi.PRIM_TORUS:
+            qx = self.sqrt(v[0] * v[0] + v[2] * v[2]) - q[3]
+            return self.sqrt(qx * qx + v[1] * v[1]) - q[4]
+        if kind == abi.PRIM_CAPSULE:
+            pa = v
+            ba = [q[3 + c] - q[c] for c in range(3)]
+            h0 = (pa[0] * ba[0] + pa[1] * ba[1] + pa[2] * ba[2]) / \
+                (ba[0] * ba[0] + ba[1] * ba[1] + ba[2] * ba[2])
+            h = self.gmin(self.gmax(h0, 0.0), 1.0)
+            u = [pa[c] - ba[c] * h for c in range(3)]
+            return self.sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]) - q[6]
+        assert kind == abi.PRIM_CYLINDER, kind
+        dx = self.sqrt(v[0] * v[0] + v[2] * v[2]) - q[3]
+        dy = self.gabs(v[1]) - q[4]
+        inside = self.gmin(self.gmax(dx, dy), 0.0)
+        ox, oy = self.gmax(dx, 0.0), self.gmax(dy, 0.0)
+        return inside + self.sqrt(ox * ox + oy * oy)
+
+    def smin(self, a, b, k):
+        h = self.gmax(k - self.gabs(a - b), 0.0) / k
+        return self.gmin(a, b) - h * h * k * 0.25
+
+    def combine(self, op, d, v, k):
+        if op == abi.OP_UNION:
+            return self.gmin(d, v)
+        if op == abi.OP_SMOOTH_UNION:
+            return self.smin(d, v, k)
+        if op == abi.OP_SUBTRACT:
+            return self.gmax(d, -v)
+        if op == abi.OP_INTERSECT:
+            return self.gmax(d, v)
+        if op == abi.OP_SMOOTH_SUBTRACT:
+            return -self.smin(-d, v, k)
+        assert op == abi.OP_SMOOTH_INTERSECT, op
+        return -self.smin(-d, -v, k)
+
+
+def scene_value(kinds, ops, theta, points):
+    """(f (n,), kink margin (n,) float64) of the primitive list at `points`;
+    theta[i][s] is slot s of primitive i: a 0-dim tensor, or (n,) with one value
+    per point (which makes per-point parameter gradients one backward pass)."""
+    n = points.shape[0]
+    ev = _Eval(n, points.dtype)
+    p = [points[:, c] for c in range(3)]
+    d = torch.full((n,), float("inf"), dtype=points.dtype)
+    for i, (kind, op) in enumerate(zip(kinds, ops)):
+        q = [theta[i][4 + j] for j in range(12)]
+        v = ev.prim(int(kind), p, q)
+        d = ev.combine(int(op), d, v, theta[i][2])
+    return d, ev.margin
+
+
+def scene_lists(scene):
+    """(kinds, ops, theta float64 (count, 16)) of an abi.sdf_scene."""
+    n = int(scene.count)
+    kinds = [int(scene.prims[i].kind) for i in range(n)]
+    ops = [int(scene.prims[i].op) for i in range(n)]
+    theta = np.zeros((n, 16), dtype=np.float64)
+    for i in range(n):
+        pr = scene.prims[i]
+        theta[i, 0], theta[i, 1], theta[i, 2], theta[i, 3] = pr.kind, pr.op, pr.k, pr.reserved
+        theta[i, 4:] = [pr.p[j] for j in range(12)]
+    return kinds, ops, torch.from_numpy(theta)
+
+
+FLOAT_SLOTS = [2] + list(range(4, 16))   # k and p[0..11]
+
+
+class Result:
+    """f, margin and the gradients of sum_i g_i f(p_i): grad_points (n, 3) = g_i
+    df/dp, grad_prims (count, 16) (zeros in the kind, op and reserved slots), and
+    scale (count, 16) = sum_i |g_i| |df_i/dtheta|, all in the evaluation's dtype."""
+
+
+def gradients(scene, points, upstream=None, dtype=torch.float64, round_upstream=True):
+    """The reference outputs of sdf_sample_grad for `points` ((n, 3), rounded to
+    fp32 values first: the kernel's inputs) and `upstream` ((n,) or None: ones),
+    evaluated and differentiated in `dtype`; `upstream` is rounded to fp32 as well
+    (a kernel input) unless round_upstream is False."""
+    kinds, ops, theta64 = scene_lists(scene)
+    pts = torch.as_tensor(np.asarray(points, dtype=np.float32)).to(dtype).requires_grad_()
+    n = pts.shape[0]
+    g = (torch.ones(n, dtype=dtype) if upstream is None
+         else torch.as_tensor(np.asarray(
+             upstream, dtype=np.float32 if round_upstream else np.float64)).to(dtype))
+    base = theta64.to(torch.float32).to(dtype)
+    # one copy of every parameter per point: the backward pass then returns the
+    # per-point terms g_i df_i/dtheta, whose sum and absolute sum are wanted
+    theta = [[base[i, s].expand(n).clone().requires_grad_() for s in range(16)]
+             for i in range(len(kinds))]
+    f, margin = scene_value(kinds, ops, theta, pts)
+    leaves = [theta[i][s] for i in range(len(kinds)) for s in FLOAT_SLOTS]
+    grads = torch.autograd.grad((f * g).sum(), [pts] + leaves, allow_unused=True)
+    r = Result()
+    r.f, r.margin = f.detach(), margin
+    r.grad_points = grads[0] if grads[0] is not None else torch.zeros_like(pts)
+    r.grad_prims = torch.zeros((len(kinds), 16), dtype=dtype)
+    r.scale = torch.zeros((len(kinds), 16), dtype=dtype)
+    it = iter(grads[1:])
+    for i in range(len(kinds)):
+        for s in FLOAT_SLOTS:
+            t = next(it)
+            if t is not None:
+                r.grad_prims[i, s] = t.sum()
+                r.scale[i, s] = t.abs().sum()
+    return r
+
+
+# ---- the scenes and points the gradient tests share ---------------------------
+COVERAGE_K = 0.3
+# the second primitive of the coverage scenes, per kind: fixed parameters, placed
+# so that points of the +-3 cube fall inside it, beside its faces, edges and caps,
+# and outside
+COVERAGE_PARAMS = {
+    abi.PRIM_SPHERE: (0.6, 0.2, -0.3, 0.7),
+    abi.PRIM_PLANE: (0.3, 0.9, -0.2, 0.25),
+    abi.PRIM_BOX: (0.5, -0.4, 0.3, 1.3, 0.9, 1.1),
+    abi.PRIM_ROUND_BOX: (-0.4, 0.3, 0.5, 1.2, 1.0, 0.9, 0.15),
+    abi.PRIM_TORUS: (0.3, 0.1, -0.2, 1.4, 0.45),
+    abi.PRIM_CAPSULE: (-0.9, -0.5, 0.4, 1.1, 0.8, -0.6, 0.5),
+    abi.PRIM_CYLINDER: (0.2, -0.1, 0.4, 1.1, 1.2),
+}
+KIND_NAMES = {abi.PRIM_SPHERE: "sphere", abi.PRIM_PLANE: "plane", abi.PRIM_BOX: "box",
+              abi.PRIM_ROUND_BOX: "roundbox", abi.PRIM_TORUS: "torus",
+              abi.PRIM_CAPSULE: "capsule", abi.PRIM_CYLINDER: "cylinder"}
+OP_NAMES = {abi.OP_UNION: "union", abi.OP_SMOOTH_UNION: "sunion", abi.OP_SUBTRACT: "sub",
+            abi.OP_INTERSECT: "isect", abi.OP_SMOOTH_SUBTRACT: "ssub",
+            abi.OP_SMOOTH_INTERSECT: "sisect"}
+
+
+def coverage_frame(kind: int, op: int):
+    """A unit sphere, then one primitive of `kind` under `op` (smooth k = 0.3)."""
+    import ctypes as C
+
+    from sdf3d_amd import scenes
+    f = scenes.config("C1", 64, 36)
+    C.memset(C.addressof(f.scene.prims), 0, C.sizeof(f.scene.prims))
+    f.scene.count = 2
+    scenes._prim(f.scene, 0, abi.PRIM_SPHERE, abi.OP_UNION, 0.0, 0.0, 0.0, 0.0, 1.0)
+    scenes._prim(f.scene, 1, kind, op, COVERAGE_K if op in SMOOTH else 0.0,
+                 *COVERAGE_PARAMS[kind])
+    f.params.dispatch = abi.DISPATCH_UNCULLED
+    f.name = f"{KIND_NAMES[kind]}-{OP_NAMES[op]}"
+    return f
+
+
+def named_frame(name: str):
+    """REF, C1, C4 (built-in dispatch) or jit<seed>: test_gpu_jit.custom_scene
+    with that test's generator and primitive count, on the generic kernel."""
+    from sdf3d_amd import scenes
+    if name.startswith("jit"):
+        from test_gpu_jit import custom_scene
+        seed = int(name[3:])
+        f = custom_scene(np.random.default_rng(100 + seed), 2 + seed % 7)
+        f.params.dispatch = abi.DISPATCH_UNCULLED
+        f.name = name
+        return f
+    return scenes.config(name, 64, 36)
+
+
+NAMED = ["REF", "C1", "C4", "jit0", "jit4", "jit6"]
+COVERAGE = [(k, o) for k in COVERAGE_PARAMS for o in OP_NAMES]
+
+
+def all_frames():
+    """name -> frame of every test scene (6 named, 42 coverage)."""
+    out = {n: named_frame(n) for n in NAMED}
+    for k, o in COVERAGE:
+        f = coverage_frame(k, o)
+        out[f.name] = f
+    return out
+
+
+def cube_points(n: int, seed: int = 20260, half: float = 3.0) -> np.ndarray:
+    """n fp32 points, uniform in the cube of +-half around the origin."""
+    rng = np.random.default_rng(seed)
+    return rng.uniform(-half, half, (n, 3)).astype(np.float32)
+
+
+def kink_mask(margin, points, rel: float = 1e-4) -> np.ndarray:
+    """True where the kink margin is at least rel max(1, |p|)."""
+    p = np.linalg.norm(np.asarray(points, dtype=np.float64), axis=1)
+    return np.asarray(margin) >= rel * np.maximum(1.0, p)
+
+
+# ---- the accuracy metric of the GPU tests and of tools/grad_probe.py -----------
+FLOOR = 2.0 ** -20   # of a slot's relative error (a slot the fp32 reference gets exactly)
+
+
+class Case:
+    """The reference side of one (scene, points): computed once, shared."""
+
+    def __init__(self, frame, points, seed=5):
+        self.points = np.ascontiguousarray(points, dtype=np.float32)
+        n = self.points.shape[0]
+        self.count = int(frame.scene.count)
+        probe = gradients(frame.scene, self.points)
+        self.keep = kink_mask(probe.margin.numpy(), self.points)
+        assert (~self.keep).mean() <= 0.05
+        g = np.random.default_rng(seed).uniform(-2.0, 2.0, n).astype(np.float32)
+        g[~self.keep] = 0.0
+        self.upstream = g
+        self.r64 = gradients(frame.scene, self.points, g, torch.float64)
+        self.r32 = gradients(frame.scene, self.points, g, torch.float32)
+        self.den = np.maximum(1.0, np.abs(g.astype(np.float64)))[:, None]
+        self.scale = self.r64.scale.numpy()
+
+    def points_error(self, got):
+        """largest |component error| / max(1, |g_i|) over the kept points"""
+        err = np.abs(np.asarray(got, dtype=np.float64) - self.r64.grad_points.numpy()) / self.den
+        return float(err[self.keep].max()) if self.keep.any() else 0.0
+
+    def prims_error(self, got):
+        """largest |error| / S over the slots with S > 0, each floored at 2^-20;
+        where S = 0 no point contributes and the value must be exactly 0"""
+        got = np.asarray(got, dtype=np.float64)[: self.count]
+        live = self.scale > 0
+        assert np.all(got[~live] == 0.0)
+        if not live.any():
+            return FLOOR
+        rel = np.abs(got - self.r64.grad_prims.numpy())[live] / self.scale[live]
+        return float(np.maximum(rel, FLOOR).max())
+
+    def e32(self):
+        return (self.points_error(self.r32.grad_points.numpy()),
+                self.prims_error(self.r32.grad_prims.numpy().astype(np.float64)))
+
+
+def _ag():
+    from sdf3d_amd import autograd
+    return autograd
+
+
+def _scenes():
+    from sdf3d_amd import scenes
+    return scenes
+
+
+# ---- the fit of the GPU tests: scene, points, optimiser -------------------------
+FIT_STEPS, FIT_RATE = 400, 0.01
+
+
+def fit_frames():
+    """(target, start): a sphere and a round box in smooth union; the start has
+    every float parameter 10 % larger."""
+    tgt = _scenes().config("C1", 64, 36)
+    tgt.scene.count = 2
+    _scenes()._prim(tgt.scene, 0, abi.PRIM_SPHERE, abi.OP_UNION, 0.0, 0.5, 0.4, 0.3, 0.6)
+    _scenes()._prim(tgt.scene, 1, abi.PRIM_ROUND_BOX, abi.OP_SMOOTH_UNION, 0.3,
+                 -0.4, -0.3, -0.2, 0.7, 0.5, 0.6, 0.2)
+    tgt.params.dispatch = abi.DISPATCH_UNCULLED
+    start = tgt.copy()
+    th = _ag().scene_tensor(tgt.scene)
+    th[:, 2:] *= 1.1
+    start.scene = _ag().apply(tgt.scene, th)
+    return tgt, start
+
+
+def fit_points(tgt, n=512):
+    """n fp32 points on the target's surface: random points pulled onto f = 0 by
+    Newton steps along the reference's gradient."""
+    kinds, ops, theta = scene_lists(tgt.scene)
+    p = torch.from_numpy(np.random.default_rng(11).uniform(-1.5, 1.5, (n, 3)))
+    for _ in range(30):
+        p = p.detach().requires_grad_()
+        f, _ = scene_value(kinds, ops, theta, p)
+        (g,) = torch.autograd.grad(f.sum(), p)
+        p = p - (f / (g * g).sum(dim=1).clamp(min=1e-12))[:, None] * g
+    return p.detach().to(torch.float32)
+
+
+def fit(value, theta0):
+    """Adam on mean f^2; returns (first loss, last loss, final theta)."""
+    theta = theta0.clone().requires_grad_()
+    opt = torch.optim.Adam([theta], lr=FIT_RATE)
+    first = None
+    for _ in range(FIT_STEPS):
+        opt.zero_grad()
+        loss = value(theta).square().mean()
+        loss.backward()
+        theta.grad[:, [0, 1, 3]] = 0
+        opt.step()
+        first = float(loss.detach()) if first is None else first
+    return first, float(value(theta.detach()).square().mean()), theta.detach()
