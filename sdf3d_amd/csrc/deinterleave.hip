@@ -9,7 +9,7 @@
 // the reference renders into a single GL context (main.cpp:48,53).
 #include <hip/hip_runtime.h>
 
-#include "kernel_args.h"
+#include "host_api.h"   // this unit's launcher prototypes (and kernel_args.h)
 
 namespace sdf {
 

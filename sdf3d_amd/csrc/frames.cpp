@@ -166,9 +166,9 @@ extern "C" int sdf_render_frames(const sdf_scene* scene, const sdf_camera* camer
     if (hipMemsetAsync(fa.counter, 0, fa.queues * sdf::kQueueStride * 4, (hipStream_t)stream) !=
         hipSuccess)
       return SDF_E_HIP;
-    const int err = plan.exact ? sdf::launch_frames_exact(fa, plan.variant, blocks, stream)
-                               : sdf::launch_frames_fast(fa, plan.variant, blocks, stream);
-    if (err != hipSuccess) return SDF_E_HIP;
+    // built-in kernels only: a run-time specialised scene has left above
+    rc = sdf::launch_built_in(plan, &sdf::RenderUnit::frames, fa, stream, blocks);
+    if (rc != SDF_OK) return rc;
     if (hipEventRecord(ds->done[slot], (hipStream_t)stream) != hipSuccess) return SDF_E_HIP;
     ds->used[slot] = true;
   }

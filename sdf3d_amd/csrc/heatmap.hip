@@ -11,7 +11,7 @@
 // HBM-bound (8 B in, <= 16 B out per pixel).
 #include <hip/hip_runtime.h>
 
-#include "kernel_args.h"
+#include "host_api.h"   // this unit's launcher prototypes (and kernel_args.h)
 
 namespace sdf {
 

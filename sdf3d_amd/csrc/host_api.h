@@ -1,5 +1,18 @@
-// host_api.h -- library-internal host interfaces shared by the C-ABI
-// (sdf_abi.cpp) and the native frame driver (driver.cpp).  Not installed.
+// host_api.h -- the library's internal host interfaces.  Not installed, host
+// only: never handed to hipRTC, no part of sdf_kernel_id.
+//
+//   RenderPlan: a prepared scene and the kernel that serves it, made by
+//     make_render_plan (sdf_abi.cpp); the frame driver (driver.cpp) and
+//     sdf_render_multi (multi.cpp) keep plans and re-launch them.
+//   The kernel launchers: each render unit's as a RenderUnit, the run-time
+//     specialised ones (jit.cpp), and the ladder over both, launch_planned.
+//   Per kernel family its grid and its argument contract, which the built-in
+//     launchers (render_launch.inc) and the run-time specialised ones share.
+//
+// A new kernel family is a kernel body (render_kernel.inc), a
+// launch_*_scene (render_launch.inc) with a RenderUnit slot, a *_args_fit and
+// *_grid here, and one launch_planned (or launch_built_in) line where its
+// entry point has the scene's plan (sdf_abi.cpp scene_plan).
 #pragma once
 
 #include "../../include/sdf_abi.h"
@@ -58,8 +71,95 @@ void plan_set_camera(RenderPlan* plan, const sdf_camera* camera);
 // Enqueue a prepared plan on `stream`.  SDF_OK or SDF_E_HIP.
 int launch_render_plan(const RenderPlan& plan, void* stream);
 
+// ---- compile-time scene variants (kernel_args.h SDF_FIXED_VARIANTS) ---------
+// A primitive's kind as the kernels and the signatures have it: a PLANE whose
+// normal is exactly (0,1,0) is a kPrimPlaneY.
+inline int prim_kind(const sdf_primitive& p) {
+  return p.kind == SDF_PRIM_PLANE && p.p[0] == 0.0f && p.p[1] == 1.0f && p.p[2] == 0.0f
+             ? kPrimPlaneY
+             : p.kind;
+}
+// Variant for a validated scene (kVariantGeneric when no fixed one matches).
+int select_variant(const sdf_scene& scene);
+int scene_signature(const sdf_scene& scene, int* sig);
+
+// ---- the kernel launchers ---------------------------------------------------
+// Every launcher returns a hipError_t as int.
+//
+// The launchers of one render translation unit (render_launch.inc), a slot per
+// kernel family.  `variant` selects the compile-time scene specialisation.
+struct RenderUnit {
+  int (*render)(const RenderArgs& a, int variant, void* stream);
+  // the persistent frame-sequence kernel on `nblocks` 256-thread workgroups
+  int (*frames)(const FramesArgs& a, int variant, void* stream, int nblocks);
+  int (*query)(const QueryArgs& q, int variant, void* stream);   // by QueryArgs::kind
+  int (*rays)(const RaysArgs& q, int variant, void* stream);     // sdf_render_rays
+  int (*mesh)(const MeshArgs& m, int variant, void* stream, int emit);   // mesh_count / mesh_emit
+  // one kernel each, in the units of the primitive scenes alone (null in the
+  // Mandelbulb's): the ray generator of sdf_camera_rays, and the gradient
+  // kernel followed by grad_reduce into `grad_prims`
+  int (*camera_rays)(const RaysArgs& q, int variant, void* stream);
+  int (*grad)(const GradArgs& g, int variant, void* stream, float* grad_prims);
+};
+// Each precision's units in its namespace: render_{exact,fast}.hip, and the
+// Mandelbulb scene's kernels in render_{exact,fast}_bulb.hip, scheduled for
+// ILP (sdf3d_amd/build.py).
+namespace exact_impl { const RenderUnit& unit(); const RenderUnit& bulb_unit(); }
+namespace fast_impl { const RenderUnit& unit(); const RenderUnit& bulb_unit(); }
+inline const RenderUnit& render_unit(bool exact, int variant) {
+  const bool bulb = variant == kVariantBulb;
+  if (exact) return bulb ? exact_impl::bulb_unit() : exact_impl::unit();
+  return bulb ? fast_impl::bulb_unit() : fast_impl::unit();
+}
+// The run-time specialised kernel of a family for the plan's signature and
+// precision (jit.cpp); -1 = none, the caller launches the built-in one.
+int launch_render_jit(const RenderArgs& a, const RenderPlan& plan, void* stream);
+int launch_query_jit(const QueryArgs& q, const RenderPlan& plan, void* stream);
+int launch_rays_jit(const RaysArgs& q, const RenderPlan& plan, void* stream);
+int launch_mesh_jit(const MeshArgs& m, const RenderPlan& plan, void* stream, int emit);
+int jit_compiled_count();
+
+// One kernel launch for a prepared scene, through the built-in kernel of the
+// plan's precision and variant: `built_in` names the family's slot, `x` is
+// what the slot takes behind the stream.  SDF_OK or SDF_E_HIP.
+template <class Args, class... X>
+int launch_built_in(const RenderPlan& plan, int (*RenderUnit::*built_in)(const Args&, int, void*, X...),
+                    const Args& a, void* stream, X... x) {
+  const auto launch = render_unit(plan.exact, plan.variant).*built_in;
+  // a family the variant's unit has no kernel for is an error
+  const int err = launch ? launch(a, plan.variant, stream, x...) : (int)hipErrorInvalidValue;
+  return err == hipSuccess ? SDF_OK : SDF_E_HIP;
+}
+// The same behind the family's run-time specialised kernel, where the plan
+// asks for one and there is one.
+template <class Args, class... X>
+int launch_planned(const RenderPlan& plan, int (*jit)(const Args&, const RenderPlan&, void*, X...),
+                   int (*RenderUnit::*built_in)(const Args&, int, void*, X...), const Args& a,
+                   void* stream, X... x) {
+  if (plan.jit) {
+    const int err = jit(a, plan, stream, x...);
+    if (err != -1) return err == hipSuccess ? SDF_OK : SDF_E_HIP;
+  }
+  return launch_built_in(plan, built_in, a, stream, x...);
+}
+
+// the scan over the bricks' counts (mesh.hip): offsets per brick into the
+// workspace, the totals into counts[0..3] (device)
+int launch_mesh_scan(unsigned char* ws, long long nbricks, long long* counts, void* stream);
+int launch_deinterleave(const void* parts, int nparts, int part_stride_rows, int row_bytes,
+                        int height, int block_rows, void* frame, void* stream);
+int launch_deinterleave_rgb(const void* parts, int nparts, int part_stride_rows, int width,
+                            int height, int block_rows, void* frame, void* stream);
+int launch_heatmap(const int32_t* steps, int count, int which, int max_steps, int format,
+                   void* out, void* stream);
+int launch_tiles_decode(const DecodeParts& d, void* frame, const void* parts, void* stream);
+// `used_out` (may be null): a device word that also receives the stream's
+// length (header word 0), e.g. one slot of the frame driver's lengths array
+// whose slots of consecutive frames are all-gathered in one call.
+int launch_tiles_compact(void* stream_buf, int ntiles, void* stream, uint32_t* used_out = nullptr);
+
 // ---- the render kernels' launch geometry and argument contract -------------
-// Shared by the built-in launchers of every render unit (render_kernel.inc)
+// Shared by the built-in launchers of every render unit (render_launch.inc)
 // and the run-time specialised one (jit.cpp): each refuses with
 // hipErrorInvalidValue what render_args_fit refuses.
 inline dim3 render_block() { return dim3(64 * kWgWaves); }
@@ -71,10 +171,14 @@ inline dim3 render_grid(const KernelArgs& a) {
 inline bool order_fits(const RenderArgs& r, dim3 grid) {
   return r.o.n == 0 || (r.o.n == (int)grid.y && r.o.n <= kMaxOrderBlocks);
 }
-// several lights: at most SDF_MAX_LIGHTS, and never into a TILES stream
+// a stream of shading terms (TILES, SHADE32F) carries one light's and one
+// material's terms of one layer: no kernel of several writes one
+inline bool is_stream(int32_t format) {
+  return format == SDF_FORMAT_TILES || format == SDF_FORMAT_SHADE32F;
+}
+// several lights: at most SDF_MAX_LIGHTS, and never into a stream
 inline bool lights_fit(const RenderArgs& r) {
-  return r.l.n == 0 || (r.l.n > 0 && r.l.n <= SDF_MAX_LIGHTS && r.a.format != SDF_FORMAT_TILES &&
-                        r.a.format != SDF_FORMAT_SHADE32F);
+  return r.l.n == 0 || (r.l.n > 0 && r.l.n <= SDF_MAX_LIGHTS && !is_stream(r.a.format));
 }
 // a material per primitive: one per primitive of a primitive scene, with
 // lights (the materials kernels are lights kernels)
@@ -88,8 +192,7 @@ inline bool materials_fit(const RenderArgs& r) {
 inline bool reflect_fit(const RenderArgs& r) {
   if (!r.r.on) return true;
   const bool prims = r.a.scene_kind == SDF_SCENE_PRIMITIVES;
-  return r.l.n > 0 && r.a.format != SDF_FORMAT_TILES && r.a.format != SDF_FORMAT_SHADE32F &&
-         (prims ? r.m.n == r.a.prim_count && r.m.n > 0 : r.m.n == 0) && r.r.bounces >= 0 &&
+  return r.l.n > 0 && !is_stream(r.a.format) && (prims ? r.m.n == r.a.prim_count && r.m.n > 0 : r.m.n == 0) && r.r.bounces >= 0 &&
          r.r.bounces <= SDF_MAX_BOUNCES && r.r.layer >= -1 && r.r.layer <= r.r.bounces;
 }
 // an environment: a reflect launch (reflect_fit) with known flags, at least
@@ -108,7 +211,7 @@ inline bool render_args_fit(const RenderArgs& r, dim3 grid) {
 }
 
 // ---- the rays kernels' launch geometry and argument contract ----------------
-// Shared by the built-in launchers (render_kernel.inc launch_rays_scene) and
+// Shared by the built-in launchers (render_launch.inc launch_rays_scene) and
 // the run-time specialised one (jit.cpp launch_rays_jit).  64 rays to a wave;
 // sdf_render_rays holds n to 2^30, so the grid fits.
 inline dim3 rays_grid(const RaysArgs& q) {
@@ -129,5 +232,28 @@ inline bool rays_args_fit(const RaysArgs& q) {
          (q.flags & ~SDF_RAYS_UNIT) == 0 && lights_fit(r) && materials_fit(r) && reflect_fit(r) &&
          env_fit(r);
 }
+
+// ---- the query kernels' launch geometry and argument contract ---------------
+// Shared by launch_query_scene and launch_query_jit.  Camera rays on the
+// render's 8x8 tiles over width x height; buffer rays and points 64 to a wave,
+// at most 2^30 of them (sdf_trace and sdf_sample hold n to that), so the grid
+// fits.  An empty grid is a success without a launch.
+inline bool query_args_fit(const QueryArgs& q) {
+  return q.kind == kQueryCamera ||
+         ((q.kind == kQueryRays || q.kind == kQueryPoints) && q.n <= (1ll << 30));
+}
+inline dim3 query_grid(const QueryArgs& q) {
+  if (q.kind == kQueryCamera)
+    return dim3((q.a.width + 8 * kWgWaves - 1) / (8 * kWgWaves), (q.a.height + 7) / 8);
+  return dim3(q.n > 0 ? (unsigned)((q.n + 64 * kWgWaves - 1) / (64 * kWgWaves)) : 0u);
+}
+
+// ---- the mesh kernels' launch geometry and argument contract ----------------
+// Shared by launch_mesh_scene and launch_mesh_jit.  One wave per brick: a
+// count that fits a grid, and the workspace the kernels write through.
+inline bool mesh_args_fit(const MeshArgs& m) {
+  return m.nbricks > 0 && m.nbricks <= 0x7fffffffll && m.ws;
+}
+inline dim3 mesh_grid(const MeshArgs& m) { return dim3((unsigned)m.nbricks); }
 
 }  // namespace sdf

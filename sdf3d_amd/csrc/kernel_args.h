@@ -4,6 +4,10 @@
 // focal term -2/tan(fov*PI/360); voxel_fragment.frag:180, :191-192) so each
 // lane only does per-pixel arithmetic.  Passed by value as the kernel argument
 // so the fields are read with scalar loads (SGPRs), never per lane.
+//
+// Kernel source: hipRTC compiles it with render_kernel.inc, and it enters
+// sdf_kernel_id.  Argument blocks, buffer layouts and the constants kernels
+// and host share live here; every host function's prototype in host_api.h.
 #pragma once
 
 #ifndef __HIPCC_RTC__
@@ -320,55 +324,6 @@ constexpr int kFrameQueues = 32;   // at most; kDefaultQueues by default
 constexpr int kDefaultQueues = 8;
 constexpr int kQueueStride = 64;
 
-// Kernel launchers, one per precision translation unit (render_exact.hip /
-// render_fast.hip); `variant` selects a compile-time scene specialisation
-// (see render_kernel.inc).  Return a hipError_t as int.
-int launch_render_exact(const RenderArgs& a, int variant, void* stream);
-int launch_render_fast(const RenderArgs& a, int variant, void* stream);
-// the persistent frame-sequence kernel on `nblocks` 256-thread workgroups
-int launch_frames_exact(const FramesArgs& a, int variant, int nblocks, void* stream);
-int launch_frames_fast(const FramesArgs& a, int variant, int nblocks, void* stream);
-// the Mandelbulb scene's kernels live in units of their own
-// (render_{fast,exact}_bulb.hip, scheduled for ILP: sdf3d_amd/build.py); the
-// launchers above forward kVariantBulb to these
-int launch_render_exact_bulb(const RenderArgs& a, void* stream);
-int launch_render_fast_bulb(const RenderArgs& a, void* stream);
-int launch_frames_exact_bulb(const FramesArgs& a, int nblocks, void* stream);
-int launch_frames_fast_bulb(const FramesArgs& a, int nblocks, void* stream);
-// the query kernels (QueryArgs::kind) of each precision; kVariantBulb is
-// forwarded to the Mandelbulb units
-int launch_query_exact(const QueryArgs& q, int variant, void* stream);
-int launch_query_fast(const QueryArgs& q, int variant, void* stream);
-int launch_query_exact_bulb(const QueryArgs& q, void* stream);
-int launch_query_fast_bulb(const QueryArgs& q, void* stream);
-// the rays kernels (sdf_render_rays) and the ray generator (sdf_camera_rays) of
-// each precision; kVariantBulb is forwarded to the Mandelbulb units
-int launch_rays_exact(const RaysArgs& q, int variant, void* stream);
-int launch_rays_fast(const RaysArgs& q, int variant, void* stream);
-int launch_rays_exact_bulb(const RaysArgs& q, void* stream);
-int launch_rays_fast_bulb(const RaysArgs& q, void* stream);
-int launch_camera_rays_exact(const RaysArgs& q, void* stream);
-int launch_camera_rays_fast(const RaysArgs& q, void* stream);
-// the mesh kernels of each precision (emit = 0: mesh_count, 1: mesh_emit), one
-// brick per workgroup; kVariantBulb is forwarded to the Mandelbulb units
-int launch_mesh_exact(const MeshArgs& m, int variant, int emit, void* stream);
-int launch_mesh_fast(const MeshArgs& m, int variant, int emit, void* stream);
-int launch_mesh_exact_bulb(const MeshArgs& m, int emit, void* stream);
-int launch_mesh_fast_bulb(const MeshArgs& m, int emit, void* stream);
-// the scan over the bricks' counts (mesh.hip): offsets per brick into the
-// workspace, the totals into counts[0..3] (device)
-int launch_mesh_scan(unsigned char* ws, long long nbricks, long long* counts, void* stream);
-// the gradient kernel of each precision (primitive scenes only, always the
-// generic unculled evaluator), followed by grad_reduce into `grad_prims` (device,
-// kGradSlots floats) when it and g.rows are set
-int launch_grad_exact(const GradArgs& g, float* grad_prims, void* stream);
-int launch_grad_fast(const GradArgs& g, float* grad_prims, void* stream);
-int launch_deinterleave(const void* parts, int nparts, int part_stride_rows, int row_bytes,
-                        int height, int block_rows, void* frame, void* stream);
-int launch_heatmap(const int32_t* steps, int count, int which, int max_steps, int format,
-                   void* out, void* stream);
-int launch_deinterleave_rgb(const void* parts, int nparts, int part_stride_rows, int width,
-                            int height, int block_rows, void* frame, void* stream);
 // TILES decode of parts with their own tilings (sdf_tiles_decode_tilings)
 struct DecodeParts {
   int nparts, width, height;
@@ -398,7 +353,6 @@ struct DecodeParts {
 constexpr uint32_t kTilesBadHeader = SDF_TILES_BAD_HEADER;   // length / tile count disagree
 constexpr uint32_t kTilesBadTile = SDF_TILES_BAD_TILE;       // a tile's offset, size or widths
 constexpr uint32_t kTilesBadField = SDF_TILES_BAD_FIELD;     // an escape field past its tile
-int launch_tiles_decode(const DecodeParts& d, void* frame, const void* parts, void* stream);
 
 // ---- TILES stream buffer (sdf_abi.h SDF_FORMAT_TILES) ----------------------
 // The buffer handed to sdf_render holds the stream (header, offset table,
@@ -422,29 +376,16 @@ struct TilesLayout {
     end = slots + n * kTilePlaneBytes;
   }
 };
-// `used_out` (may be null): a device word that also receives the stream's
-// length (header word 0), e.g. one slot of the frame driver's lengths array
-// whose slots of consecutive frames are all-gathered in one call.
-int launch_tiles_compact(void* stream_buf, int ntiles, void* stream, uint32_t* used_out = nullptr);
 // A tile's head word 0 (sdf_abi.h SDF_FORMAT_TILES): base widths b0 | b1 << 6
 // | b2 << 12, the tile's data in qwords << 18, escaped channels << 26.
 __host__ __device__ inline uint32_t tile_qwords(uint32_t head) { return (head >> 18) & 255u; }
 constexpr int kEscapeWindow = 12;   // base widths tried below the widest residual
 constexpr int kEscapeDwords = 72;   // bitstream bound: 3 width bytes + 3 x 12 x 63 bits
-// run-time specialised kernel for a scene signature (jit.cpp); -1 = none
-int launch_render_jit(const RenderArgs& a, const int* sig, int n, bool exact, void* stream);
-// the same for a query (its kind enters the cache key); -1 = none
-int launch_query_jit(const QueryArgs& q, const int* sig, int n, bool exact, void* stream);
-// the same for sdf_render_rays (steps and env enter the cache key); -1 = none
-int launch_rays_jit(const RaysArgs& q, const int* sig, int n, bool exact, void* stream);
-// the same for a mesh kernel (count or emit enters the cache key); -1 = none
-int launch_mesh_jit(const MeshArgs& m, const int* sig, int n, bool exact, int emit, void* stream);
-int jit_compiled_count();
 
 // ---- compile-time scene variants ------------------------------------------
 // A variant fixes the (kind, op) sequence of the primitive list at compile
 // time; parameter values stay runtime uniforms.  The host picks the variant
-// whose signature equals the scene's (select_variant, sdf_abi.cpp); anything
+// whose signature equals the scene's (host_api.h select_variant); anything
 // else runs the generic kernel, which reads kinds and ops at run time.
 
 // Internal primitive kind: a PLANE whose normal is exactly (0,1,0), evaluated
@@ -489,9 +430,5 @@ enum SceneVariant : int {
   kVariantGeneric = 0,
   kVariantBulb = 100,
 };
-
-// Variant for a validated scene (kVariantGeneric when no fixed one matches).
-int select_variant(const sdf_scene& scene);
-int scene_signature(const sdf_scene& scene, int* sig);
 
 }  // namespace sdf

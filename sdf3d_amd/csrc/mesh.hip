@@ -7,7 +7,7 @@
 // same offsets on every run.
 #include <hip/hip_runtime.h>
 
-#include "kernel_args.h"
+#include "host_api.h"   // this unit's launcher prototypes (and kernel_args.h)
 
 namespace sdf {
 namespace {

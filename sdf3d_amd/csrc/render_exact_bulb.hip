@@ -3,3 +3,4 @@
 #define SDF_EXACT 1
 #define SDF_TU_BULB 1
 #include "render_kernel.inc"
+#include "render_launch.inc"   // the unit's host launchers

@@ -18,14 +18,13 @@
 // constants come from
 // the kernel-argument segment with scalar loads.  The only HBM traffic is the
 // 16-byte float4 store per pixel (row-contiguous 128-byte segments per tile row).
+//
+// Device code only: the four render units include their host launchers
+// behind this file (render_launch.inc); hipRTC compiles this file alone.
 
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #include <math.h>
-
-#include <type_traits>
-
-#include "host_api.h"   // the launchers' grid and argument contract (render_args_fit)
 #else
 // compiled at run time by hipRTC for one scene signature (jit.cpp)
 #define INFINITY __builtin_inff()
@@ -83,32 +82,8 @@
 #endif
 #if SDF_EXACT
 #define SDF_NS exact_impl
-#define SDF_LAUNCH launch_render_exact
-#define SDF_LAUNCH_FRAMES launch_frames_exact
-#define SDF_LAUNCH_BULB launch_render_exact_bulb
-#define SDF_LAUNCH_FRAMES_BULB launch_frames_exact_bulb
-#define SDF_LAUNCH_QUERY launch_query_exact
-#define SDF_LAUNCH_QUERY_BULB launch_query_exact_bulb
-#define SDF_LAUNCH_RAYS launch_rays_exact
-#define SDF_LAUNCH_RAYS_BULB launch_rays_exact_bulb
-#define SDF_LAUNCH_CAMERA_RAYS launch_camera_rays_exact
-#define SDF_LAUNCH_MESH launch_mesh_exact
-#define SDF_LAUNCH_MESH_BULB launch_mesh_exact_bulb
-#define SDF_LAUNCH_GRAD launch_grad_exact
 #else
 #define SDF_NS fast_impl
-#define SDF_LAUNCH launch_render_fast
-#define SDF_LAUNCH_FRAMES launch_frames_fast
-#define SDF_LAUNCH_BULB launch_render_fast_bulb
-#define SDF_LAUNCH_FRAMES_BULB launch_frames_fast_bulb
-#define SDF_LAUNCH_QUERY launch_query_fast
-#define SDF_LAUNCH_QUERY_BULB launch_query_fast_bulb
-#define SDF_LAUNCH_RAYS launch_rays_fast
-#define SDF_LAUNCH_RAYS_BULB launch_rays_fast_bulb
-#define SDF_LAUNCH_CAMERA_RAYS launch_camera_rays_fast
-#define SDF_LAUNCH_MESH launch_mesh_fast
-#define SDF_LAUNCH_MESH_BULB launch_mesh_fast_bulb
-#define SDF_LAUNCH_GRAD launch_grad_fast
 #endif
 
 namespace sdf {
@@ -3272,297 +3247,5 @@ void camera_rays(RaysArgs args) {
 #undef SMIN_KSC
 
 }  // namespace SDF_NS
-
-#ifndef __HIPCC_RTC__   // host launchers (not part of a run-time compiled kernel)
-#ifdef SDF_STATS
-extern "C" int sdf_debug_stats(unsigned long long* out, int n, int reset) {
-  if (n > 128) n = 128;
-  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(SDF_NS::g_sdf_stats), n * 8) != hipSuccess)
-    return -1;
-  if (reset) {
-    static const unsigned long long zero[128] = {};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(SDF_NS::g_sdf_stats), zero, sizeof(zero)) != hipSuccess)
-      return -1;
-  }
-  return 0;
-}
-#endif
-
-// The two run-time booleans of a launch -- step counts asked for, and a
-// supersampled frame -- as template arguments: f(steps, ssaa), each a
-// std::bool_constant.
-template <class F>
-static void with_steps_ssaa(const KernelArgs& a, F&& f) {
-  using T = std::true_type;
-  using N = std::false_type;
-  if (a.ss_log2 > 0) a.steps ? f(T{}, T{}) : f(N{}, T{});
-  else a.steps ? f(T{}, N{}) : f(N{}, N{});
-}
-
-// one launch of scene kernel S: its kernel family by the format and by what
-// rides in the arguments (render_args_fit holds for them), and the
-// step-recording instantiation only when the caller asked for step counts
-template <class S, bool TILES>
-static void launch_scene(const RenderArgs& a, dim3 grid, dim3 block, hipStream_t s) {
-  constexpr bool kFold = !SDF_TU_BULB;   // a primitive list to fold materials over
-#define SDF_GO(...) hipLaunchKernelGGL((SDF_NS::__VA_ARGS__), grid, block, 0, s, a)
-  with_steps_ssaa(a.a, [&](auto steps, auto ssaa) {
-    constexpr bool STEPS = decltype(steps)::value, SSAA = decltype(ssaa)::value;
-    if constexpr (TILES) {
-      SDF_GO(render_tiles<S, true, STEPS>);   // never supersampled (sdf_validate)
-    } else if (a.e.on) {
-      // a reflect launch with an environment (env_fit)
-      SDF_GO(render_env<S, STEPS, SSAA, kFold>);
-    } else if (a.r.on) {
-      // mirror reflections (reflect_fit: lights, and a material table for every
-      // scene with a primitive list; never TILES)
-      SDF_GO(render_reflect<S, STEPS, SSAA, kFold>);
-    } else if (a.m.n > 0) {
-      // a material per primitive (materials_fit: never a Mandelbulb, which has
-      // no primitive list to fold over; never TILES)
-      if constexpr (kFold) SDF_GO(render_materials<S, STEPS, SSAA>);
-    } else if (a.l.n > 0) {
-      // several lights (the host refuses TILES with them)
-      SDF_GO(render_lights<S, STEPS, SSAA>);
-    } else if constexpr (SSAA) {
-      SDF_GO(render_ssaa<S, STEPS>);
-    } else {
-      SDF_GO(render<S, false, STEPS>);
-    }
-  });
-#undef SDF_GO
-}
-
-template <class S>
-static void launch_frames_scene(const FramesArgs& a, int nblocks, hipStream_t s) {
-  bool steps = false;
-  for (int i = 0; i < a.nframes; ++i) steps = steps || a.frame[i].steps != nullptr;
-  if (steps)
-    hipLaunchKernelGGL((SDF_NS::render_frames<S, true>), dim3(nblocks), dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((SDF_NS::render_frames<S, false>), dim3(nblocks), dim3(256), 0, s, a);
-}
-
-// one launch of scene kernel S for a query: camera rays on the render
-// kernels' grid of 8x8 tiles, buffer rays and points 64 to a wave.  The host
-// (sdf_abi.cpp query_launch) has bounded n, so the grid fits.
-template <class S>
-static int launch_query_scene(const QueryArgs& q, hipStream_t s) {
-  const dim3 block(64 * kWgWaves);
-  (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
-  if (q.kind == kQueryCamera) {
-    const dim3 grid((q.a.width + 8 * kWgWaves - 1) / (8 * kWgWaves), (q.a.height + 7) / 8);
-    if (grid.x == 0 || grid.y == 0) return 0;
-    hipLaunchKernelGGL((SDF_NS::query<S, kQueryCamera>), grid, block, 0, s, q);
-  } else {
-    if (q.n <= 0) return 0;
-    if (q.n > (1ll << 30)) return (int)hipErrorInvalidValue;
-    const dim3 grid((unsigned)((q.n + 64 * kWgWaves - 1) / (64 * kWgWaves)));
-    if (q.kind == kQueryRays)
-      hipLaunchKernelGGL((SDF_NS::query<S, kQueryRays>), grid, block, 0, s, q);
-    else if (q.kind == kQueryPoints)
-      hipLaunchKernelGGL((SDF_NS::query<S, kQueryPoints>), grid, block, 0, s, q);
-    else
-      return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
-}
-
-#if SDF_TU_BULB
-int SDF_LAUNCH_QUERY_BULB(const QueryArgs& q, void* stream) {
-  return launch_query_scene<SDF_NS::BulbScene>(q, (hipStream_t)stream);
-}
-#else
-int SDF_LAUNCH_QUERY(const QueryArgs& q, int variant, void* stream) {
-  if (variant == kVariantBulb) return SDF_LAUNCH_QUERY_BULB(q, stream);   // its own unit
-  hipStream_t s = (hipStream_t)stream;
-  switch (variant) {
-#define SDF_LAUNCH_FIXED(id, ...) \
-  case id:                        \
-    return launch_query_scene<SDF_NS::FixedScene<__VA_ARGS__>>(q, s);
-    SDF_FIXED_VARIANTS(SDF_LAUNCH_FIXED)
-#undef SDF_LAUNCH_FIXED
-    default:
-      return launch_query_scene<SDF_NS::GenericScene>(q, s);
-  }
-}
-#endif
-
-// one launch of scene kernel S for a mesh extraction: one wave per brick,
-// mesh_count or mesh_emit.  The host (sdf_abi.cpp mesh_launch) has bounded the
-// grid, so the bricks fit the launch.
-template <class S>
-static int launch_mesh_scene(const MeshArgs& m, int emit, hipStream_t s) {
-  if (m.nbricks <= 0 || m.nbricks > 0x7fffffffll || !m.ws) return (int)hipErrorInvalidValue;
-  const dim3 block(64), grid((unsigned)m.nbricks);
-  (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
-  if (emit) hipLaunchKernelGGL((SDF_NS::mesh_emit<S>), grid, block, 0, s, m);
-  else hipLaunchKernelGGL((SDF_NS::mesh_count<S>), grid, block, 0, s, m);
-  return (int)hipGetLastError();
-}
-
-#if SDF_TU_BULB
-int SDF_LAUNCH_MESH_BULB(const MeshArgs& m, int emit, void* stream) {
-  return launch_mesh_scene<SDF_NS::BulbScene>(m, emit, (hipStream_t)stream);
-}
-#else
-int SDF_LAUNCH_MESH(const MeshArgs& m, int variant, int emit, void* stream) {
-  if (variant == kVariantBulb) return SDF_LAUNCH_MESH_BULB(m, emit, stream);   // its own unit
-  hipStream_t s = (hipStream_t)stream;
-  switch (variant) {
-#define SDF_LAUNCH_FIXED(id, ...) \
-  case id:                        \
-    return launch_mesh_scene<SDF_NS::FixedScene<__VA_ARGS__>>(m, emit, s);
-    SDF_FIXED_VARIANTS(SDF_LAUNCH_FIXED)
-#undef SDF_LAUNCH_FIXED
-    default:
-      return launch_mesh_scene<SDF_NS::GenericScene>(m, emit, s);
-  }
-}
-#endif
-
-#if !SDF_TU_BULB
-// sdf_sample_grad: the grid-stride gradient kernel, then the sum of its rows.
-// The host (sdf_abi.cpp sdf_sample_grad) has bounded n and sized g.rows.
-int SDF_LAUNCH_GRAD(const GradArgs& g, float* grad_prims, void* stream) {
-  if (g.n <= 0 || !g.points || (grad_prims != nullptr) != (g.rows != nullptr))
-    return (int)hipErrorInvalidValue;
-  hipStream_t s = (hipStream_t)stream;
-  const int nblocks = (int)grad_blocks(g.n);
-  const dim3 block(kGradBlock), grid((unsigned)nblocks);
-  (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
-  if (grad_prims) {
-    hipLaunchKernelGGL((SDF_NS::sample_grad<true>), grid, block, 0, s, g);
-    hipLaunchKernelGGL(SDF_NS::grad_reduce, dim3(1), dim3(4 * kGradSlots), 0, s, g.rows, nblocks,
-                       grad_prims);
-  } else {
-    hipLaunchKernelGGL((SDF_NS::sample_grad<false>), grid, block, 0, s, g);
-  }
-  return (int)hipGetLastError();
-}
-#endif
-
-// one launch of scene kernel S for sdf_render_rays: 64 rays to a wave, the env
-// kernels when an environment rides in the arguments, the step-recording
-// instantiation only when the caller asked for step counts.  It refuses what
-// the kernels' loops would trust blindly (host_api.h rays_args_fit).
-template <class S>
-static int launch_rays_scene(const RaysArgs& q, hipStream_t s) {
-  constexpr bool kFold = !SDF_TU_BULB;   // a primitive list to fold materials over
-  if (q.n <= 0) return 0;
-  if (!rays_args_fit(q)) return (int)hipErrorInvalidValue;
-  const dim3 block(64 * kWgWaves), grid(rays_grid(q));
-  (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
-#define SDF_GO(...) hipLaunchKernelGGL((SDF_NS::__VA_ARGS__), grid, block, 0, s, q)
-  if (q.e.on) {
-    if (q.a.steps) SDF_GO(render_rays_env<S, true, kFold>);
-    else SDF_GO(render_rays_env<S, false, kFold>);
-  } else {
-    if (q.a.steps) SDF_GO(render_rays<S, true, kFold>);
-    else SDF_GO(render_rays<S, false, kFold>);
-  }
-#undef SDF_GO
-  return (int)hipGetLastError();
-}
-
-#if SDF_TU_BULB
-int SDF_LAUNCH_RAYS_BULB(const RaysArgs& q, void* stream) {
-  return launch_rays_scene<SDF_NS::BulbScene>(q, (hipStream_t)stream);
-}
-#else
-int SDF_LAUNCH_RAYS(const RaysArgs& q, int variant, void* stream) {
-  if (variant == kVariantBulb) return SDF_LAUNCH_RAYS_BULB(q, stream);   // its own unit
-  hipStream_t s = (hipStream_t)stream;
-  switch (variant) {
-#define SDF_LAUNCH_FIXED(id, ...) \
-  case id:                        \
-    return launch_rays_scene<SDF_NS::FixedScene<__VA_ARGS__>>(q, s);
-    SDF_FIXED_VARIANTS(SDF_LAUNCH_FIXED)
-#undef SDF_LAUNCH_FIXED
-    default:
-      return launch_rays_scene<SDF_NS::GenericScene>(q, s);
-  }
-}
-
-// sdf_camera_rays: the render's grid of 8x8 tiles over width x height
-int SDF_LAUNCH_CAMERA_RAYS(const RaysArgs& q, void* stream) {
-  const dim3 block = render_block();
-  const dim3 grid((q.a.width + 8 * kWgWaves - 1) / (8 * kWgWaves), (q.a.height + 7) / 8);
-  if (q.a.width <= 0 || q.a.height <= 0 || (!q.out0 && !q.out1)) return (int)hipErrorInvalidValue;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(SDF_NS::camera_rays, grid, block, 0, (hipStream_t)stream, q);
-  return (int)hipGetLastError();
-}
-#endif
-
-#if SDF_TU_BULB
-// the Mandelbulb scene's launches (called by the other unit's launchers)
-int SDF_LAUNCH_BULB(const RenderArgs& a, void* stream) {
-  const dim3 block = render_block(), grid = render_grid(a.a);
-  if (grid.x == 0 || grid.y == 0) return 0;
-  if (!render_args_fit(a, grid)) return (int)hipErrorInvalidValue;
-  hipStream_t s = (hipStream_t)stream;
-  (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
-  if (a.a.format == SDF_FORMAT_TILES) launch_scene<SDF_NS::BulbScene, true>(a, grid, block, s);
-  else launch_scene<SDF_NS::BulbScene, false>(a, grid, block, s);
-  return (int)hipGetLastError();
-}
-
-int SDF_LAUNCH_FRAMES_BULB(const FramesArgs& a, int nblocks, void* stream) {
-  if (a.nframes <= 0 || a.tiles_per_frame <= 0 || nblocks <= 0) return 0;
-  (void)hipGetLastError();
-  launch_frames_scene<SDF_NS::BulbScene>(a, nblocks, (hipStream_t)stream);
-  return (int)hipGetLastError();
-}
-#else
-template <bool TILES>
-static int launch_variant(const RenderArgs& a, int variant, dim3 grid, dim3 block,
-                          hipStream_t s) {
-  (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
-  switch (variant) {
-#define SDF_LAUNCH_FIXED(id, ...)                                         \
-  case id:                                                                \
-    launch_scene<SDF_NS::FixedScene<__VA_ARGS__>, TILES>(a, grid, block, s); \
-    break;
-    SDF_FIXED_VARIANTS(SDF_LAUNCH_FIXED)
-#undef SDF_LAUNCH_FIXED
-    default:
-      launch_scene<SDF_NS::GenericScene, TILES>(a, grid, block, s);
-      break;
-  }
-  return (int)hipGetLastError();
-}
-
-int SDF_LAUNCH(const RenderArgs& a, int variant, void* stream) {
-  if (variant == kVariantBulb) return SDF_LAUNCH_BULB(a, stream);   // its own unit
-  const dim3 block = render_block(), grid = render_grid(a.a);
-  if (grid.x == 0 || grid.y == 0) return 0;
-  if (!render_args_fit(a, grid)) return (int)hipErrorInvalidValue;
-  hipStream_t s = (hipStream_t)stream;
-  if (a.a.format == SDF_FORMAT_TILES) return launch_variant<true>(a, variant, grid, block, s);
-  return launch_variant<false>(a, variant, grid, block, s);
-}
-
-int SDF_LAUNCH_FRAMES(const FramesArgs& a, int variant, int nblocks, void* stream) {
-  if (variant == kVariantBulb) return SDF_LAUNCH_FRAMES_BULB(a, nblocks, stream);
-  if (a.nframes <= 0 || a.tiles_per_frame <= 0 || nblocks <= 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  (void)hipGetLastError();
-  switch (variant) {
-#define SDF_LAUNCH_FIXED(id, ...)                                         \
-  case id:                                                                \
-    launch_frames_scene<SDF_NS::FixedScene<__VA_ARGS__>>(a, nblocks, s);  \
-    break;
-    SDF_FIXED_VARIANTS(SDF_LAUNCH_FIXED)
-#undef SDF_LAUNCH_FIXED
-    default:
-      launch_frames_scene<SDF_NS::GenericScene>(a, nblocks, s);
-      break;
-  }
-  return (int)hipGetLastError();
-}
-#endif  // SDF_TU_BULB
-
-#endif  // __HIPCC_RTC__
 
 }  // namespace sdf

@@ -105,6 +105,11 @@ bool invert_view(const float* mf, float* out) {
   return true;
 }
 
+// the ops that blend over a radius k
+bool smooth_op(int op) {
+  return op == SDF_OP_SMOOTH_UNION || op == SDF_OP_SMOOTH_SUBTRACT || op == SDF_OP_SMOOTH_INTERSECT;
+}
+
 bool finite3(const float* v) {
   return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
 }
@@ -276,8 +281,7 @@ void prepare_bounds(const sdf_scene& s, sdf::KernelArgs& a, bool exact = false) 
       default: R = 0; break;
     }
     R = std::fabs(R) * (1.0 + 1e-6) + 1e-6;
-    int kind = pr.kind;
-    if (kind == SDF_PRIM_PLANE && q[0] == 0.0f && q[1] == 1.0f && q[2] == 0.0f) kind = sdf::kPrimPlaneY;
+    const int kind = sdf::prim_kind(pr);
     cull[i] = sdf::cullable(kind, pr.op);
     const double k = pr.op == SDF_OP_SMOOTH_UNION ? pr.k : 0.0;
     for (int j = 0; j < 3; ++j) { cen[i][j] = c[j]; a.bound[i][j] = float(c[j]); }
@@ -316,13 +320,7 @@ namespace sdf {
 // FixedScene kernel (an upward plane through its own kind, kPrimPlaneY)
 int scene_signature(const sdf_scene& scene, int* sig) {
   const int n = scene.count;
-  for (int i = 0; i < n; ++i) {
-    const sdf_primitive& p = scene.prims[i];
-    int kind = p.kind;
-    if (kind == SDF_PRIM_PLANE && p.p[0] == 0.0f && p.p[1] == 1.0f && p.p[2] == 0.0f)
-      kind = kPrimPlaneY;
-    sig[i] = SDF_KO(kind, p.op);
-  }
+  for (int i = 0; i < n; ++i) sig[i] = SDF_KO(prim_kind(scene.prims[i]), scene.prims[i].op);
   return n;
 }
 
@@ -473,7 +471,6 @@ int make_render_plan(const sdf_scene* scene, const sdf_camera* camera, const sdf
 
 int launch_render_plan(const RenderPlan& plan, void* stream) {
   if (plan.rows == 0) return SDF_OK;
-  int err = -1;
   RenderArgs r;
   r.a = plan.a;
   r.o.cost = plan.order.cost;
@@ -484,12 +481,9 @@ int launch_render_plan(const RenderPlan& plan, void* stream) {
   r.m = plan.materials;
   r.r = plan.reflect;
   r.e = plan.env;
-  if (plan.jit) err = launch_render_jit(r, plan.sig, plan.nsig, plan.exact, stream);
-  if (err == -1)
-    err = plan.exact ? launch_render_exact(r, plan.variant, stream)
-                     : launch_render_fast(r, plan.variant, stream);
-  if (err == hipSuccess && plan.tiles_ntiles > 0)
-    err = launch_tiles_compact(plan.a.rgba, plan.tiles_ntiles, stream, plan.tiles_used);
+  const int rc = launch_planned(plan, launch_render_jit, &RenderUnit::render, r, stream);
+  if (rc != SDF_OK || plan.tiles_ntiles == 0) return rc;
+  const int err = launch_tiles_compact(plan.a.rgba, plan.tiles_ntiles, stream, plan.tiles_used);
   return err == hipSuccess ? SDF_OK : SDF_E_HIP;
 }
 
@@ -650,6 +644,17 @@ static void fill_materials(sdf::RenderPlan& plan, const sdf_material* materials,
       m.m[i][3 + c] = materials[i].dif[c];
       m.m[i][6 + c] = materials[i].ref[c];
     }
+}
+
+// A validated sdf_reflect's uniforms (the reflect, env and rays kernels).
+static sdf::ReflectArgs fill_reflect(const sdf_reflect& reflect) {
+  sdf::ReflectArgs r{};
+  r.on = 1;
+  r.bounces = reflect.bounces;
+  r.strength = reflect.strength;
+  r.layer = reflect.layer;
+  r.weight = (reflect.flags & SDF_REFLECT_WEIGHT) ? 1 : 0;
+  return r;
 }
 
 extern "C" {
@@ -834,11 +839,9 @@ int sdf_validate(const sdf_scene* scene, const sdf_camera* camera, const sdf_lig
       const sdf_primitive& pr = scene->prims[i];
       if (pr.kind < 0 || pr.kind >= SDF_PRIM_KIND_COUNT) return SDF_E_INVALID_ARG;
       if (pr.op < 0 || pr.op >= SDF_OP_COUNT) return SDF_E_INVALID_ARG;
-      const bool smooth = pr.op == SDF_OP_SMOOTH_UNION || pr.op == SDF_OP_SMOOTH_SUBTRACT ||
-                          pr.op == SDF_OP_SMOOTH_INTERSECT;
       // a smooth blend radius in [2^-64, 1e15]: the exact smooth-min's
       // h h (k/4) relies on the lower end (render_kernel.inc smin)
-      if (smooth && !(pr.k >= 0x1p-64f && pr.k <= kMaxCoord)) return SDF_E_INVALID_ARG;
+      if (smooth_op(pr.op) && !(pr.k >= 0x1p-64f && pr.k <= kMaxCoord)) return SDF_E_INVALID_ARG;
       for (float v : pr.p)
         if (!std::isfinite(v) || std::fabs(v) > kMaxCoord) return SDF_E_INVALID_ARG;
       if (pr.kind == SDF_PRIM_CAPSULE) {
@@ -890,9 +893,7 @@ int sdf_validate(const sdf_scene* scene, const sdf_camera* camera, const sdf_lig
   (void)material;
   // a valid request no kernel serves: shading terms do not average to the
   // colour, so a resolve of TILES or SHADE32F sub-samples would be wrong
-  if (p.samples > 1 &&
-      (p.output_format == SDF_FORMAT_TILES || p.output_format == SDF_FORMAT_SHADE32F))
-    return SDF_E_UNSUPPORTED;
+  if (p.samples > 1 && sdf::is_stream(p.output_format)) return SDF_E_UNSUPPORTED;
   return SDF_OK;
 }
 
@@ -943,8 +944,7 @@ int sdf_validate_lights(const sdf_scene* scene, const sdf_camera* camera, const 
   const int rc = sdf_validate(scene, camera, &lights[0], material, params, tiling);
   if (rc != SDF_OK) return rc;
   // a TILES or SHADE32F stream carries one light's terms
-  if ((nlights > 1 || light_flags != 0) && (params->output_format == SDF_FORMAT_TILES ||
-                                            params->output_format == SDF_FORMAT_SHADE32F))
+  if ((nlights > 1 || light_flags != 0) && sdf::is_stream(params->output_format))
     return SDF_E_UNSUPPORTED;
   return SDF_OK;
 }
@@ -1000,8 +1000,7 @@ int sdf_validate_materials(const sdf_scene* scene, const sdf_camera* camera,
     if (std::memcmp(&materials[i].shininess, &materials[0].shininess, sizeof(float)) != 0)
       return SDF_E_UNSUPPORTED;
   // a TILES or SHADE32F stream carries one material's constants
-  if (!one_material(materials, nmaterials) && (params->output_format == SDF_FORMAT_TILES ||
-                                               params->output_format == SDF_FORMAT_SHADE32F))
+  if (!one_material(materials, nmaterials) && sdf::is_stream(params->output_format))
     return SDF_E_UNSUPPORTED;
   return SDF_OK;
 }
@@ -1057,8 +1056,7 @@ int sdf_validate_reflect(const sdf_scene* scene, const sdf_camera* camera,
       if (!finite3(materials[i].amb) || !finite3(materials[i].dif) || !finite3(materials[i].ref))
         return SDF_E_INVALID_ARG;
   // a stream carries one layer's terms
-  if (!reflect_is_materials(*reflect) && (params->output_format == SDF_FORMAT_TILES ||
-                                          params->output_format == SDF_FORMAT_SHADE32F))
+  if (!reflect_is_materials(*reflect) && sdf::is_stream(params->output_format))
     return SDF_E_UNSUPPORTED;
   return SDF_OK;
 }
@@ -1079,12 +1077,7 @@ static int launch_reflect(const sdf_scene* scene, const sdf_camera* camera,
   // primitive scene (a Mandelbulb's one material is the plan's own)
   fill_lights(plan, lights, nlights, light_flags);
   if (scene->kind == SDF_SCENE_PRIMITIVES) fill_materials(plan, materials, nmaterials);
-  sdf::ReflectArgs& r = plan.reflect;
-  r.on = 1;
-  r.bounces = reflect->bounces;
-  r.strength = reflect->strength;
-  r.layer = reflect->layer;
-  r.weight = (reflect->flags & SDF_REFLECT_WEIGHT) ? 1 : 0;
+  plan.reflect = fill_reflect(*reflect);
   if (env) plan.env = *env;
   return run_plan(plan, schedule, stream);
 }
@@ -1140,9 +1133,7 @@ int sdf_validate_env(const sdf_scene* scene, const sdf_camera* camera, const sdf
                                       nmaterials, reflect, params, tiling);
   if (rc != SDF_OK) return rc;
   // a stream carries one layer's terms, and no sky or fog
-  if (env && env->flags != 0 && (params->output_format == SDF_FORMAT_TILES ||
-                                 params->output_format == SDF_FORMAT_SHADE32F))
-    return SDF_E_UNSUPPORTED;
+  if (env && env->flags != 0 && sdf::is_stream(params->output_format)) return SDF_E_UNSUPPORTED;
   return SDF_OK;
 }
 
@@ -1223,25 +1214,34 @@ int validate_query(const sdf_scene* scene, const sdf_camera* camera, const sdf_p
   return sdf_validate(scene, camera ? camera : &c, &l, &m, &q, nullptr);
 }
 
-// One validated query: the render's own plan (scene blocks, culling bounds,
-// hoisted camera, dispatch) with the query's buffers in place of a frame's.
-int query_launch(int kind, const sdf_scene* scene, const sdf_camera* camera, const sdf_params& q,
-                 const float* in0, const float* in1, int64_t n, float* t, int32_t* steps,
-                 float* normal, int32_t* prim, void* stream) {
+// The prepared scene of a call that renders no frame (a query, a mesh, a
+// gradient), under the query's params `q`: plan->a with the scene blocks, the
+// culling bounds and the march parameters (and `camera` hoisted where the call
+// has one), no outputs, and beside it the variant, the precision, the JIT flag
+// and the signature.  A render's plan, made with sdf_defaults' camera, light
+// and material standing in for what such a call does not have.
+int scene_plan(const sdf_scene* scene, const sdf_camera* camera, const sdf_params& q,
+               sdf::RenderPlan* plan) {
   sdf_camera c;
   sdf_light l;
   sdf_material m;
   sdf_defaults(nullptr, &c, &l, &m, nullptr, 0, 0);
+  int unused = 0;   // a render's plan refuses a null framebuffer
+  const int rc = sdf::make_render_plan(scene, camera ? camera : &c, &l, &m, &q, nullptr, &unused,
+                                       nullptr, plan);
+  if (rc == SDF_OK) plan->a.rgba = nullptr;
+  return rc;
+}
+
+// One validated query: the scene's plan with the query's buffers.
+int query_launch(int kind, const sdf_scene* scene, const sdf_camera* camera, const sdf_params& q,
+                 const float* in0, const float* in1, int64_t n, float* t, int32_t* steps,
+                 float* normal, int32_t* prim, void* stream) {
   std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
-  // the plan wants a framebuffer to name; a query has none and reads neither field
-  int dummy = 0;
-  const int rc = sdf::make_render_plan(scene, camera ? camera : &c, &l, &m, &q, nullptr, &dummy,
-                                       nullptr, plan.get());
+  const int rc = scene_plan(scene, camera, q, plan.get());
   if (rc != SDF_OK) return rc;
   std::unique_ptr<sdf::QueryArgs> a(new sdf::QueryArgs());
   a->a = plan->a;
-  a->a.rgba = nullptr;
-  a->a.steps = nullptr;
   a->in0 = in0;
   a->in1 = in1;
   a->t = t;
@@ -1251,12 +1251,7 @@ int query_launch(int kind, const sdf_scene* scene, const sdf_camera* camera, con
   a->n = n;
   a->kind = kind;
   a->reserved = 0;
-  int err = -1;
-  if (plan->jit) err = sdf::launch_query_jit(*a, plan->sig, plan->nsig, plan->exact, stream);
-  if (err == -1)
-    err = plan->exact ? sdf::launch_query_exact(*a, plan->variant, stream)
-                      : sdf::launch_query_fast(*a, plan->variant, stream);
-  return err == hipSuccess ? SDF_OK : SDF_E_HIP;
+  return sdf::launch_planned(*plan, sdf::launch_query_jit, &sdf::RenderUnit::query, *a, stream);
 }
 }  // namespace
 
@@ -1354,9 +1349,7 @@ float mesh_skip_bound(const sdf_scene& s, const sdf_grid& g) {
   for (int i = 0; i < s.count; ++i) {
     const sdf_primitive& pr = s.prims[i];
     for (float v : pr.p) S = std::max(S, std::fabs(double(v)));
-    const bool smooth = pr.op == SDF_OP_SMOOTH_UNION || pr.op == SDF_OP_SMOOTH_SUBTRACT ||
-                        pr.op == SDF_OP_SMOOTH_INTERSECT;
-    if (smooth) S = std::max(S, double(pr.k));
+    if (smooth_op(pr.op)) S = std::max(S, double(pr.k));
     if (pr.kind == SDF_PRIM_PLANE)
       L = std::max(L, std::sqrt(double(pr.p[0]) * pr.p[0] + double(pr.p[1]) * pr.p[1] +
                                 double(pr.p[2]) * pr.p[2]));
@@ -1367,25 +1360,17 @@ float mesh_skip_bound(const sdf_scene& s, const sdf_grid& g) {
   return std::nextafter(float(bound), INFINITY);
 }
 
-// One validated mesh call: the render's own plan (scene blocks, culling
-// bounds, dispatch) with the grid and the mesh buffers; the count is followed
-// by the scan that turns the bricks' counts into offsets and totals.
+// One validated mesh call: the scene's plan with the grid and the mesh
+// buffers; the count is followed by the scan that turns the bricks' counts
+// into offsets and totals.
 int mesh_launch(bool emit, const sdf_scene* scene, const sdf_params* params, const sdf_grid* g,
                 int64_t nbricks, void* workspace, int64_t* counts, const sdf_mesh_out* out,
                 void* stream) {
-  const sdf_params q = query_params(*params, false);
-  sdf_camera c;
-  sdf_light l;
-  sdf_material mt;
-  sdf_defaults(nullptr, &c, &l, &mt, nullptr, 0, 0);
   std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
-  int dummy = 0;   // the plan wants a framebuffer to name; a mesh has none
-  const int rc = sdf::make_render_plan(scene, &c, &l, &mt, &q, nullptr, &dummy, nullptr, plan.get());
+  const int rc = scene_plan(scene, nullptr, query_params(*params, false), plan.get());
   if (rc != SDF_OK) return rc;
   std::unique_ptr<sdf::MeshArgs> m(new sdf::MeshArgs());
   m->a = plan->a;
-  m->a.rgba = nullptr;
-  m->a.steps = nullptr;
   for (int i = 0; i < 3; ++i) {
     m->origin[i] = g->origin[i];
     m->cell[i] = g->cell[i];
@@ -1404,13 +1389,10 @@ int mesh_launch(bool emit, const sdf_scene* scene, const sdf_params* params, con
     m->max_verts = out->max_verts;
     m->max_tris = out->max_tris;
   }
-  int err = -1;
-  if (plan->jit)
-    err = sdf::launch_mesh_jit(*m, plan->sig, plan->nsig, plan->exact, emit ? 1 : 0, stream);
-  if (err == -1)
-    err = plan->exact ? sdf::launch_mesh_exact(*m, plan->variant, emit ? 1 : 0, stream)
-                      : sdf::launch_mesh_fast(*m, plan->variant, emit ? 1 : 0, stream);
-  if (err == hipSuccess && !emit) err = sdf::launch_mesh_scan(m->ws, nbricks, (long long*)counts, stream);
+  const int lrc = sdf::launch_planned(*plan, sdf::launch_mesh_jit, &sdf::RenderUnit::mesh, *m,
+                                      stream, emit ? 1 : 0);
+  if (lrc != SDF_OK || emit) return lrc;
+  const int err = sdf::launch_mesh_scan(m->ws, nbricks, (long long*)counts, stream);
   return err == hipSuccess ? SDF_OK : SDF_E_HIP;
 }
 
@@ -1493,31 +1475,22 @@ int sdf_sample_grad(const sdf_scene* scene, const sdf_params* params, const floa
   const int rc = validate_grad(scene, params);
   if (rc != SDF_OK) return rc;
   if (n == 0) return SDF_OK;   // nothing to launch, no device needed
-  // the render's own plan for the prepared scene blocks; always the generic,
-  // unculled evaluator (the dispatch was validated and is otherwise ignored)
+  // always the generic, unculled evaluator (the dispatch was validated and is
+  // otherwise ignored): no run-time specialised kernel is ever tried
   sdf_params q = query_params(*params, false);
   q.dispatch = SDF_DISPATCH_UNCULLED;
-  sdf_camera c;
-  sdf_light l;
-  sdf_material m;
-  sdf_defaults(nullptr, &c, &l, &m, nullptr, 0, 0);
   std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
-  int dummy = 0;   // the plan wants a framebuffer to name; a gradient has none
-  const int prc = sdf::make_render_plan(scene, &c, &l, &m, &q, nullptr, &dummy, nullptr, plan.get());
+  const int prc = scene_plan(scene, nullptr, q, plan.get());
   if (prc != SDF_OK) return prc;
   std::unique_ptr<sdf::GradArgs> g(new sdf::GradArgs());
   g->a = plan->a;
-  g->a.rgba = nullptr;
-  g->a.steps = nullptr;
   g->points = points;
   g->upstream = upstream;
   g->dist = out->dist;
   g->grad_points = out->grad_points;
   g->rows = out->grad_prims ? static_cast<float*>(workspace) : nullptr;
   g->n = n;
-  const int err = plan->exact ? sdf::launch_grad_exact(*g, out->grad_prims, stream)
-                              : sdf::launch_grad_fast(*g, out->grad_prims, stream);
-  return err == hipSuccess ? SDF_OK : SDF_E_HIP;
+  return sdf::launch_built_in(*plan, &sdf::RenderUnit::grad, *g, stream, out->grad_prims);
 }
 
 // ---- caller-supplied rays (sdf_abi.h "Rays") ----------------------------------
@@ -1555,22 +1528,13 @@ int rays_launch(const sdf_scene* scene, const sdf_light* lights, int32_t nlights
   a->a = plan->a;
   a->l = plan->lights;
   a->m = plan->materials;
-  a->r.on = 1;
-  a->r.bounces = reflect.bounces;
-  a->r.strength = reflect.strength;
-  a->r.layer = reflect.layer;
-  a->r.weight = (reflect.flags & SDF_REFLECT_WEIGHT) ? 1 : 0;
+  a->r = fill_reflect(reflect);
   if (env && env->flags != 0) a->e = fill_env(env);
   a->in0 = rays.origins;
   a->in1 = rays.dirs;
   a->n = rays.n;
   a->flags = rays.flags;
-  int err = -1;
-  if (plan->jit) err = sdf::launch_rays_jit(*a, plan->sig, plan->nsig, plan->exact, stream);
-  if (err == -1)
-    err = plan->exact ? sdf::launch_rays_exact(*a, plan->variant, stream)
-                      : sdf::launch_rays_fast(*a, plan->variant, stream);
-  return err == hipSuccess ? SDF_OK : SDF_E_HIP;
+  return sdf::launch_planned(*plan, sdf::launch_rays_jit, &sdf::RenderUnit::rays, *a, stream);
 }
 }  // namespace
 
@@ -1589,9 +1553,7 @@ int sdf_validate_rays(const sdf_scene* scene, const sdf_light* lights, int32_t n
                                   reflect ? reflect : &kNoBounce, env, &q, nullptr);
   if (rc != SDF_OK) return rc;
   // the caller supplies more rays and averages; a stream has no list of rays
-  if (q.samples > 1 || q.output_format == SDF_FORMAT_TILES ||
-      q.output_format == SDF_FORMAT_SHADE32F)
-    return SDF_E_UNSUPPORTED;
+  if (q.samples > 1 || sdf::is_stream(q.output_format)) return SDF_E_UNSUPPORTED;
   return SDF_OK;
 }
 
@@ -1621,9 +1583,11 @@ int sdf_camera_rays(const sdf_camera* camera, const sdf_params* params, float* o
   if (params->samples > 1) return SDF_E_UNSUPPORTED;   // one ray per pixel
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return SDF_E_NO_DEVICE;
-  // the hoisted camera and the quad mapping of a render of this frame size
+  // the hoisted camera and the quad mapping of a render of this frame size;
+  // no scene: the precision alone picks the kernel (variant 0, never JIT)
   std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
   std::unique_ptr<sdf::RaysArgs> a(new sdf::RaysArgs());
+  plan->exact = q.precision == SDF_PRECISION_EXACT;
   plan->a.width = q.width;
   plan->a.height = q.height;
   sdf::plan_set_camera(plan.get(), camera);
@@ -1632,9 +1596,7 @@ int sdf_camera_rays(const sdf_camera* camera, const sdf_params* params, float* o
   a->a.inv_height = 1.0f / (float)q.height;
   a->out0 = origins;
   a->out1 = dirs;
-  const int err = q.precision == SDF_PRECISION_EXACT ? sdf::launch_camera_rays_exact(*a, stream)
-                                                     : sdf::launch_camera_rays_fast(*a, stream);
-  return err == hipSuccess ? SDF_OK : SDF_E_HIP;
+  return sdf::launch_built_in(*plan, &sdf::RenderUnit::camera_rays, *a, stream);
 }
 
 int sdf_jit_count(void) { return sdf::jit_compiled_count(); }

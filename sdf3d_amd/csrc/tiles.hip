@@ -26,7 +26,7 @@
 
 #include <stdint.h>
 
-#include "kernel_args.h"
+#include "host_api.h"   // this unit's launcher prototypes (and kernel_args.h)
 // Exact-precision streams' specular term: 1 = the library fp64 pow alone
 // (through round 4), 0 = shade.h's repeated squaring with the library pow
 // only on lanes near a rounding boundary -- the same floats

@@ -77,6 +77,42 @@ def test_frames_generic_and_jit_scenes():
     _check(rd, frames)
 
 
+@pytest.mark.parametrize("path", ["generic", "unculled", "jit", "bulb"])
+def test_frames_dispatch_paths_exact(path):
+    """The launch paths of the frames family that no case above takes in exact
+    precision: the persistent generic kernel culled and unculled, a run-time
+    specialised scene (one launch per frame) and the Mandelbulb's unit.  Two
+    cameras of 40 x 17 pixels (five tiles and a ragged column across, a ragged
+    last 8-row block): each frame equals sdf_render's, and the same call
+    through SDF_DISPATCH_UNCULLED, bit for bit."""
+    from sdf3d_amd import Renderer, abi
+    rd = Renderer("cuda:0")
+
+    def cams(dispatch):
+        frames = _cams("C5" if path == "bulb" else "C3", 40, 17, abi.PRECISION_EXACT, 2)
+        for f in frames:
+            f.params.dispatch = dispatch
+            if path == "jit":   # swap two primitives: no built-in signature
+                p = f.scene.prims
+                p[2], p[3] = abi.sdf_primitive.from_buffer_copy(p[3]), \
+                    abi.sdf_primitive.from_buffer_copy(p[2])
+        return frames
+
+    def run(frames):
+        outs = [rd.alloc(f)[0].fill_(7) for f in frames]
+        rd.render_frames(frames[0], [f.camera for f in frames], outs)
+        torch.cuda.synchronize()
+        return outs
+
+    dispatch = {"generic": abi.DISPATCH_GENERIC, "unculled": abi.DISPATCH_UNCULLED}.get(
+        path, abi.DISPATCH_AUTO)
+    _check(rd, cams(dispatch), with_steps=True)
+    got, want = run(cams(dispatch)), run(cams(abi.DISPATCH_UNCULLED))
+    for a, b in zip(got, want):
+        assert torch.equal(a.view(torch.uint8), b.view(torch.uint8))
+    assert not torch.equal(got[0].view(torch.uint8), got[1].view(torch.uint8))   # two cameras
+
+
 def test_frames_oracle_parity():
     """The bench path of a sequence (no steps buffer: shadow skip active)
     against the oracle, exact precision, strict policy."""

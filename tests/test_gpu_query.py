@@ -269,6 +269,18 @@ def test_camera_rays(renderer, name, wh):
     """steps equal sdf_render's primary counts in both precisions, with
     SHADOW | AO and with flags 0; in exact precision t, normal and prim equal
     the reference on every pixel."""
+    check_camera_rays(renderer, name, wh)
+
+
+@pytest.mark.parametrize("name", ["C4-generic", "C4-unculled", "J4"])
+def test_camera_rays_dispatch_paths(renderer, name):
+    """The same on the launch paths test_camera_rays does not take: the generic
+    kernel culled and unculled, and a run-time specialised scene.  40 x 17
+    pixels: five tiles and a ragged column across, a ragged last 8-row block."""
+    check_camera_rays(renderer, name, (40, 17))
+
+
+def check_camera_rays(renderer, name, wh):
     W, H = wh
     for prec in (EXACT, FAST):
         f = frame_of(name, prec, wh)
