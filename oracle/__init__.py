@@ -73,6 +73,11 @@ def load(variant: str = "ieee") -> C.CDLL:
     lib.sdf_oracle_shadow.restype = C.c_float
     lib.sdf_oracle_normal.argtypes = [P(abi.sdf_scene), P(abi.sdf_params), F3, F3]
     lib.sdf_oracle_normal.restype = None
+    lib.sdf_oracle_scene_sdf_f64.argtypes = lib.sdf_oracle_scene_sdf.argtypes
+    lib.sdf_oracle_scene_sdf_f64.restype = C.c_double
+    lib.sdf_oracle_normal_f64.argtypes = [P(abi.sdf_scene), P(abi.sdf_params), F3,
+                                          C.POINTER(C.c_double)]
+    lib.sdf_oracle_normal_f64.restype = None
     _libs[variant] = lib
     return lib
 
@@ -97,9 +102,16 @@ def shadow(scene, params, pos, direction, k=10.0):
     return float(s), n.value
 
 
-def normal(scene, params, pos):
+def normal(scene, params, pos, reading: str = "ieee"):
+    """The normal at `pos`: float32 (3,) of the fp32 restatement (reading "ieee")
+    or of its contracted reading ("fma"); float64 (3,), not rounded, of the fp64
+    twin ("f64").  The alternative readings are for diagnosis only."""
+    if reading == "f64":
+        out = (C.c_double * 3)()
+        load().sdf_oracle_normal_f64(C.byref(scene), C.byref(params), _f3(pos), out)
+        return np.array(list(out), dtype=np.float64)
     out = (C.c_float * 3)()
-    load().sdf_oracle_normal(C.byref(scene), C.byref(params), _f3(pos), out)
+    load(reading).sdf_oracle_normal(C.byref(scene), C.byref(params), _f3(pos), out)
     return np.array(list(out), dtype=np.float32)
 
 
@@ -217,8 +229,11 @@ def replay(frame, steps, t=None, mask=None, nthreads: int | None = None, variant
     return rgba, out_steps
 
 
-def scene_sdf(scene, x: float, y: float, z: float) -> float:
-    return float(load().sdf_oracle_scene_sdf(C.byref(scene), x, y, z))
+def scene_sdf(scene, x: float, y: float, z: float, reading: str = "ieee") -> float:
+    """sceneSDF at (x, y, z) as fp32 values, in the reading of `normal`."""
+    if reading == "f64":
+        return float(load().sdf_oracle_scene_sdf_f64(C.byref(scene), x, y, z))
+    return float(load(reading).sdf_oracle_scene_sdf(C.byref(scene), x, y, z))
 
 
 def uniforms(camera, params) -> dict:

@@ -16,6 +16,9 @@
  *   sdf_oracle_replay     fp32 restatement with per-pixel break points imposed
  *                         (forced-step replay: is a kernel's outlier explained
  *                         by the step counts it recorded?  tests/parity.py)
+ *   sdf_oracle_scene_sdf, _normal, _raymarch, _shadow, _uniforms
+ *                         point probes of the fp32 restatement;
+ *   sdf_oracle_scene_sdf_f64, _normal_f64  the same two of the fp64 twin
  */
 #include <math.h>
 #include <stddef.h>
@@ -315,5 +318,20 @@ void sdf_oracle_normal(const sdf_scene* s, const sdf_params* p, const float* pos
   f32_v3 q = f32_mk(pos[0], pos[1], pos[2]);
   f32_v3 n = p->normal_mode == SDF_NORMAL_TETRA ? f32_normal_tetra(s, q, p->normal_eps)
                                                 : f32_normal_central(s, q, p->normal_eps);
+  out[0] = n.x; out[1] = n.y; out[2] = n.z;
+}
+
+/* The same two probes of the fp64 twin (diagnosis only: which points' fp32
+ * normal depends on the rounding; tests/fast_paths.py).  The inputs are the
+ * fp32 values widened, the results are not rounded. */
+double sdf_oracle_scene_sdf_f64(const sdf_scene* s, float x, float y, float z) {
+  return f64_scene_sdf(s, f64_mk(x, y, z));
+}
+
+void sdf_oracle_normal_f64(const sdf_scene* s, const sdf_params* p, const float* pos,
+                           double* out) {
+  f64_v3 q = f64_mk(pos[0], pos[1], pos[2]);
+  f64_v3 n = p->normal_mode == SDF_NORMAL_TETRA ? f64_normal_tetra(s, q, p->normal_eps)
+                                                : f64_normal_central(s, q, p->normal_eps);
   out[0] = n.x; out[1] = n.y; out[2] = n.z;
 }

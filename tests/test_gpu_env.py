@@ -511,9 +511,12 @@ def test_supersampled(renderer, name, s, prec):
 
 # ---- 6. fast precision near the reference -------------------------------------------
 
-def fast_case(name):
-    f = the_frame(name, {"C4": 0, "C3": 2, "REF": 0}[name], FAST)
-    mats = (RR.materials_for(f) if name == "REF" else MR.palette_for(f))
+def fast_case(name, dispatch=None):
+    """(frame in fast precision, materials).  `dispatch` None: the frame's own
+    launch path (a built-in variant, EJ's run-time specialised kernel, the
+    Mandelbulb's unit).  REF and C5 take the one-material form."""
+    f = the_frame(name, {"C4": 0, "C3": 2, "REF": 0, "EJ": 2, "C5": 0}[name], FAST, dispatch)
+    mats = (RR.materials_for(f) if name in ("REF", "C5") else MR.palette_for(f))
     return f, mats
 
 

@@ -59,15 +59,17 @@ def test_frames_formats_and_steps(fmt):
 
 
 def test_frames_generic_and_jit_scenes():
-    """A dispatch-generic scene runs the persistent generic kernel; a scene
-    with no built-in variant goes through its run-time specialised kernel,
-    one launch per frame -- both equal sdf_render."""
+    """A dispatch-generic scene runs the persistent generic kernel, culled and
+    (SDF_DISPATCH_UNCULLED) unculled; a scene with no built-in variant goes
+    through its run-time specialised kernel, one launch per frame -- all equal
+    sdf_render (fast precision)."""
     from sdf3d_amd import Renderer, abi
     rd = Renderer("cuda:0")
-    frames = _cams("C3", 160, 90, 1, 3)
-    for f in frames:
-        f.params.dispatch = abi.DISPATCH_GENERIC
-    _check(rd, frames)
+    for dispatch in (abi.DISPATCH_GENERIC, abi.DISPATCH_UNCULLED):
+        frames = _cams("C3", 160, 90, 1, 3)
+        for f in frames:
+            f.params.dispatch = dispatch
+        _check(rd, frames)
     frames = _cams("C3", 160, 90, 1, 3)
     for f in frames:   # swap two primitives: no built-in signature
         p = f.scene.prims

@@ -3,7 +3,8 @@ include/sdf_abi.h "Meshes") against tests/mesh_ref.py, the NumPy reference over
 the CPU oracle: in exact precision counts, vertices (as bit patterns), triangles,
 normals and owners equal the reference on every dispatch path; skipping bricks
 changes no bit; in fast precision the connectivity is the reference's and the
-positions stay within a measured bound.
+positions stay within a measured bound, on every dispatch path of the
+primitive scenes (tests/fast_paths.py).
 
 Grids: partial bricks, several bricks per axis, sub-second references.  Every
 output buffer is test_gpu_query.py's guarded buffer (64 sentinels behind it,
@@ -15,6 +16,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import fast_paths as FP
 import mesh_ref as M
 from sdf3d_amd import abi, meshio, renderer as R
 from test_gpu_query import FAST, JIT_SEEDS, frame_of, guarded, ptr, same, unguard
@@ -36,6 +38,7 @@ CASES = {
     "J0": ("J0", *C4_GRID, 0.0),
     "J4": ("J4", *C4_GRID, 0.0),
     "J6": ("J6", *C4_GRID, 0.0),
+    "C4-carved": ("C4-carved", *C4_GRID, 0.0),
     "C5": ("C5", (-0.61, -0.32, -0.59), (0.05, 0.05, 0.05), (24, 25, 23), 0.0),
 }
 FINE = ("C4", (-1.01, -0.05, -1.02), (0.04, 0.04, 0.04), (50, 20, 42), 0.0)
@@ -135,7 +138,8 @@ def test_exact_mesh_equals_the_reference(renderer, case):
     assert got["counts"][3] == ref["bricks"][1] and got["counts"][2] <= got["counts"][3]
     assert got["counts"][2] >= ref["bricks"][0]          # every active brick was evaluated
     assert bad == {"verts": 0, "tris": 0, "normal": 0, "prim": 0}
-    assert jit_first == (2 if CASES[case][0] in JIT_SEEDS else 0) and jit_second == 0
+    jit = CASES[case][0] in JIT_SEEDS or CASES[case][0] in FP.JIT
+    assert jit_first == (2 if jit else 0) and jit_second == 0
     if case == "C5":
         assert got["counts"][2] == got["counts"][3]     # no Lipschitz bound: always dense
     if case in ("C1", "C1-zero", "C1-iso"):
@@ -238,21 +242,56 @@ def test_cpp_host_program_mesh(renderer, tmp_path):
 
 
 # 5. fast precision ------------------------------------------------------------------------
-def fast_deviation(rd, case):
+def fast_mesh(rd, case):
+    """The fast mesh of `case`, extracted twice with the same bits.  On a
+    run-time specialised scene the first sdf_mesh_count and the first
+    sdf_mesh_emit in fast precision compile one kernel each, the second
+    extraction none."""
     kind, *spec = CASES[case]
-    _, ref, _, _ = exact_run(rd, case)
-    return M.fast_deviation(ref, raw_mesh(rd, frame_of(kind, FAST), spec), spec[1])
+    f, g = frame_of(kind, FAST), R.grid(*spec)
+    jit = [FP.first_use(("mesh", k, kind)) if kind in FP.JIT else None for k in ("count", "emit")]
+    n = [rd.lib.sdf_jit_count()]
+    ws, nbytes, cn = count(rd, f, g)
+    n.append(rd.lib.sdf_jit_count())
+    got = emit(rd, f, g, ws, nbytes, cn[0], cn[1])
+    n.append(rd.lib.sdf_jit_count())
+    got["counts"] = cn
+    again = raw_mesh(rd, f, spec)
+    n.append(rd.lib.sdf_jit_count())
+    if kind in FP.JIT:
+        assert [n[1] - n[0], n[2] - n[1], n[3] - n[2]] == [jit[0], jit[1], 0], (case, n)
+    assert got["counts"] == again["counts"]
+    for k in ("verts", "tris", "normal", "prim"):
+        assert np.all(same(got[k], again[k])), f"{case}: {k} differs between two fast calls"
+    return got
 
 
-@pytest.mark.parametrize("case", ["C1", "C4"])
+def fast_deviation(rd, case):
+    """(mesh_ref.fast_deviation of the fast mesh, the words of its vertices and
+    normals that differ from the exact mesh's, which equals the reference)."""
+    exact, ref, _, _ = exact_run(rd, case)
+    got = fast_mesh(rd, case)
+    r = M.fast_deviation(ref, got, CASES[case][2])
+    differ = sum(FP.bits_differ(got[k], exact[k]) for k in ("verts", "normal")) \
+        if r["same_connectivity"] else -1
+    return r, differ
+
+
+@pytest.mark.parametrize("case", ["C1", "C4", "C4-generic", "C4-unculled", "C4-carved"])
 def test_fast_mesh_within_the_measured_bound(renderer, case):
     """Grids whose reference lattice has min |w| >= 1e-4, so no sign can flip:
     counts and triangles equal the reference, vertices and normals stay within
-    4 x the measured deviation."""
+    4 x the measured deviation.  The generic kernel culled and unculled and the
+    run-time specialised C4-carved are held to the bound measured on the fixed
+    variants (C4's primitives and smooth kernel, the same grid).  And the fast
+    unit ran: some word of the vertices or normals differs from the exact
+    mesh's, which equals the reference."""
     _, ref, _, _ = exact_run(renderer, case)
     assert ref["min_abs_w"] >= 1e-4
-    r = fast_deviation(renderer, case)
-    print(f"{case}: fast deviation {r}; bounds vertex/cell {FAST_BOUND_V:.3e} normal {FAST_BOUND_N:.3e}")
+    r, differ = fast_deviation(renderer, case)
+    print(f"{case}: fast deviation {r}; bounds vertex/cell {FAST_BOUND_V:.3e} normal "
+          f"{FAST_BOUND_N:.3e}; words differing from the exact mesh {differ}")
     assert r["same_connectivity"]
     assert r["vertex_over_cell"] <= FAST_BOUND_V
     assert r["normal"] <= FAST_BOUND_N
+    assert differ > 0, "the exact kernel's bits: the fast unit did not run"

@@ -2,7 +2,9 @@
 sdf_sample; include/sdf_abi.h "Queries") against tests/query_ref.py, the NumPy
 reference over the CPU oracle's point probes: in exact precision bit for bit on
 every ray, pixel and point, on every dispatch path; in fast precision within a
-measured bound.
+measured bound, on every dispatch path too (tests/fast_paths.py: the bound of
+the fixed variants on scenes of the same arithmetic, and the fast result not
+the exact one's bits).
 
 Sizes: the 200-ray set (three full waves and a tail of 8) plus five hand-made
 rays; frames of 64 x 36 and 37 x 23 (ragged tiles); a 17 x 13 x 11 point grid.
@@ -13,6 +15,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import fast_paths as FP
 import materials_ref as MR
 import query_ref as Q
 from sdf3d_amd import abi, scenes
@@ -49,6 +52,8 @@ def frame_of(kind, prec=EXACT, wh=(64, 36)):
     if kind in JIT_SEEDS:
         seed = JIT_SEEDS[kind]
         f = custom_scene(np.random.default_rng(100 + seed), 2 + seed % 7, *wh)
+    elif kind == "C4-carved":       # run-time specialised, with C4's arithmetic (fast_paths.py)
+        f = FP.PATHS[kind](prec, wh)
     else:
         f = scenes.config(kind.split("-")[0], *wh)
         if kind.endswith("-generic"):
@@ -342,22 +347,99 @@ def test_points_equal_the_oracle(renderer, kind):
 
 
 # 6. fast precision, buffer rays --------------------------------------------------------
-@pytest.mark.parametrize("name", ["REF", "C4", "C5"])
+def counted(rd, key, call):
+    """call()'s result, twice: on a run-time specialised path (`key` names the
+    family's fast kernel on it, else None) the first call compiles exactly one
+    kernel the first time the key is used in this process, the second none;
+    the two results are the same bits."""
+    count = rd.lib.sdf_jit_count
+    n0 = count()
+    got = call()
+    n1 = count()
+    again = call()
+    n2 = count()
+    if key is not None:
+        assert (n1 - n0, n2 - n1) == (FP.first_use(key), 0), (key, n1 - n0, n2 - n1)
+    for k in got:
+        assert np.all(same(got[k], again[k])), f"{key}: {k} differs between two calls"
+    return got
+
+
+@pytest.mark.parametrize("name", ["REF", "C4", "C5", "C4-generic", "C4-unculled", "C4-carved"])
 def test_fast_rays_within_the_measured_bound(renderer, name):
     """Fast precision on the 200-ray set against the reference
     (query_ref.fast_deviation): t against the replay at the kernel's own step
     counts on every ray, normal on the rays whose steps agree with the
     oracle's, prim on every hit ray whose closest owner decision is at least
-    materials_ref.GAP wide (at most 2 % are not: test_query_ref.py)."""
+    materials_ref.GAP wide (at most 2 % are not: test_query_ref.py,
+    test_fast_paths_ref.py).  The generic kernel culled and unculled and the
+    run-time specialised C4-carved are held to the bound measured on the fixed
+    variants: C4's primitives and smooth kernel, the same scene in exact
+    precision as reference.  And the fast unit ran: some word differs from the
+    exact result of the same call, which equals the oracle's."""
     f = frame_of(name, FAST)
     o, d = Q.ray_set()
-    got = trace(renderer, f, o, d)
+    got = counted(renderer, ("trace", name) if name in FP.JIT else None,
+                  lambda: trace(renderer, f, o, d))
     r = Q.fast_deviation(frame_of(name), o, d, got, MR.GAP)
-    print(f"{name}: fast deviation {r}; bounds t {FAST_BOUND_T:.3e} normal {FAST_BOUND_N:.3e}")
+    exact = exact_run(renderer, name)[0]
+    differ = {k: FP.bits_differ(got[k], exact[k][:len(o)]) for k in ("t", "normal")}
+    print(f"{name}: fast deviation {r}; bounds t {FAST_BOUND_T:.3e} normal {FAST_BOUND_N:.3e}; "
+          f"words differing from the exact result {differ}")
     assert r["prim_left_out"] <= 0.02 * r["hit"]
     assert r["prim_wrong"] == 0
     assert r["t"] <= FAST_BOUND_T
     assert r["normal"] <= FAST_BOUND_N
+    assert differ["t"] + differ["normal"] > 0, "the exact kernel's bits: the fast unit did not run"
+
+
+# 6b. fast precision, points ------------------------------------------------------------
+def sample(rd, f, P, n=None, normal=True):
+    """sdf_sample of the first n points through the C ABI into guarded buffers."""
+    torch = rd.torch
+    n = len(P) if n is None else n
+    Pd = dev(rd, P)
+    bd = guarded(rd, n, 1, torch.float32)
+    bn = guarded(rd, n, 3, torch.float32, normal)
+    rc = rd.lib.sdf_sample(C.byref(f.scene), C.byref(f.params), ptr(Pd), n, ptr(bd), ptr(bn),
+                           C.c_void_p(torch.cuda.current_stream(rd.device).cuda_stream))
+    abi.check(rc, "sdf_sample")
+    torch.cuda.synchronize()
+    return {"dist": unguard(bd, n, 1), "normal": unguard(bn, n, 3)}
+
+
+@pytest.mark.parametrize("kind", ["REF", "C4", "C4-generic", "C4-unculled", "C4-carved", "C5"])
+def test_fast_points_within_the_bound(renderer, kind):
+    """Fast sdf_sample on the 17 x 13 x 11 grid, on all five launch paths,
+    against the oracle (fast_paths.point_deviation).  dist is held to
+    FAST_BOUND_T, which bounds a whole march's t -- a sum of up to max_steps of
+    these evaluations -- in the same relative metric over REF, C4 and C5; one
+    evaluation is held to no looser bound.  normal is held to FAST_BOUND_N,
+    which bounds the same tap code at hit points, there with P itself
+    deviating; at most 2 % of the points, where the oracle's own readings
+    disagree, are left out.  Some word differs from the exact result of the
+    same call (test_points_equal_the_oracle holds that one); C4-carved
+    compiles one kernel, once.  On the generic path the first n results do not
+    depend on n."""
+    f, P = frame_of(kind, FAST), Q.grid()
+    got = counted(renderer, ("sample", kind) if kind in FP.JIT else None,
+                  lambda: sample(renderer, f, P))
+    exact = sample(renderer, frame_of(kind), P)
+    differ = {k: FP.bits_differ(got[k], exact[k]) for k in got}
+    r = FP.point_deviation(frame_of(kind), P, got["dist"], got["normal"])
+    print(f"{kind}: fast deviation {r}; bounds dist {FAST_BOUND_T:.3e} normal {FAST_BOUND_N:.3e}; "
+          f"words differing from the exact result {differ}")
+    assert r["normal_left_out"] <= FP.LEFT_OUT_SHARE * r["points"]
+    assert r["dist"] <= FAST_BOUND_T
+    assert r["normal"] <= FAST_BOUND_N
+    assert differ["dist"] + differ["normal"] > 0, "the exact kernel's bits: the fast unit did not run"
+    if kind == "C4-generic":
+        for n in (1, 63, 64, 65):
+            part = sample(renderer, f, P, n=n)
+            for k in part:
+                assert len(part[k]) == n and np.all(same(part[k], got[k][:n])), (k, n)
+        only = sample(renderer, f, P, normal=False)
+        assert only["normal"] is None and np.all(same(only["dist"], got["dist"]))
 
 
 # 7. the C++ host program -----------------------------------------------------------------

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import env_ref as ER
+import fast_paths as FP
 import query_ref as QR
 import reflect_ref as RR
 from parity import quantize
@@ -390,33 +391,74 @@ def own_layers(rd, f, o, d, bounces, env, mats, lights):
     return Sj, Sj[..., 0] > 0
 
 
-def rays_fast_deviation(rd, name, bounces):
-    """test_gpu_env.fast_deviation with the frame shaded from its camera rays."""
-    f, mats = fast_case(name)
+# case -> (test_gpu_env.fast_case's frame, dispatch): the fixed variants the bound
+# was measured on, then C4 on the generic kernel culled and unculled, the
+# run-time specialised EJ (round box, plane, torus under smooth union: kinds and
+# an operator of C4's) and the Mandelbulb's unit
+FAST_CASES = {"C4": ("C4", None), "C3": ("C3", None), "REF": ("REF", None),
+              "C4-generic": ("C4", G), "C4-unculled": ("C4", U), "EJ": ("EJ", None),
+              "C5": ("C5", None)}
+
+
+def rays_fast_deviation(rd, name, bounces, dispatch=None, frame_out=None):
+    """test_gpu_env.fast_deviation with the frame shaded from its camera rays.
+    `frame_out`: a dict that receives the case (f, mats, lights, env, o, d) and
+    the fast composite `out`."""
+    f, mats = fast_case(name, dispatch)
     lights, env = [LIGHTS[0]], ER.environment(ALL)
     o, d = cam_rays(rd, f)
     Sj, alive = own_layers(rd, f, o, d, bounces, env, mats, lights)
     out, st = both(rd, f, o, d, True, lights=lights, materials=mats,
                    reflect=RR.reflect(bounces, 1.0), env=env)
     assert np.array_equal(st, Sj.sum(axis=1))
+    if frame_out is not None:
+        frame_out.update(f=f, mats=mats, lights=lights, env=env, o=o, d=d, out=out)
     J = bounces + 1
     return ER.fast_deviation(f, mats, lights, env, bounces, out.reshape(H, W, 4),
                              Sj.reshape(H, W, J, 2), alive.reshape(H, W, J))
 
 
 @pytest.mark.parametrize("bounces", [1, 2])
-@pytest.mark.parametrize("name", ["C4", "C3", "REF"])
-def test_fast_is_near_the_reference(renderer, name, bounces):
+@pytest.mark.parametrize("case", list(FAST_CASES))
+def test_fast_is_near_the_reference(renderer, case, bounces):
     """The fast composite of the camera's rays with SKY | SUN | FOG against the
     reference replayed at the kernel's own per-layer step counts, taken by
     `layer` passes: within test_gpu_env.FAST_BOUND, the project's measured bound
     for this arithmetic on these rays, with at most ER.BOUNDARY_SHARE of the
-    frame left out."""
-    dev, left_out, pixels = rays_fast_deviation(renderer, name, bounces)
-    print(f"{name} bounces {bounces}: largest deviation {dev:.3e}, {left_out} of {pixels} rays "
-          f"left out; bound {FAST_BOUND:.3e}")
+    frame left out -- on the fixed variants it was measured on, and with the
+    same constant on the generic kernel culled and unculled, a run-time
+    specialised scene and the Mandelbulb's unit.  And the fast unit ran: some
+    word of the composite differs from the exact result of the same call
+    (test_camera_rays_shade_to_the_frame holds that one); the run-time
+    specialised scene compiles one rays kernel per instantiation, once."""
+    name, dispatch = FAST_CASES[case]
+    jit = case == "EJ"
+    if jit:     # the two instantiations the case uses: without and with step counts
+        f, mats = fast_case(name, dispatch)
+        o, d = cam_rays(renderer, f)
+        kw = dict(lights=[LIGHTS[0]], materials=mats, reflect=RR.reflect(bounces, 1.0),
+                  env=ER.environment(ALL))
+        count = renderer.lib.sdf_jit_count
+        for steps in (False, True):
+            n0 = count()
+            shade(renderer, f, o, d, True, steps=steps, **kw)
+            n1 = count()
+            shade(renderer, f, o, d, True, steps=steps, **kw)
+            assert (n1 - n0, count() - n1) == (FP.first_use(("rays", case, steps)), 0), steps
+    before = renderer.lib.sdf_jit_count()
+    run = {}
+    dev, left_out, pixels = rays_fast_deviation(renderer, name, bounces, dispatch, run)
+    assert renderer.lib.sdf_jit_count() == before
+    g = run["f"].copy()
+    g.params.precision = EXACT
+    exact, _ = both(renderer, g, run["o"], run["d"], True, lights=run["lights"],
+                    materials=run["mats"], reflect=RR.reflect(bounces, 1.0), env=run["env"])
+    differ = FP.bits_differ(run["out"], exact)
+    print(f"{case} bounces {bounces}: largest deviation {dev:.3e}, {left_out} of {pixels} rays "
+          f"left out; bound {FAST_BOUND:.3e}; {differ} words differ from the exact result")
     assert left_out <= ER.BOUNDARY_SHARE * pixels
     assert dev <= FAST_BOUND
+    assert differ > 0, "the exact kernel's bits: the fast unit did not run"
 
 
 # ---- 9. the C++ host program -----------------------------------------------------------------
