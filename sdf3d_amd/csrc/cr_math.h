@@ -20,9 +20,9 @@
 //                           every positive k in its domain.
 //   cr_log(x)            == (float)log((double)x) for every x.  Fast path:
 //                           m in [sqrt(1/2), sqrt(2)), f = (m-1)/(m+1) with a
-//                           refined v_rcp_f64, 2 f (1 + s/3 + ... + s^8/17)
+//                           refined v_rcp_f64, 2 f (1 + s/3 + ... + s^7/15)
 //                           with s = f^2, plus e ln2, in fp64 (error below
-//                           2^-49 relative); when that value lies too close to
+//                           2^-42 relative); when that value lies too close to
 //                           a float rounding boundary to round it safely, or x
 //                           is not a positive normal float, the lane takes the
 //                           fp64 library log the oracle's reading is.
@@ -103,23 +103,6 @@ __device__ __forceinline__ float cr_sqrt_g(float x) {
 }
 __device__ __forceinline__ float cr_sqrt(float x) { return cr_sqrt_g<SDF_CRM_SQRT_GUARD>(x); }
 
-// N square roots behind ONE guard (independent chains stay in one basic
-// block, render_kernel.inc mandelbulb_n): each s[i] == cr_sqrt(x[i])
-template <int N>
-__device__ __forceinline__ void cr_sqrt_n(const float (&x)[N], float (&s)[N]) {
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    s[i] = sqrt_fast(x[i]);
-    ok = ok & sqrt_guard(x[i]);
-  }
-  if (any_lane(!ok)) {
-    SDF_CRM_COLD();
-#pragma unroll
-    for (int i = 0; i < N; i++) s[i] = sqrt_guard(x[i]) ? s[i] : __builtin_sqrtf(x[i]);
-  }
-}
-
 // 1/x for x in [2^-100, 2^100) (the caller's domain; no guard): v_rcp and
 // one Newton step with an exact fma residual, checked equal to IEEE 1.0f / x
 // on every float of that range
@@ -140,8 +123,7 @@ __device__ __forceinline__ float div_prepared(float a, float b, float yb) {
 
 // a / l from y = RN(1/l) (the host's, or rcp_fast) by ONE Markstein step:
 // q0 = RN(a y), r = RN(l q0 - a), q1 = RN(q0 - r y) == RN(a/l) wherever
-// nothing underflows or overflows.  Proof (round 6; rounds 1-5 took a second
-// step because q0 need not be faithful):
+// nothing underflows or overflows.  Proof (q0 need not be faithful):
 //   Let Q = a/l = mu 2^j (mu in [1,2)), u = ulp(Q), l = ml 2^e (ml in [1,2);
 //   a power-of-two l makes everything exact).  |y - 1/l| <= ulp(1/l)/2 gives
 //   |a y - Q| <= E u with E = mu (ml/2) / 2 < ml/2.
@@ -168,15 +150,8 @@ __device__ __forceinline__ float div_prepared(float a, float b, float yb) {
 // in [1, 2^17) and its divisor the width (height) the KERNEL indexes, an
 // integer in [1, 2^16] -- with supersampling the sub-sample width S W, which
 // sdf_validate holds to 65536 like a plain frame's.
-// SDF_CRM_DIV_STEPS 2: rounds 1-5's second step (A/B only; same results)
-#ifndef SDF_CRM_DIV_STEPS
-#define SDF_CRM_DIV_STEPS 1
-#endif
 __device__ __forceinline__ float div_refined(float a, float l, float y) {
-  float q = a * y;
-#if SDF_CRM_DIV_STEPS == 2
-  q = __builtin_fmaf(-__builtin_fmaf(l, q, -a), y, q);
-#endif
+  const float q = a * y;
   const float r = __builtin_fmaf(l, q, -a);
   return __builtin_fmaf(-r, y, q);
 }
@@ -200,22 +175,15 @@ __device__ __forceinline__ bool div3_ok(float a0, float a1, float a2, float l) {
   return d & n;
 }
 // (a0, a1, a2) / l from the host's y = RN(1/l), l's range checked by the
-// caller (wave-uniform): the Mandelbulb's (p - c) / scale
-// SDF_CRM_DIV3_MIN3 1 (round 6): the wave's fast test is ONE v_min3_f32 of
-// the numerators' magnitudes against 2^-60 (2 VALU instead of 5); a wave
-// where it fails (a zero numerator: the Mandelbulb's p - c is rarely exactly
-// zero) takes the exact numerators_ok test in the cold block.  Same
-// quotients: a lane passing the min3 test passes numerators_ok.
-#ifndef SDF_CRM_DIV3_MIN3
-#define SDF_CRM_DIV3_MIN3 1
-#endif
+// caller (wave-uniform): the Mandelbulb's (p - c) / scale.  The wave's fast
+// test is ONE v_min3_f32 of the numerators' magnitudes against 2^-60 (2 VALU
+// instead of 5); a wave where it fails (a zero numerator: the Mandelbulb's
+// p - c is rarely exactly zero) takes the exact numerators_ok test in the
+// cold block.  Same quotients: a lane passing the min3 test passes
+// numerators_ok.
 __device__ __forceinline__ void div3_prepared(float& a0, float& a1, float& a2, float l, float y) {
-#if SDF_CRM_DIV3_MIN3
   const bool fast = __builtin_fminf(__builtin_fminf(__builtin_fabsf(a0), __builtin_fabsf(a1)),
                                     __builtin_fabsf(a2)) >= 0x1p-60f;
-#else
-  const bool fast = numerators_ok(a0, a1, a2);
-#endif
   float q0 = div_refined(a0, l, y), q1 = div_refined(a1, l, y), q2 = div_refined(a2, l, y);
   if (any_lane(!fast)) {
     SDF_CRM_COLD();
@@ -229,7 +197,9 @@ __device__ __forceinline__ void div3_prepared(float& a0, float& a1, float& a2, f
   a1 = q1;
   a2 = q2;
 }
-// a / b for one division (the DE's, the shadow march's): computed as
+// a / b for one division (no kernel calls it: the DE's and the shadow
+// march's divisions measured no faster with it; kept
+// because tests/crmath/crmath_check.hip "div" exercises it): computed as
 // (sign(b) a) / |b| -- the same correctly rounded quotient (round to nearest
 // is symmetric), and with a positive divisor the two steps keep a zero
 // numerator's sign (with a negative one +0 / b would come out +0, not -0) --
@@ -276,7 +246,7 @@ __device__ __forceinline__ float div_scaled(float n, float k, float sc, float ys
 
 // The smooth-min's whole h = max(k - |e|, 0) / k (e = RN(a - b)) from the
 // same preparation, ksc = k sc (exact), in 4 instructions instead of 6
-// (round 6, tools/block_counts.py: the smooth-min was 12 VALU, ~400 per
+// (tools/block_counts.py: the smooth-min was 12 VALU, ~400 per
 // wave on C4):
 //   n' = clamp(RN(ksc - |e| sc), 0, 1): ONE FMA whose product |e| sc is exact,
 //        with the clamp bit for the max (n' <= ksc < 1, so the clamp's upper
@@ -301,53 +271,35 @@ __device__ __forceinline__ float smin_h(float e, float sc, float ksc, float ys) 
 // log(2) as a double (the rounding error, 2^-54 relative, times |e| <= 126
 // stays far below the fast path's error bound)
 #define SDF_CRM_LN2 0.693147180559945309417232121458
-// relative error bound of log_fast's double result.  Round 6
-// (SDF_CRM_LOG_SHORT 1): the series to s^7/15 and ONE Newton step for the
-// reciprocal -- truncation s^8/17 <= 2^-44.8 relative at |f| <= 0.1716, the
-// reciprocal 2^-46 (v_rcp_f64's 2^-23, squared), ~17 fp64 roundings each
-// <= 2^-52: a generous 2^-42 (a lane whose value lies that close to a float
-// rounding boundary, ~2^-17 of them, takes the library log; the exhaustive
-// check of all 2^32 inputs is the proof that the bound holds); three fp64 operations fewer per log
-// (tools/block_counts.py: cr_log was 9 % of C5 exact's VALU issue).  0: the
-// round-5 evaluation (s^8/17, two Newton steps, 2^-47)
-#ifndef SDF_CRM_LOG_SHORT
-#define SDF_CRM_LOG_SHORT 1
-#endif
-#if SDF_CRM_LOG_SHORT
+// relative error bound of log_fast's double result: the series to s^7/15 and
+// ONE Newton step for the reciprocal -- truncation s^8/17 <= 2^-44.8 relative
+// at |f| <= 0.1716, the reciprocal 2^-46 (v_rcp_f64's 2^-23, squared), ~17
+// fp64 roundings each <= 2^-52: a generous 2^-42 (a lane whose value lies
+// that close to a float rounding boundary, ~2^-17 of them, takes the library
+// log; the exhaustive check of all 2^32 inputs is the proof that the bound
+// holds); three fp64 operations fewer per log than the series to s^8/17 with
+// two Newton steps (tools/block_counts.py: cr_log was 9 % of C5 exact's VALU
+// issue)
 #define SDF_CRM_LOG_EPS 2.2737367544323206e-13
-#else
-#define SDF_CRM_LOG_EPS 7.105427357601002e-15
-#endif
 
 // p s + c as a three-address v_fma_f64 with the coefficient c in an SGPR
-// pair (SDF_CRM_FMA64 1).  With the builtin the compiler keeps the Horner
-// coefficients in VGPR pairs and picks the two-address v_fmac_f64, so every
-// step first copies its coefficient (v_mov_b64): 6 extra VALU per log and 14
-// VGPRs held.  Same operation, same rounding; C5 exact 2.0-2.5 % faster
-// (72 -> 68 VGPRs, profiles/r05_ab_log_fma64_C5.json).
-#ifndef SDF_CRM_FMA64
-#define SDF_CRM_FMA64 1
-#endif
+// pair.  With the builtin the compiler keeps the Horner coefficients in VGPR
+// pairs and picks the two-address v_fmac_f64, so every step first copies its
+// coefficient (v_mov_b64): 6 extra VALU per log and 14 VGPRs held.  Same
+// operation, same rounding; C5 exact 2.0-2.5 % faster (72 -> 68 VGPRs,
+// profiles/r05_ab_log_fma64_C5.json).
 __device__ __forceinline__ double fma64(double p, double s, double c) {
-#if SDF_CRM_FMA64
   double r;
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(p), "v"(s), "s"(c));
   return r;
-#else
-  return __builtin_fma(p, s, c);
-#endif
 }
 
 // The library fp64 log (the oracle's reading), out of line: only the rare
 // lanes near a rounding boundary call it, and its constants stay out of the
 // callers' loops (shade.h library_pow)
-#if !defined(SDF_CRM_LOG_CALL) || SDF_CRM_LOG_CALL
 inline __device__ __attribute__((noinline)) float library_log(float x) {
   return (float)log((double)x);
 }
-#else
-__device__ __forceinline__ float library_log(float x) { return (float)log((double)x); }
-#endif
 
 __device__ __forceinline__ double log_fast(float x) {
   // x = 2^e m, m in [sqrt(1/2), sqrt(2))
@@ -361,17 +313,9 @@ __device__ __forceinline__ double log_fast(float x) {
   const double d = m + 1.0;                              // exact
   double y = __builtin_amdgcn_rcp(d);                    // ~2^-23 relative
   y = __builtin_fma(__builtin_fma(-d, y, 1.0), y, y);    // ~2^-46
-#if !SDF_CRM_LOG_SHORT
-  y = __builtin_fma(__builtin_fma(-d, y, 1.0), y, y);    // ~2^-52
-#endif
   const double f = (m - 1.0) * y;                        // m - 1 exact
   const double s = f * f;
-#if SDF_CRM_LOG_SHORT
   double p = 1.0 / 15.0;
-#else
-  double p = 1.0 / 17.0;
-  p = fma64(p, s, 1.0 / 15.0);
-#endif
   p = fma64(p, s, 1.0 / 13.0);
   p = fma64(p, s, 1.0 / 11.0);
   p = fma64(p, s, 1.0 / 9.0);
@@ -384,60 +328,31 @@ __device__ __forceinline__ double log_fast(float x) {
 
 // Rounding v to float is safe when v's error interval [v - tol, v + tol],
 // tol = SDF_CRM_LOG_EPS |v|, holds no fp32 rounding midpoint (x a positive
-// normal float).  SDF_CRM_LOG_BITCHECK 1 (round 6) tests that on v's bits:
-// an fp32 midpoint is a double whose low 29 mantissa bits are 2^28, and tol
-// is below 2^11 of v's ulps (2^-42 |v| with |v| < 2 2^ev, ulp 2^(ev-52)), so
+// normal float).  log_round_ok tests that on v's bits: an fp32 midpoint is
+// a double whose low 29 mantissa bits are 2^28, and tol is below 2^11 of
+// v's ulps (2^-42 |v| with |v| < 2 2^ev, ulp 2^(ev-52)), so
 // v is safe when its low 29 bits differ from 2^28 by more than 2^11 -- two
 // integer VALU on the low dword instead of an fp64 multiply, two fp64 adds
 // and two conversions (at a power of two the interval may reach the next
 // binade, whose midpoints lie 2^-25 relative away: no midpoint either).  The
 // exhaustive GPU check of all 2^32 inputs (tests/crmath "log") covers both.
-#ifndef SDF_CRM_LOG_BITCHECK
-#define SDF_CRM_LOG_BITCHECK 1
-#endif
-__device__ __forceinline__ bool log_round_ok(float x, double v, float r) {
+__device__ __forceinline__ bool log_round_ok(float x, double v) {
   const bool normal = (__float_as_uint(x) - 0x00800000u) < (0x7F800000u - 0x00800000u);
-#if SDF_CRM_LOG_BITCHECK
   static_assert(SDF_CRM_LOG_EPS <= 0x1p-42, "tol must stay below 2^11 ulps of v");
-  (void)r;
   const uint32_t lo = (uint32_t)__builtin_bit_cast(unsigned long long, v);
   return normal & (((lo & 0x1FFFFFFFu) - (0x10000000u - 0x800u)) >= 0x1000u);
-#else
-  const double tol = SDF_CRM_LOG_EPS * __builtin_fabs(v);
-  return normal & ((float)(v - tol) == r) & ((float)(v + tol) == r);
-#endif
 }
 
 __device__ __forceinline__ float cr_log(float x) {
   const double v = log_fast(x);
   const float r = (float)v;
-  const bool ok = log_round_ok(x, v, r);
+  const bool ok = log_round_ok(x, v);
   float out = r;
   if (any_lane(!ok)) {
     SDF_CRM_COLD();
     out = ok ? r : library_log(x);
   }
   return out;
-}
-
-// N logs behind ONE guard (as cr_sqrt_n): each out[i] == cr_log(x[i])
-template <int N>
-__device__ __forceinline__ void cr_log_n(const float (&x)[N], float (&out)[N]) {
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    const double v = log_fast(x[i]);
-    out[i] = (float)v;
-    ok = ok & log_round_ok(x[i], v, out[i]);
-  }
-  if (any_lane(!ok)) {
-    SDF_CRM_COLD();
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-      const double v = log_fast(x[i]);
-      if (!log_round_ok(x[i], v, out[i])) out[i] = library_log(x[i]);
-    }
-  }
 }
 
 }  // namespace crm

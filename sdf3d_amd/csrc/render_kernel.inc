@@ -14,8 +14,7 @@
 // Mapping: one lane = one pixel; one wave64 = an 8x8 pixel tile (rays of a
 // tile are coherent, so the march loop's exec mask stays full longer and the
 // wave leaves the loop as soon as its last lane converges); a workgroup is
-// kWgWaves tiles side by side (kernel_args.h: one, since round 4).  Scene
-// constants come from
+// kWgWaves tiles side by side (kernel_args.h: one).  Scene constants come from
 // the kernel-argument segment with scalar loads.  The only HBM traffic is the
 // 16-byte float4 store per pixel (row-contiguous 128-byte segments per tile row).
 //
@@ -55,15 +54,6 @@
 #define SDF_WAVES_PER_EU 8
 #endif
 
-// Culling bounds in VGPRs (fast precision: its SGPRs hold the primitive
-// parameters) or as uniform kernel-argument values (exact precision: its
-// longer sequences need the VGPRs -- with the bounds in them the CSG8 kernel
-// spilled 68 bytes per lane at 8 waves, 170 MB of scratch writes per 4K
-// launch; without, none, and C3/C4 exact run 1-21 % faster).
-#ifndef SDF_BOUNDS_VGPR
-#define SDF_BOUNDS_VGPR (!SDF_EXACT)
-#endif
-
 // Stage ablation (tools/ablate.py): 1 skips the normal's taps, so a frame's
 // time splits into primary march, normal, AO and shadow.  Experiment builds
 // only (tools/flag_variant.py defines SDF_EXPERIMENT).
@@ -95,6 +85,13 @@ namespace SDF_NS {
 #define KARG __attribute__((address_space(4)))
 typedef const KARG KernelArgs KA;
 typedef const KARG float* KF;
+
+// Culling bounds in VGPRs (fast precision: its SGPRs hold the primitive
+// parameters) or as uniform kernel-argument values (exact precision: its
+// longer sequences need the VGPRs -- with the bounds in them the CSG8 kernel
+// spilled 68 bytes per lane at 8 waves, 170 MB of scratch writes per 4K
+// launch; without, none, and C3/C4 exact run 1-21 % faster).
+constexpr bool kBoundsInVgprs = !SDF_EXACT;
 
 struct V3 {
   float x, y, z;
@@ -156,45 +153,20 @@ __device__ __forceinline__ float flog(float x) { return crm::cr_log(x); }
 // Exact precision's divisions by Markstein's steps instead of the IEEE
 // sequence (v_div_scale x2, v_rcp, 5 fma, v_div_fmas / v_div_fixup through
 // VCC): correctly rounded, proven in cr_math.h, guarded to their domain.
-//   NORMDIV  normalize's three divisions, one shared reciprocal (div3):
-//            C4 exact 2.8-2.9 % faster than without, C5 1.3 %
-//   BULBDIV  the Mandelbulb's (p - c) / scale from the host's RN(1/scale),
-//            three divisions per DE evaluation: C5 exact 10-11 % faster
-//   DEDIV    the DE's final division by dz (div_one): +-0.5 %, not kept
-//   SHDIV    the shadow march's h^2 / (2 h_prev) (div_one): C4 exact 1 %
-//            slower, C5 +-0.7 %, not kept
-// (all bit-exact at 4K, profiles/r05_ab_exact_C4.json, r05_ab_divisions_C5.json)
-#ifndef SDF_EXACT_NORMDIV
-#define SDF_EXACT_NORMDIV 1
-#endif
-#ifndef SDF_EXACT_BULBDIV
-#define SDF_EXACT_BULBDIV 1
-#endif
-#ifndef SDF_EXACT_DEDIV
-#define SDF_EXACT_DEDIV 0
-#endif
-#ifndef SDF_EXACT_SHDIV
-#define SDF_EXACT_SHDIV 0
-#endif
-//   SHSKIP   (round 6) the shadow term formed exactly only on steps where a
-//            division-free lower bound cannot show that it leaves s alone
-//            (shade_pixel's shadow march)
-#ifndef SDF_EXACT_SHSKIP
-#define SDF_EXACT_SHSKIP 1
-#endif
-//   QDIV     the pixel's quad coordinates (2x+1)/W, (2y+1)/H (div_refined
-//            with the host's RN(1/W), no guard: integers in range)
-#ifndef SDF_EXACT_QDIV
-#define SDF_EXACT_QDIV 1
-#endif
+//   normalize's three divisions, one shared reciprocal (div3): C4 exact
+//     2.8-2.9 % faster than without, C5 1.3 %
+//   the Mandelbulb's (p - c) / scale from the host's RN(1/scale), three
+//     divisions per DE evaluation (BulbScene::local): C5 exact 10-11 % faster
+//   the pixel's quad coordinates (2x+1)/W, (2y+1)/H (div_refined with the
+//     host's RN(1/W), no guard: integers in range)
+//   the capsule's h (sd_capsule) and the smooth-min's h (smin)
+// (all bit-exact at 4K, profiles/r05_ab_exact_C4.json, r05_ab_divisions_C5.json).
+// The DE's final division by dz and the shadow march's h^2 / (2 h_prev) stay
+// IEEE: div_one measured no faster there (DESIGN.md Appendix A).
 __device__ __forceinline__ V3 normalize(V3 a) {
   float l = fsqrt(dot(a, a));
-#if SDF_EXACT_NORMDIV
   crm::div3(a.x, a.y, a.z, l);
   return a;
-#else
-  return mk(a.x / l, a.y / l, a.z / l);
-#endif
 }
 #else
 // Hardware min/max (differ from the GLSL select only for a NaN first
@@ -217,7 +189,7 @@ __device__ __forceinline__ float gclamp(float x, float a, float b) { return gmin
 
 // min / max inside the primitive SDFs (box, round box, cylinder, the
 // capsule's clamp).  Exact precision: the hardware v_max_f32 / v_min_f32 /
-// v_max3_f32 equal the GLSL select there (SDF_EXACT_PRIMMM 1): no operand is
+// v_max3_f32 equal the GLSL select there: no operand is
 // NaN (sdf_validate's working range keeps every coordinate, square and
 // distance finite) and none is -0 -- |v| - b and sqrt(.) - r are never -0
 // (x - y = -0 needs x = -0), and a max of such values is one of them -- so
@@ -226,12 +198,6 @@ __device__ __forceinline__ float gclamp(float x, float a, float b) { return gmin
 // keeps -0 where the hardware gives +0, and h only enters pa - ba h, whose
 // components are then +-0 alike and square to +0: the same length.
 #if SDF_EXACT
-#ifndef SDF_EXACT_PRIMMM
-#define SDF_EXACT_PRIMMM 1
-#endif
-#ifndef SDF_EXACT_HEADMIN
-#define SDF_EXACT_HEADMIN 1
-#endif
 __device__ __forceinline__ float hw_max(float x, float y) {
   float r;
   asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
@@ -247,15 +213,9 @@ __device__ __forceinline__ float hw_max3(float x, float y, float z) {
   asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(z));
   return r;
 }
-#if SDF_EXACT_PRIMMM
 __device__ __forceinline__ float pmax(float x, float y) { return hw_max(x, y); }
 __device__ __forceinline__ float pmin(float x, float y) { return hw_min(x, y); }
 __device__ __forceinline__ float pmax3(float x, float y, float z) { return hw_max3(x, y, z); }
-#else
-__device__ __forceinline__ float pmax(float x, float y) { return gmax(x, y); }
-__device__ __forceinline__ float pmin(float x, float y) { return gmin(x, y); }
-__device__ __forceinline__ float pmax3(float x, float y, float z) { return gmax(x, gmax(y, z)); }
-#endif
 #else
 __device__ __forceinline__ float pmax(float x, float y) { return gmax(x, y); }
 __device__ __forceinline__ float pmin(float x, float y) { return gmin(x, y); }
@@ -270,6 +230,7 @@ __device__ __forceinline__ float length(V3 a) { return fsqrt(dot(a, a)); }
 // call (b - r, b - a, dot(ba, ba)), so exact precision stays bit-identical.
 // Q is a kernarg pointer (generic kernel) or a register array (fixed scenes).
 
+// x / d with the host's 1 / d beside it (grad_kernel.inc's capsule)
 #if SDF_EXACT
 #define DIVK(x, d, inv) ((x) / (d))
 #else
@@ -321,27 +282,23 @@ __device__ __forceinline__ float sd_torus(V3 p, const Q& q) {
 }
 // a.xyz, (b - a).xyz, r, dot(ba, ba), 1 / dot(ba, ba)
 //
-// SDF_EXACT_CAPDIV 1 (round 6, exact precision): h = clamp(dot(pa, ba) /
-// dot(ba, ba), 0, 1) as the quotient of the CLAMPED numerator med3(n, 0, b)
-// by cr_math.h div_refined (the host's RN(1/b), two Markstein steps) instead
-// of the IEEE division (11 VALU, a v_rcp among them) and the clamp: 8 VALU.
+// Exact precision: h = clamp(dot(pa, ba) / dot(ba, ba), 0, 1) as the
+// quotient of the CLAMPED numerator med3(n, 0, b) by cr_math.h div_refined
+// (the host's RN(1/b), one Markstein step: the proof is at div_refined)
+// instead of the IEEE division (11 VALU, a v_rcp among them) and the clamp.
 // The same bits: for n <= 0 both give +0 (the capsule's pa - ba h squares a
 // -0 alike, see pmax); for 0 < n < b the quotient is RN(n/b) either way and
 // lies in (0, 1]; for n >= b both give RN(b/b) = 1.  div_refined's domain:
 // b = dot(ba, ba) in [2^-30, 2^30) -- sdf_validate's capsule length range
 // [2^-15, 2^15) -- and a numerator 0 or >= 2^-60 (lanes with a smaller one
 // take the IEEE path).  tools/block_counts.py: 9 capsule evaluations per
-// wave on C4.
-#if SDF_EXACT && !defined(SDF_EXACT_CAPDIV)
-#define SDF_EXACT_CAPDIV 1
-#endif
+// wave on C4.  Fast precision multiplies by the host's 1 / dot(ba, ba).
 template <class Q>
 __device__ __forceinline__ float sd_capsule(V3 p, const Q& q) {
   V3 pa = sub(p, mk(q[0], q[1], q[2]));
   V3 ba = mk(q[3], q[4], q[5]);
 #if SDF_EXACT
   const float n = dot(pa, ba);
-#if SDF_EXACT_CAPDIV
   const float a = __builtin_amdgcn_fmed3f(n, 0.0f, q[7]);
   float h = crm::div_refined(a, q[7], q[8]);
   const bool ok = (__float_as_uint(a) << 1) - 1u >= (0x21800000u << 1) - 1u;
@@ -350,10 +307,7 @@ __device__ __forceinline__ float sd_capsule(V3 p, const Q& q) {
     if (!ok) h = pmin(pmax(n / q[7], 0.0f), 1.0f);
   }
 #else
-  const float h = pmin(pmax(n / q[7], 0.0f), 1.0f);
-#endif
-#else
-  float h = pmin(pmax(DIVK(dot(pa, ba), q[7], q[8]), 0.0f), 1.0f);
+  float h = pmin(pmax(dot(pa, ba) * q[8], 0.0f), 1.0f);
 #endif
   return length(sub(pa, muls(ba, h))) - q[6];
 }
@@ -381,18 +335,9 @@ __device__ __forceinline__ float sd_cylinder(V3 p, const Q& q) {
 // select: operands never NaN (or NaN only where the select keeps the other
 // operand too) and never the (+0, -0) pair the select orders differently
 // (the hardware's answers on the pairs relied on: tests/test_gpu_crmath.py
-// minmax).  Round 4: the smooth-min's max and min and the shadow march's
-// max / min, C4 exact 0.8-1.4 % faster at 3 poses, bit-identical
-// (profiles/r04_ab_minmax_exact_C4.json); 0 turns them off (A/B).
-#ifndef SDF_EXACT_SMAX
-#define SDF_EXACT_SMAX 1
-#endif
-#ifndef SDF_EXACT_SMIN
-#define SDF_EXACT_SMIN 1
-#endif
-#ifndef SDF_EXACT_SHMM
-#define SDF_EXACT_SHMM 1
-#endif
+// minmax).  They serve the smooth-min's max and min and the shadow march's
+// max / min: C4 exact 0.8-1.4 % faster at 3 poses, bit-identical
+// (profiles/r04_ab_minmax_exact_C4.json).
 // h = max(k - |a-b|, 0) / k by cr_math.h div_scaled (`ik` = RN(1/(k sc)),
 // `sc` = 2^s, prepared by the host in p[10], p[9]): 4 instructions instead of
 // the IEEE sequence's 11, and the same result bit for bit (h*h is what
@@ -400,7 +345,7 @@ __device__ __forceinline__ float sd_cylinder(V3 p, const Q& q) {
 // HW: b is a primitive value that is never -0 (every kind but the plane:
 // length(.) - r, box, torus, capsule, cylinder), so the hardware minimum
 // (-0 below +0, tests/test_gpu_crmath.py) equals the select gmin(a, b)
-// Round 6: h by cr_math.h smin_h -- the subtraction, the max and the scaling
+// h by cr_math.h smin_h -- the subtraction, the max and the scaling
 // as one clamped FMA -- and the product h h k 0.25 as h h (k/4) with the
 // host's exact k/4: 9 VALU per smooth union instead of 12 (tools/
 // block_counts.py), bit-identical.  The second rests on sdf_validate's
@@ -412,7 +357,7 @@ __device__ __forceinline__ float sd_cylinder(V3 p, const Q& q) {
 template <bool HW = false>
 __device__ __forceinline__ float smin(float a, float b, float k4, float ik, float sc, float ksc) {
   const float h = crm::smin_h(a - b, sc, ksc, ik);
-  if constexpr (HW && SDF_EXACT_SMIN) return hw_min(a, b) - h * h * k4;
+  if constexpr (HW) return hw_min(a, b) - h * h * k4;
   return gmin(a, b) - h * h * k4;
 }
 #else
@@ -528,33 +473,24 @@ __device__ __forceinline__ bool owner_step(int op, float d, float v) {
 
 // Power-8 Mandelbulb DE, trig-free polynomial form (DESIGN.md Scene spec).
 #if SDF_EXACT
-// Measured and not kept (round 4, profiles/r04_ab_bulb_exact_C5.json, code
-// in git history): the map's independent products paired into v_pk_mul_f32
-// (+3.7 %), max(x2 + z2, 1e-30) as v_max_f32 (+2 %), 1/sqrt(k3) without the
-// sqrt guard its proven domain allows (+1 %) -- all bit-identical, all slower
-// (commit 602e5af has them as SDF_BULB_PK / _VMAX / _NOGUARD).
+// Measured and not kept (profiles/r04_ab_bulb_exact_C5.json, code in git
+// history): the map's independent products paired into v_pk_mul_f32
+// (+3.7 %), 1/sqrt(k3) without the sqrt guard its proven domain allows
+// (+1 %) -- bit-identical, slower (commit 602e5af has them as SDF_BULB_PK /
+// _NOGUARD).  max(x2 + z2, 1e-30) as v_max_f32 measured +2 % on the kernel
+// of then; on this one C5 exact is 0.1-2.1 % faster with it at three poses,
+// with cr_math.h div3_prepared's min3 guard
+// (profiles/r06_ab_bulb_min3_k3max.json).
 //
-// SDF_BULB_K3MAX 1 (round 6; round 4 measured it +2 % on the kernel of
-// then): C5 exact 0.1-2.1 % faster at three poses with the min3 guard below
-// (profiles/r06_ab_bulb_min3_k3max.json)
-#ifndef SDF_BULB_K3MAX
-#define SDF_BULB_K3MAX 1
-#endif
-// One iteration is split around its two square roots (bulb_roots: the
-// arguments; bulb_map: the rest, given sqrt(m^7) and sqrt(k3)), so that a
-// batch of independent orbits (BulbScene::taps) can take all its roots with
-// ONE slow-path guard (cr_sqrt_n) and keep the orbits in one basic block.
+// One iteration around its two square roots: bulb_roots forms their
+// arguments, bulb_map the rest, given sqrt(m^7) and sqrt(k3).
 __device__ __forceinline__ void bulb_roots(const V3& w, float m, float& a7, float& k3) {
   const float m2 = m * m;
   const float m4 = m2 * m2;
   a7 = m4 * m2 * m;
-#if SDF_BULB_K3MAX
   // v_max_f32: the GLSL select max(x, 1e-30) for x = x^2 + z^2, which is
   // never NaN or -0 (w is finite at the start of an iteration)
   k3 = __builtin_fmaxf(w.x * w.x + w.z * w.z, 1e-30f);
-#else
-  k3 = gmax(w.x * w.x + w.z * w.z, 1e-30f);
-#endif
 }
 __device__ __forceinline__ void bulb_map(const V3& q, V3& w, float& m, float& dz, float s7,
                                          float k3, float sk3) {
@@ -577,34 +513,14 @@ __device__ __forceinline__ void bulb_map(const V3& q, V3& w, float& m, float& dz
                    28.0f * xn2 * zn2 * zn4 + zn4 * zn4) * s;
   m = dot(w, w);
 }
-// SDF_EXACT_K3FAST: sqrt(k3) by cr_math.h's fast path without its guard.
-// Its domain holds there: k3 = max(x^2 + z^2, 1e-30) >= 1e-30 > 2^-100, and
-// k3 <= m(1 + 2^-22) <= bailout^2 (1 + 2^-22) <= 2^65 < 2^100 at the start of
-// every iteration (the orbit continues only while m <= bailout^2, bailout <=
-// 2^32 by sdf_validate; the first starts from |q|^2 <= 2.25).
-#ifndef SDF_EXACT_K3FAST
-#define SDF_EXACT_K3FAST 0
-#endif
+// sqrt(k3) keeps cr_sqrt's guard although its domain holds there (k3 in
+// [1e-30, 2^65]): without it the kernel measured slower (DESIGN.md
+// Appendix A).
 __device__ __forceinline__ void bulb_step(const V3& q, V3& w, float& m, float& dz) {
   float a7, k3;
   bulb_roots(w, m, a7, k3);
   const float s7 = fsqrt(a7);
-#if SDF_EXACT_K3FAST
-  bulb_map(q, w, m, dz, s7, k3, crm::sqrt_fast(k3));
-#else
   bulb_map(q, w, m, dz, s7, k3, fsqrt(k3));
-#endif
-}
-// the DE from the orbit's last state
-__device__ __forceinline__ float de_div(float a, float dz) {
-#if SDF_EXACT_DEDIV
-  return crm::div_one(a, dz);
-#else
-  return fdiv(a, dz);
-#endif
-}
-__device__ __forceinline__ float bulb_de(float m, float dz) {
-  return de_div(0.25f * flog(m) * fsqrt(m), dz);
 }
 #else
 // The same map with cheaper identities (fast precision: a different rounding
@@ -634,10 +550,11 @@ __device__ __forceinline__ void bulb_step(const V3& q, V3& w, float& m, float& d
   w.z = fmaf(-ys, a, q.z);
   m = dot(w, w);
 }
+#endif
+// the DE from the orbit's last state
 __device__ __forceinline__ float bulb_de(float m, float dz) {
   return fdiv(0.25f * flog(m) * fsqrt(m), dz);
 }
-#endif
 __device__ __forceinline__ float mandelbulb(V3 q, int iters, float bail2) {
   V3 w = q;
   float m = dot(w, w);
@@ -647,78 +564,6 @@ __device__ __forceinline__ float mandelbulb(V3 q, int iters, float bail2) {
     if (m > bail2) break;
   }
   return bulb_de(m, dz);
-}
-
-// G independent orbits of the map in lockstep (BulbScene::taps: the normal's
-// and the AO's taps of one pixel), each with exactly the operation sequence
-// of mandelbulb(): while every orbit of the lane is running they iterate
-// together in one basic block (their square roots behind one slow-path guard
-// in exact precision), so the dependent chain of one orbit overlaps the
-// others'; from the first iteration after which one of them has escaped,
-// each remaining orbit finishes on its own.  `run[j]` false: orbit j is not
-// wanted (its DE is not used).
-#if SDF_EXACT
-template <int G>
-__device__ __forceinline__ void bulb_steps(const V3 (&q)[G], V3 (&w)[G], float (&m)[G],
-                                           float (&dz)[G]) {
-  float a[2 * G], s[2 * G];
-#pragma unroll
-  for (int j = 0; j < G; j++) bulb_roots(w[j], m[j], a[2 * j], a[2 * j + 1]);
-  crm::cr_sqrt_n<2 * G>(a, s);
-#pragma unroll
-  for (int j = 0; j < G; j++) bulb_map(q[j], w[j], m[j], dz[j], s[2 * j], a[2 * j + 1], s[2 * j + 1]);
-}
-#else
-template <int G>
-__device__ __forceinline__ void bulb_steps(const V3 (&q)[G], V3 (&w)[G], float (&m)[G],
-                                           float (&dz)[G]) {
-#pragma unroll
-  for (int j = 0; j < G; j++) bulb_step(q[j], w[j], m[j], dz[j]);
-}
-#endif
-template <int G>
-__device__ __forceinline__ void mandelbulb_n(const V3 (&q)[G], const bool (&run)[G], int iters,
-                                             float bail2, float (&de)[G]) {
-  V3 w[G];
-  float m[G], dz[G];
-  bool all = true;
-#pragma unroll
-  for (int j = 0; j < G; j++) {
-    w[j] = q[j];
-    m[j] = dot(w[j], w[j]);
-    dz[j] = 1.0f;
-    all = all && run[j];
-  }
-  int i = 0;
-  if (all) {
-    for (; i < iters;) {
-      bulb_steps<G>(q, w, m, dz);
-      i++;
-      bool out = false;
-#pragma unroll
-      for (int j = 0; j < G; j++) out = out || m[j] > bail2;
-      if (out) break;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < G; j++) {
-    if (run[j] && (i == 0 || !(m[j] > bail2))) {
-      for (int ii = i; ii < iters; ii++) {
-        bulb_step(q[j], w[j], m[j], dz[j]);
-        if (m[j] > bail2) break;
-      }
-    }
-  }
-#if SDF_EXACT
-  float lg[G], sq[G];
-  crm::cr_log_n<G>(m, lg);
-  crm::cr_sqrt_n<G>(m, sq);
-#pragma unroll
-  for (int j = 0; j < G; j++) de[j] = de_div(0.25f * lg[j] * sq[j], dz[j]);
-#else
-#pragma unroll
-  for (int j = 0; j < G; j++) de[j] = bulb_de(m[j], dz[j]);
-#endif
 }
 
 // ---- framebuffer formats (sdf_abi.h sdf_format) ----------------------------
@@ -1061,12 +906,9 @@ __device__ __forceinline__ void sdf_stat(int i) {
 // VALU fewer per test); a sphere's own bound keeps the plain sum, which its
 // SDF computes too (one computation for both).  Fast precision contracts
 // either form by itself.
-#ifndef SDF_CULL_FMA
-#define SDF_CULL_FMA 1
-#endif
 template <bool FUSE>
 __device__ __forceinline__ float cull_dist2(float dx, float dy, float dz) {
-  if constexpr (FUSE && SDF_EXACT && SDF_CULL_FMA)
+  if constexpr (FUSE && SDF_EXACT)
     return __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));
   else
     return dx * dx + dy * dy + dz * dz;
@@ -1212,13 +1054,6 @@ __device__ __forceinline__ float prim_ct(V3 p, const Q& q) {
 // skips work only when every active lane of the wave passes it (wave-uniform
 // branch), and a skipped primitive would have left d unchanged bit for bit,
 // so results and step counts equal the unculled evaluation.
-// FixedScene::apply: skip a smooth union that cannot change d (bit 0: march
-// steps, bit 1: batched taps).  Measured and not kept: C4 exact 0.5-1.4 %
-// faster, C3 exact 1.3-2.2 % and C4 fast 1.4 % slower
-// (profiles/r05_ab_sqrt_guard_C4.json)
-#ifndef SDF_SMIN_SKIP
-#define SDF_SMIN_SKIP 0
-#endif
 template <int... KO>
 struct FixedScene {
   static constexpr int N = sizeof...(KO);
@@ -1232,7 +1067,7 @@ struct FixedScene {
   static constexpr bool kBatchedTaps = true;
   float q[N][9];
   float k[N], ik[N], sc[N], ksc[N];
-  float kg[N];   // exact, cullable primitives: the own-value gap's offset (SDF_CULL_SGAP)
+  float kg[N];   // exact, cullable primitives: the own-value gap's offset (step_cached)
   float b[N][4];  // bound: centre (read only for capsules; the others use q[i][0..2]), K
   float cl[4];
   __device__ __forceinline__ explicit FixedScene(KA& A) {
@@ -1253,9 +1088,9 @@ struct FixedScene {
       kg[i] = A.prims[i].reserved;
     }
     // bounds are read rarely (cached gaps): VGPRs, loaded as float4 vectors
-    // (SDF_BOUNDS_VGPR 0: uniform kernel-argument values, which the compiler
-    // keeps in SGPRs or reloads with scalar loads)
-    const int vz = SDF_BOUNDS_VGPR ? lane_zero() : 0;
+    // (exact precision, kBoundsInVgprs false: uniform kernel-argument values,
+    // which the compiler keeps in SGPRs or reloads with scalar loads)
+    const int vz = kBoundsInVgprs ? lane_zero() : 0;
 #pragma unroll
     for (int i = kFirst; i < N; i++) {
 #pragma unroll
@@ -1264,24 +1099,10 @@ struct FixedScene {
 #pragma unroll
     for (int j = 0; j < 4; j++) cl[j] = A.cluster[vz * 4 + j];
   }
-  // d combined with the primitive value v.  SDF_SMIN_SKIP (bit 0: march
-  // steps, bit 1: the batched taps): a smooth union whose v exceeds d by at
-  // least k on every active lane is skipped (wave-uniform) -- its h is 0 there
-  // and the smooth-min returns d bit for bit: exact precision h = max(k -
-  // |d - v|, 0) / k = +0 for RN(d - v) <= -k, and min(d, v) - (+0) = d as v
-  // > d; fast precision the same with its clamped FMA fma(-|d - v|, 1/k, 1)
-  // <= 0 (d - v <= 0 there, so -|d - v| = d - v).
-  template <int I, int WHERE>
+  // d combined with the primitive value v
+  template <int I>
   __device__ __forceinline__ float apply(float d, float v) const {
     constexpr int ko = kKO[I];
-    if constexpr ((SDF_SMIN_SKIP & WHERE) != 0 && (ko & 7) == SDF_OP_SMOOTH_UNION) {
-#if SDF_EXACT
-      const bool same = d - v <= -4.0f * k[I];   // k[I] = k/4
-#else
-      const bool same = __builtin_fmaf(d - v, ik[I], 1.0f) <= 0.0f;
-#endif
-      if (__builtin_amdgcn_ballot_w64(!same) == 0) return d;
-    }
     return combine<no_neg_zero(ko >> 3)>(ko & 7, d, v, k[I], ik[I], sc[I], ksc[I]);
   }
   template <int I>
@@ -1294,7 +1115,7 @@ struct FixedScene {
       const float cz = cap ? b[I][2] : q[I][2];
       if (!wave_near<(ko >> 3) != SDF_PRIM_SPHERE>(cx, cy, cz, b[I][3], p, d)) return d;
     }
-    return apply<I, 1>(d, prim_ct<(ko >> 3)>(p, q[I]));
+    return apply<I>(d, prim_ct<(ko >> 3)>(p, q[I]));
   }
   template <int... I>
   __device__ __forceinline__ float prefix(float d, V3 p, Seq<I...>) const {
@@ -1303,14 +1124,12 @@ struct FixedScene {
   }
   // the accumulator before the cullable suffix, from d = INF (:75)
   __device__ __forceinline__ float head(V3 p) const {
-#if !SDF_EXACT || SDF_EXACT_HEADMIN
     // min(INF, v) = v for every non-NaN v: start from the first primitive.
-    // Exact precision too (SDF_EXACT_HEADMIN): the GLSL select min(INF, v)
-    // differs only for a NaN v, and sdf_validate's working range keeps every
-    // primitive value finite
+    // Exact precision too: the GLSL select min(INF, v) differs only for a
+    // NaN v, and sdf_validate's working range keeps every primitive value
+    // finite
     if constexpr (kFirst > 0 && (kKO[0] & 7) == SDF_OP_UNION)
       return prefix(prim_ct<(kKO[0] >> 3)>(p, q[0]), p, MakeSeq<N>{}, 1);
-#endif
     return prefix(INFINITY, p, MakeSeq<N>{});
   }
   template <int... I>
@@ -1325,23 +1144,15 @@ struct FixedScene {
   }
   // step<I> with the primitive's bound gap cached along the march (see march)
   // (dt = d + t: the cached test pg - t >= d as pg >= dt, one compare per
-  // primitive, refreshed when a primitive changes d).  SDF_CULL_PGTEST 1
-  // (round 6): a fresh test is the cached test of the gap it has just stored
-  // (pg >= dt, the same comparison at t - t_c = 0, so valid by the same
-  // margins) instead of g >= d / (1 - kCullRel): no second accumulator ds to
-  // keep (one multiply fewer per evaluated primitive and per visit of the
-  // suffix); 0: the round-5 form
-#ifndef SDF_CULL_PGTEST
-#define SDF_CULL_PGTEST 1
-#endif
-// SDF_CULL_SGAP 1 (round 6, exact precision): an evaluated primitive's cached
-// gap comes from its own value instead of its bounding sphere
-#ifndef SDF_CULL_SGAP
-#define SDF_CULL_SGAP 1
-#endif
-
+  // primitive, refreshed when a primitive changes d).  A fresh test is the
+  // cached test of the gap it has just stored (pg >= dt, the same comparison
+  // at t - t_c = 0, so valid by the same margins) instead of g >= d / (1 -
+  // kCullRel): no second accumulator d / (1 - kCullRel) to keep (one multiply
+  // fewer per evaluated primitive and per visit of the suffix).  Exact
+  // precision: an evaluated primitive's cached gap comes from its own value
+  // instead of its bounding sphere.
   template <int I>
-  __device__ __forceinline__ float step_cached(float d, V3 p, float t, float& dt, float& ds,
+  __device__ __forceinline__ float step_cached(float d, V3 p, float t, float& dt,
                                                MarchState& st) const {
     constexpr int ko = kKO[I];
     constexpr int slot = I - kFirst;
@@ -1358,15 +1169,11 @@ struct FixedScene {
       const float g =
           __builtin_amdgcn_sqrtf(cull_dist2<(ko >> 3) != SDF_PRIM_SPHERE>(dx, dy, dz)) - b[I][3];
       st.pg[slot] = fmaf(g, 1.0f - kCullRel, t);
-#if SDF_CULL_PGTEST
       if (__builtin_amdgcn_ballot_w64(!(st.pg[slot] >= dt)) == 0) return d;
-#else
-      if (__builtin_amdgcn_ballot_w64(!(g >= ds)) == 0) return d;
-#endif
       STAT(st, 20 + slot);
       const float v = prim_ct<(ko >> 3)>(p, q[I]);
-      d = apply<I, 1>(d, v);
-#if SDF_EXACT && SDF_CULL_SGAP
+      d = apply<I>(d, v);
+#if SDF_EXACT
       // the evaluated primitive's own value bounds its values along the rest
       // of the path (an exact SDF is 1-Lipschitz): its gap v - (k + margin)
       // replaces the bounding sphere's, which is never larger.  The margin
@@ -1376,20 +1183,17 @@ struct FixedScene {
       st.pg[slot] = fmaf(v - kg[I], 1.0f - kCullRel, t);
 #endif
       dt = d + t;
-      if (!SDF_CULL_PGTEST) ds = d * kCullScale;
       return d;
     } else {
       d = step<I>(d, p);
       dt = d + t;
-      if (!SDF_CULL_PGTEST) ds = d * kCullScale;
       return d;
     }
   }
   template <int... I>
   __device__ __forceinline__ float suffix_cached(float d, V3 p, float t, float dt, MarchState& st,
                                                  Seq<I...>) const {
-    float ds = SDF_CULL_PGTEST ? 0.0f : d * kCullScale;
-    ((d = I >= kFirst ? step_cached<I>(d, p, t, dt, ds, st) : d), ...);
+    ((d = I >= kFirst ? step_cached<I>(d, p, t, dt, st) : d), ...);
     return d;
   }
   __device__ __forceinline__ float eval(V3 p) const {
@@ -1408,7 +1212,7 @@ struct FixedScene {
     constexpr int ko = kKO[I];
     const float v = prim_ct<(ko >> 3)>(p, q[I]);
     material_step(ko & 7, d, v, k[I], ik[I], M.m[I], m);
-    d = apply<I, 0>(d, v);
+    d = apply<I>(d, v);
   }
   template <int... I>
   __device__ __forceinline__ void material_fold_seq(V3 p, const KARG MaterialArgs& M,
@@ -1427,7 +1231,7 @@ struct FixedScene {
     constexpr int ko = kKO[I];
     const float v = prim_ct<(ko >> 3)>(p, q[I]);
     if (owner_step(ko & 7, d, v)) w = I;
-    d = apply<I, 0>(d, v);
+    d = apply<I>(d, v);
   }
   template <int... I>
   __device__ __forceinline__ int owner_fold_seq(V3 p, Seq<I...>) const {
@@ -1453,29 +1257,17 @@ struct FixedScene {
   // the primitives are tested directly.  This only ever forgoes a skip, so it
   // needs no rounding margin.
   //
-  // SDF_CULL_DT 1 (round 6): the cluster's cached test as gt >= dt, dt = d + t
-  // -- the primitives' form (pg >= dt), with dt then handed to them instead
-  // of being formed again; 0: gt - t >= d (round 5)
-#ifndef SDF_CULL_DT
-#define SDF_CULL_DT 1
-#endif
-// SDF_MARCH_DTFMA 1 (round 6): C4 exact 0.3-0.4 % faster at three poses,
-// bit-identical (profiles/r06_ab_dtfma_evalskip.json)
-#ifndef SDF_MARCH_DTFMA
-#define SDF_MARCH_DTFMA 1
-#endif
+  // The cluster's cached test is gt >= dt, dt = d + t -- the primitives' form
+  // (pg >= dt), with dt then handed to them instead of being formed again.
   __device__ __forceinline__ float march(V3 p, float t, MarchState& st) const {
     return march_at<false>(p, t, st);
   }
   // the primary ray's evaluation at ray distance r (path length r kPathScale):
-  // SDF_MARCH_DTFMA 1 forms dt = d + r kPathScale with one FMA, and the path
-  // length itself only where a gap is stored (the cached tests need only dt)
+  // forms dt = d + r kPathScale with one FMA, and the path length itself only
+  // where a gap is stored (the cached tests need only dt): C4 exact 0.3-0.4 %
+  // faster at three poses, bit-identical (profiles/r06_ab_dtfma_evalskip.json)
   __device__ __forceinline__ float march_primary(V3 p, float r, MarchState& st) const {
-#if SDF_MARCH_DTFMA
     return march_at<true>(p, r, st);
-#else
-    return march_at<false>(p, r * kPathScale, st);
-#endif
   }
   template <bool LIN>
   __device__ __forceinline__ float march_at(V3 p, float tr, MarchState& st) const {
@@ -1484,7 +1276,7 @@ struct FixedScene {
     if constexpr (kFirst < N) {
       const float t = LIN ? tr * kPathScale : tr;
       const float dt = LIN ? fmaf(tr, kPathScale, d) : d + t;
-      if (__builtin_amdgcn_ballot_w64(SDF_CULL_DT ? !(st.gt >= dt) : !(st.gt - t >= d)) != 0) {
+      if (__builtin_amdgcn_ballot_w64(!(st.gt >= dt)) != 0) {
         if (__builtin_amdgcn_ballot_w64(st.gu + t < d) == 0) {
           STAT(st, 2);
           const float dx = p.x - cl[0], dy = p.y - cl[1], dz = p.z - cl[2];
@@ -1548,7 +1340,7 @@ struct FixedScene {
     if constexpr (I >= kFirst) {
       if constexpr (slot < kMaxCached) STAT(st, 20 + slot);
 #pragma unroll
-      for (int j = 0; j < T::K; j++) f[j] = apply<I, 2>(f[j], prim_ct<(ko >> 3)>(tap(j), q[I]));
+      for (int j = 0; j < T::K; j++) f[j] = apply<I>(f[j], prim_ct<(ko >> 3)>(tap(j), q[I]));
       dt = max_of<T>(f) + tt;
     }
   }
@@ -1687,13 +1479,10 @@ __device__ __forceinline__ void normal_taps(const Scene& scene, const T& tap, fl
   }
 }
 
-// Orbits per lockstep group of the Mandelbulb's normal and AO taps
-// (mandelbulb_n); 1: one tap after another (scene.march per tap).
-#ifndef SDF_BULB_GROUP
-#define SDF_BULB_GROUP 1
-#endif
+// The Mandelbulb's normal and AO taps go one after another (scene.march per
+// tap): lockstep groups of orbits measured slower (DESIGN.md Appendix A).
 struct BulbScene {
-  static constexpr bool kBatchedTaps = SDF_BULB_GROUP > 1;
+  static constexpr bool kBatchedTaps = false;
   static constexpr bool kPlaneHead = false;
   float c0, c1, c2, sc, isc, bail2;
   int iters;
@@ -1703,7 +1492,7 @@ struct BulbScene {
   __device__ __forceinline__ float march(V3 p, float, MarchState&) const { return eval(p); }
   __device__ __forceinline__ float march_primary(V3 p, float, MarchState&) const { return eval(p); }
   __device__ __forceinline__ V3 local(V3 p) const {
-#if SDF_EXACT && SDF_EXACT_BULBDIV
+#if SDF_EXACT
     // (p - c) / scale by Markstein's steps from the host's RN(1/scale), for a
     // scale in [2^-30, 2^30) (a wave-uniform test; the IEEE division else)
     float a0 = p.x - c0, a1 = p.y - c1, a2 = p.z - c2;
@@ -1713,7 +1502,7 @@ struct BulbScene {
     }
     return mk(a0 / sc, a1 / sc, a2 / sc);
 #else
-    return mk(DIVK(p.x - c0, sc, isc), DIVK(p.y - c1, sc, isc), DIVK(p.z - c2, sc, isc));
+    return mk((p.x - c0) * isc, (p.y - c1) * isc, (p.z - c2) * isc);
 #endif
   }
   __device__ __forceinline__ float eval(V3 p) const {
@@ -1725,36 +1514,6 @@ struct BulbScene {
   }
   // the one shape owns every point (sdf_abi.h "Queries")
   __device__ __forceinline__ int owner_fold(V3) const { return 0; }
-  // The taps of one batch (normal, AO) in lockstep groups of SDF_BULB_GROUP:
-  // each value bit for bit eval(tap(j)).
-  template <class T>
-  __device__ __forceinline__ void taps(const T& tap, float, float, MarchState&,
-                                       float (&f)[T::K]) const {
-    group<0>(tap, f);
-  }
-  template <int J0, class T>
-  __device__ __forceinline__ void group(const T& tap, float (&f)[T::K]) const {
-    constexpr int G = SDF_BULB_GROUP < T::K - J0 ? SDF_BULB_GROUP : T::K - J0;
-    V3 q[G];
-    float m0[G], r0[G], de[G];
-    bool run[G];
-#pragma unroll
-    for (int j = 0; j < G; j++) {
-      q[j] = local(tap(J0 + j));
-      m0[j] = dot(q[j], q[j]);
-      run[j] = !(m0[j] > 2.25f);
-    }
-    mandelbulb_n<G>(q, run, iters, bail2, de);
-#if SDF_EXACT
-    crm::cr_sqrt_n<G>(m0, r0);
-#else
-#pragma unroll
-    for (int j = 0; j < G; j++) r0[j] = fsqrt(m0[j]);
-#endif
-#pragma unroll
-    for (int j = 0; j < G; j++) f[J0 + j] = run[j] ? de[j] * sc : (r0[j] - 1.25f) * sc;
-    if constexpr (J0 + G < T::K) group<J0 + G>(tap, f);
-  }
 };
 
 #define scene_sdf(A, p) scene.eval(p)
@@ -1829,16 +1588,13 @@ template <class Scene, class View, bool SURFACE = true>
 __device__ __forceinline__ void trace_surface(KA& A, const Scene& scene, const View& V, int x,
                                               int y, int& sp, MarchState& mst, Surface& S) {
   // quad = ((2x+1)/W - 1, (2y+1)/H - 1)   (voxel_geometry.geom:26-52)
-#if SDF_EXACT && SDF_EXACT_QDIV
+#if SDF_EXACT
   // (2x+1) / W by one Markstein step from the host's RN(1/W): an integer
   // numerator in [1, 2^17) over an integer W in [1, 2^16] (A.width: the
   // sub-sample width S W of a supersampled frame, held to 2^16 as well), where
   // no step underflows or overflows (cr_math.h div_refined): the IEEE quotient
   const float qx = crm::div_refined((float)(2 * x + 1), (float)A.width, A.inv_width) - 1.0f;
   const float qy = crm::div_refined((float)(2 * y + 1), (float)A.height, A.inv_height) - 1.0f;
-#elif SDF_EXACT
-  const float qx = (float)(2 * x + 1) / (float)A.width - 1.0f;
-  const float qy = (float)(2 * y + 1) / (float)A.height - 1.0f;
 #else
   const float qx = (float)(2 * x + 1) * A.inv_width - 1.0f;
   const float qy = (float)(2 * y + 1) * A.inv_height - 1.0f;
@@ -2027,7 +1783,7 @@ __device__ __forceinline__ void light_terms(KA& A, const Scene& scene, const Vie
     if constexpr (Scene::kPlaneHead) {
       if (!(STEPS && V.steps() != nullptr)) tlim = scene.shadow_limit(o, incident, k, max_dist, lit);
     }
-#if SDF_EXACT && SDF_EXACT_SHSKIP
+#if SDF_EXACT
     // k (1 - 2^-20) for the step's lower bound of k dest (a negative k: no
     // bound, every step takes the exact path)
     const float k_lo = k >= 0.0f ? k * 0x1.ffffep-1f : -INFINITY;
@@ -2038,8 +1794,7 @@ __device__ __forceinline__ void light_terms(KA& A, const Scene& scene, const Vie
       float hn = scene.march(rp, to + t * kPathScale, mst);
 #if SDF_EXACT
       const float hh = hn * hn;
-#if SDF_EXACT_SHSKIP
-      // Round 6: the step's term k dest / den is formed exactly (IEEE division
+      // The step's term k dest / den is formed exactly (IEEE division
       // of hn^2 by 2 h_prev, cr_sqrt, ...) only when some lane of the wave may
       // lower s with it.  Step 0 never does (t = 0: den = +0, the term is
       // +INF or NaN).  Later steps first bound the term from below without the
@@ -2069,38 +1824,21 @@ __device__ __forceinline__ void light_terms(KA& A, const Scene& scene, const Vie
         skip = __builtin_amdgcn_ballot_w64(!ok) == 0;
       }
       if (!skip) {
-#endif
-#if SDF_EXACT_SHDIV
-      // (step 0's h_prev = INF never reaches the division: its quotient is
-      // unused, so it divides by 1 and stays on the fast path)
-      float inter = (ss == 0) ? 0.0f : crm::div_one(hh, ss == 0 ? 1.0f : 2.0f * hprev);
-#else
-      float inter = (ss == 0) ? 0.0f : fdiv(hh, 2.0f * hprev);
-#endif
-      float dest = fsqrt(hh - inter * inter);
-#if SDF_EXACT_SHMM
-      // t - inter may be NaN (then both keep +0) but never -0 against +0
-      // ordered differently: max(+0, y) is +0 for y <= 0 either way
-      const float num = k * dest, den = hw_max(0.0f, t - inter);
-#else
-      const float num = k * dest, den = gmax(0.0f, t - inter);
-#endif
-      // gmin(s, RN(num / den)) is s wherever RN(num - s den) > 0: then num /
-      // den > s exactly (den > 0), so its rounding is >= s; num > 0 = den
-      // gives +INF (s is never NaN or above 1).  So the IEEE division runs
-      // only when some lane of the wave may lower s -- bit for bit the same
-      // (C4 exact 2.6-3.3 % faster).
-      if (__builtin_amdgcn_ballot_w64(!(__builtin_fmaf(-s, den, num) > 0.0f)) != 0)
-#if SDF_EXACT_SHMM
-        // s in [-inf, 1] is never NaN or -0; num / den >= +0 or NaN (num >=
-        // +0: k > 0, dest a square root; den >= +0), and NaN keeps s both ways
-        s = hw_min(s, fdiv(num, den));
-#else
-        s = gmin(s, fdiv(num, den));
-#endif
-#if SDF_EXACT_SHSKIP
+        float inter = (ss == 0) ? 0.0f : fdiv(hh, 2.0f * hprev);
+        float dest = fsqrt(hh - inter * inter);
+        // t - inter may be NaN (then both keep +0) but never -0 against +0
+        // ordered differently: max(+0, y) is +0 for y <= 0 either way
+        const float num = k * dest, den = hw_max(0.0f, t - inter);
+        // gmin(s, RN(num / den)) is s wherever RN(num - s den) > 0: then num /
+        // den > s exactly (den > 0), so its rounding is >= s; num > 0 = den
+        // gives +INF (s is never NaN or above 1).  So the IEEE division runs
+        // only when some lane of the wave may lower s -- bit for bit the same
+        // (C4 exact 2.6-3.3 % faster).
+        if (__builtin_amdgcn_ballot_w64(!(__builtin_fmaf(-s, den, num) > 0.0f)) != 0)
+          // s in [-inf, 1] is never NaN or -0; num / den >= +0 or NaN (num >=
+          // +0: k > 0, dest a square root; den >= +0), and NaN keeps s both ways
+          s = hw_min(s, fdiv(num, den));
       }
-#endif
 #else
       // The same term with inter = h^2 / (2 hp) eliminated:
       //   k dest / (t - inter) = k |h| sqrt(4 hp^2 - h^2) / (2 |hp| t - sgn(hp) h^2)
@@ -2570,8 +2308,8 @@ __device__ __forceinline__ void render_body() {
   // packed row -> frame row: period blk, row `within` of its run of blocks.
   // A run of a multiple of 8 rows (every tiling of 8-row blocks) holds the
   // wave's 8 packed rows whole: its period and offset are wave-uniform,
-  // scalar arithmetic (round 6: the per-lane integer division was ~20 VALU
-  // per wave, tools/block_counts.py)
+  // scalar arithmetic (the per-lane integer division was ~20 VALU per wave,
+  // tools/block_counts.py)
   int y;
   const int r0 = by * 8;
   if ((A.chunk_rows & 7) == 0) {
@@ -3207,12 +2945,9 @@ void camera_rays(RaysArgs args) {
   const int x = blockIdx.x * (8 * kWgWaves) + wave * 8 + (lane & 7);
   const int y = blockIdx.y * 8 + (lane >> 3);
   if (x >= A.width || y >= A.height) return;
-#if SDF_EXACT && SDF_EXACT_QDIV
+#if SDF_EXACT
   const float qx = crm::div_refined((float)(2 * x + 1), (float)A.width, A.inv_width) - 1.0f;
   const float qy = crm::div_refined((float)(2 * y + 1), (float)A.height, A.inv_height) - 1.0f;
-#elif SDF_EXACT
-  const float qx = (float)(2 * x + 1) / (float)A.width - 1.0f;
-  const float qy = (float)(2 * y + 1) / (float)A.height - 1.0f;
 #else
   const float qx = (float)(2 * x + 1) * A.inv_width - 1.0f;
   const float qy = (float)(2 * y + 1) * A.inv_height - 1.0f;

@@ -290,8 +290,8 @@ void prepare_bounds(const sdf_scene& s, sdf::KernelArgs& a, bool exact = false) 
     a.bound[i][3] = float((k + R + sdf::kCullAbs) / (1.0 - sdf::kCullRel) * (1.0 + 1e-6));
     // exact kernel (the prepared block's `reserved`, unused there): the
     // offset of the gap an evaluated primitive's own value leaves in the
-    // culling cache, k + margin + 1e-4 R (render_kernel.inc step_cached,
-    // SDF_CULL_SGAP), rounded up
+    // culling cache, k + margin + 1e-4 R (render_kernel.inc step_cached),
+    // rounded up
     if (exact && sdf::cullable(kind, pr.op))
       a.prims[i].reserved = float((k + sdf::kCullAbs + 1e-4 * R) * (1.0 + 1e-6));
   }

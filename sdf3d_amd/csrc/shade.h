@@ -47,10 +47,9 @@ enum TilesShade : uint32_t {
 // [0, 1.0001] (tests/crmath "pow", tests/test_gpu_crmath.py) checks it.  Where both ends of a 2^-44 interval around it round to the same
 // float, that float is the correct rounding of x^n -- and of the library's
 // fp64 pow, which lies in the same interval; other lanes (rounding
-// boundaries, NaN) take the library pow.  SDF_SHADE_LIBRARY_POW 1: the
-// library pow alone -- the same floats (the TILES decoder used it until
-// round 5 to keep its tile loop rolled at 8 waves/SIMD; on exact-precision
-// streams it cost 0.084 ms of decode per 4K frame, tiles.hip).
+// boundaries, NaN) take the library pow.  (The library pow alone gives the
+// same floats; on exact-precision streams it cost the TILES decoder 0.084 ms
+// per 4K frame, tiles.hip.)
 // The library fp64 pow, out of line (SDF_SHADE_POW_CALL 1): inlined, its
 // ~30 fp64 constants were hoisted out of the persistent frames kernel's tile
 // loop (render_kernel.inc render_frames) and spilled to scratch; as a call
@@ -69,7 +68,6 @@ template <bool EXACT>
 __device__ __forceinline__ float spec_pow(float x, float shin) {
 #pragma clang fp contract(off)
   if constexpr (EXACT) {
-#if !defined(SDF_SHADE_LIBRARY_POW) || !SDF_SHADE_LIBRARY_POW
     const int n = (int)shin;
     if ((float)n == shin && n >= 0 && n <= 64) {
       double b = (double)x, v = 1.0;
@@ -115,7 +113,6 @@ __device__ __forceinline__ float spec_pow(float x, float shin) {
       }
       return out;
     }
-#endif
     return library_pow(x, shin);
   } else {
     return __builtin_amdgcn_exp2f(shin * __builtin_amdgcn_logf(x));

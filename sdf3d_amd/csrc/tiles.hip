@@ -27,12 +27,6 @@
 #include <stdint.h>
 
 #include "host_api.h"   // this unit's launcher prototypes (and kernel_args.h)
-// Exact-precision streams' specular term: 1 = the library fp64 pow alone
-// (through round 4), 0 = shade.h's repeated squaring with the library pow
-// only on lanes near a rounding boundary -- the same floats
-#ifndef SDF_SHADE_LIBRARY_POW
-#define SDF_SHADE_LIBRARY_POW 0
-#endif
 #include "shade.h"
 
 namespace sdf {
@@ -68,38 +62,14 @@ __device__ __forceinline__ uint32_t unordered_bits(uint32_t u) {
 
 // tiles per wave of the decoder: 4 (0.051 ms for the root's 7/8 of a 4K
 // frame) beats 2 (0.055); forcing 8 waves / SIMD spills and gains nothing.
-// Round 4 (rank 0's 49/51 of the 4K C4 frame, profiles/r04_decode_ab.json):
+// On rank 0's 49/51 of the 4K C4 frame (profiles/r04_decode_ab.json):
 // non-temporal frame stores 0.0445 against 0.0466 ms; one-wave workgroups
 // 0.0470 (four kept); the column scan and the 16- and 8-bit transpose stages
 // on the VALU (v_permlane16/32_swap, v_perm_b32, DPP row_ror) instead of
 // ds_bpermute / ds_swizzle 0.0506 (not kept: the LDS round trips were not
 // what bounds it, the extra VALU work and hazard waits are).
-#ifndef SDF_DECODE_TILES
-#define SDF_DECODE_TILES 4
-#endif
-#ifndef SDF_DECODE_WG_WAVES
-#define SDF_DECODE_WG_WAVES 4   // waves per decoder workgroup
-#endif
-#ifndef SDF_DECODE_NT
-#define SDF_DECODE_NT 1         // the frame's pixels by non-temporal stores
-#endif
-#ifndef SDF_DECODE_ESC_VMEM
-#define SDF_DECODE_ESC_VMEM 0   // 1: a pixel's escape window by its own loads, not ds_bpermute
-#endif
-#ifndef SDF_DECODE_SKIP
-#define SDF_DECODE_SKIP 0   // timing probes only (wrong pixels): 2 escapes, 4 scan, 8 shade
-#endif
-// The macros above are experiment knobs (tools/flag_variant.py, which
-// defines SDF_EXPERIMENT); SKIP builds decode wrong pixels on purpose, and
-// none of them enters sdf_kernel_id, so a library built with any of them
-// away from its default must not pass for a product build.
-#if !defined(SDF_EXPERIMENT) && (SDF_DECODE_SKIP != 0 || SDF_DECODE_ESC_VMEM != 0 || \
-                                 SDF_DECODE_TILES != 4 || SDF_DECODE_WG_WAVES != 4 || \
-                                 SDF_DECODE_NT != 1)
-#error "decoder probe / layout knobs build only as experiments (tools/flag_variant.py)"
-#endif
-constexpr int kDecodeTiles = SDF_DECODE_TILES;
-constexpr int kDecodeWgWaves = SDF_DECODE_WG_WAVES;
+constexpr int kDecodeTiles = 4;
+constexpr int kDecodeWgWaves = 4;   // waves per decoder workgroup
 
 // One wave = TPW consecutive tiles of one part, lane j = pixel (j / 8, j % 8)
 // of each.  The memory traffic is issued up front in two dependent rounds:
@@ -259,7 +229,7 @@ __device__ __forceinline__ void decode_body(const DecodeParts& D, const uint8_t*
     // window by v_bfe at the running offset, without 64-bit shifts
     const int P = __builtin_popcount(escaped);
     uint32_t dl[3] = {0u, 0u, 0u}, f_lo = 0u, f_hi = 0u;
-    if (!(SDF_DECODE_SKIP & 2) && escaped) {
+    if (escaped) {
       const int bs = 2 * (B + P);                       // bitstream's first dword
       const uint32_t deltas = bs < 128 ? (uint32_t)__builtin_amdgcn_readlane(
                                              (int)((bs & 1) ? pa[k].y : pa[k].x), bs >> 1)
@@ -293,16 +263,6 @@ __device__ __forceinline__ void decode_body(const DecodeParts& D, const uint8_t*
       const uint32_t endbit = (o & 31u) + nb;
       const bool inside = nb == 0u || dw + ((endbit - 1u) >> 5) < 2u * (uint32_t)nq;
       if (__builtin_amdgcn_ballot_w64(!inside)) report(kTilesBadField);
-#if SDF_DECODE_ESC_VMEM
-      // dwords dw .. dw + 2 of the tile's data, loaded by the lanes with fields
-      uint32_t d0 = 0u, d1 = 0u, d2 = 0u;
-      if (nb && inside) {
-        const uint32_t* t32 = reinterpret_cast<const uint32_t*>(tdata);
-        d0 = t32[dw];
-        d1 = endbit > 32u ? t32[dw + 1] : 0u;
-        d2 = endbit > 64u ? t32[dw + 2] : 0u;
-      }
-#else
       // dwords dw .. dw + 2 of the tile's data: qwords dw / 2 and dw / 2 + 1
       // from the lanes holding them
       const int a = (int)((dw >> 1) << 2);
@@ -317,7 +277,6 @@ __device__ __forceinline__ void decode_body(const DecodeParts& D, const uint8_t*
         d1 = endbit > 32u ? t32[dw + 1] : 0u;
         d2 = endbit > 64u ? t32[dw + 2] : 0u;
       }
-#endif
       f_lo = __builtin_amdgcn_alignbit(d1, d0, o & 31);
       f_hi = __builtin_amdgcn_alignbit(d2, d1, o & 31);
     }
@@ -334,8 +293,7 @@ __device__ __forceinline__ void decode_body(const DecodeParts& D, const uint8_t*
       }
       uint32_t r = (z >> 1) ^ (0u - (z & 1u));            // un-zigzag
       if (lane == 0) r = first[ch];                       // pixel 0 travels raw
-      if constexpr (SDF_DECODE_SKIP & 4) v[ch] = __uint_as_float(r);
-      else v[ch] = __uint_as_float(unordered_bits(scan_tile(r, SL)));
+      v[ch] = __uint_as_float(unordered_bits(scan_tile(r, SL)));
     }
     const int x = tx * 8 + col;
     if (x < width && ty * 8 + prow < rows) {
@@ -348,16 +306,12 @@ __device__ __forceinline__ void decode_body(const DecodeParts& D, const uint8_t*
       }
       const int y = (first_blk + b * period) * brows + w + jb * gap;
       float4 px = make_float4(v[0], v[1], v[2], 1.0f);
-      if (SDF_DECODE_SKIP & 8) px = make_float4(v[0], v[1], v[2], 1.0f);
-      else if (shade == kTilesShadeFast) px = shade_colour<false>(K, v[0], v[1], v[2]);
+      if (shade == kTilesShadeFast) px = shade_colour<false>(K, v[0], v[1], v[2]);
       else if (shade == kTilesShadeExact) px = shade_colour<true>(K, v[0], v[1], v[2]);
-      if constexpr (SDF_DECODE_NT) {
-        typedef float v4f __attribute__((ext_vector_type(4)));
-        const v4f pv = {px.x, px.y, px.z, px.w};
-        __builtin_nontemporal_store(pv, reinterpret_cast<v4f*>(frame + (size_t)y * width + x));
-      } else {
-        frame[(size_t)y * width + x] = px;
-      }
+      // the frame's pixels by non-temporal stores
+      typedef float v4f __attribute__((ext_vector_type(4)));
+      const v4f pv = {px.x, px.y, px.z, px.w};
+      __builtin_nontemporal_store(pv, reinterpret_cast<v4f*>(frame + (size_t)y * width + x));
     }
     (void)nq;
   }

@@ -23,7 +23,7 @@ sys.path.insert(0, str(ROOT))
 
 def main():
     name, flags = sys.argv[1], sys.argv[2:]
-    flags = ["-DSDF_EXPERIMENT=1", *flags]   # unlocks the experiment-only knobs (tiles.hip)
+    flags = ["-DSDF_EXPERIMENT=1", *flags]   # unlocks the experiment-only switches (SDF_ABLATE_NO_NORMAL)
     prefixes = ("render_",)
     # --sched=NAME (after NAME): the render units' scheduler strategy
     # (max-ilp, iterative-ilp, ..., or default: none)

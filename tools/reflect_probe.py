@@ -14,8 +14,7 @@ with device events on one stream, alternated window by window in one process:
   parent_materials  of the library (--parent-lib, e.g. the parent commit's):
                     are the existing kernels untouched?
   NAME              sdf_render_reflect, 2 bounces, of a variant build
-                    (--variant NAME=PATH, e.g. another SDF_REFLECT_WAVES_PER_EU
-                    or SDF_REFLECT_PEEL=0)
+                    (--variant NAME=PATH, e.g. another SDF_REFLECT_WAVES_PER_EU)
 
 Each window renders back to back for at least --window seconds (after a
 warm-up of every leg) and gives one ms-per-frame figure; --repeats windows per
