@@ -1225,8 +1225,13 @@ int sdf_jit_count(void);
  * NULL for an unknown precision. */
 const char* sdf_kernel_id(int32_t precision);
 
-/* The culling bounds a primitive scene's fixed-scene kernels read (host
- * only, no device needed; diagnostics and tests): per primitive
+/* The culling bounds the generic kernel reads for a primitive scene (host
+ * only, no device needed; diagnostics and tests).  A plan of the fixed-scene
+ * or run-time specialised kernels (SDF_DISPATCH_AUTO) caches gaps along a
+ * path and reads larger ones: 2^-20 (|c|_inf + R_i + k_i + max_dist) is added
+ * to the 1e-4 below.  No plan culls when a cullable primitive has |c|_inf +
+ * R_i + k_i + max_dist > 2^22; this call knows no max_dist and reports
+ * *cluster_first = count from |c|_inf + R_i + k_i > 2^22 on.  Per primitive
  * bounds[4 * i ..] = {centre.xyz, K_i = (k_i + R_i + 1e-4) / (1 - 1e-5)}
  * with R_i the radius of a sphere containing primitive i, the cluster
  * cluster[0..3] = {centre.xyz, K} of the sphere containing primitives

@@ -1728,6 +1728,62 @@ __device__ __forceinline__ void trace_ray(KA& A, const Scene& scene, const V3 ca
   S.d = T.d;
 }
 
+// A path's ray (shade_pixel_reflect, shade_pixel_env, shade_ray: O_j, D_j of a
+// reflected layer) may have components that are not finite: a normal that is
+// normalize(0) -- far from the origin, where the taps P +- normal_eps all
+// round to P -- is NaN, and so are the ray mirrored at it and its origin.  The
+// path "goes on as the arithmetic says" (sdf_abi.h "Reflections"), the
+// arithmetic of the scene spec with its selects, which the scene evaluators
+// do not keep on a NaN point (see sel_query below: sdf_trace's rays of this
+// kind).  So a lane with such a ray takes its primary march through sel_scene,
+// operation for operation the CPU oracle's raymarch: d_j, P_j and the primary
+// step count are the oracle's.  Its culling state stays the fresh one.  A cold
+// path behind a real branch, entered by a wave only when one of its lanes has
+// such a ray; primitive scenes only, as there.
+__device__ __forceinline__ float sel_scene(KA& A, V3 p);
+template <class Scene>
+__device__ __forceinline__ void trace_march_path(KA& A, const Scene& scene, const V3 cam,
+                                                 const V3 ray, int& sp, MarchState& mst,
+                                                 Surface& S) {
+  const bool odd = !(fabsf(ray.x) < INFINITY && fabsf(ray.y) < INFINITY &&
+                     fabsf(ray.z) < INFINITY && fabsf(cam.x) < INFINITY &&
+                     fabsf(cam.y) < INFINITY && fabsf(cam.z) < INFINITY);
+  if (A.scene_kind == SDF_SCENE_PRIMITIVES && __builtin_amdgcn_ballot_w64(odd) != 0) {
+    asm volatile("" ::: "memory");   // a real branch: never if-converted into the march
+    if (odd) {
+      float d = 0.0f;
+#pragma unroll 1
+      for (; sp < A.max_steps;) {
+        const float s = sel_scene(A, add(cam, muls(ray, d)));
+        d += s;
+        sp++;
+        if (d > A.max_dist || s < A.eps) break;
+      }
+      S.P = add(cam, muls(ray, d));
+      S.tP = d * kPathScale;
+      S.d = d;
+      return;
+    }
+  }
+  trace_march(A, scene, cam, ray, sp, mst, S);
+}
+// trace_ray for such a ray
+template <class Scene>
+__device__ __forceinline__ void trace_ray_path(KA& A, const Scene& scene, const V3 cam,
+                                               const V3 ray, int& sp, MarchState& mst,
+                                               Surface& S) {
+  Surface T;
+  trace_march_path(A, scene, cam, ray, sp, mst, T);
+  trace_shape(A, scene, mst, T);
+  S.cam = cam;
+  S.P = T.P;
+  S.N = T.N;
+  S.tP = T.tP;
+  S.ao = T.ao;
+  S.ray = ray;
+  S.d = T.d;
+}
+
 // The terms of the light at Lp for the surface S: dif = clamp(N.L, 0, 1) *
 // shadow and spec_x = max(N.H, 0); `mst` is the culling state at P (advanced
 // along the shadow ray), `ss` counts the shadow march's iterations from 0.
@@ -2130,7 +2186,7 @@ __device__ __forceinline__ float4 shade_pixel_reflect(KA& A, const KARG LightsAr
     MarchState mst;
     Surface S;
     int spj = 0, ssj = 0;
-    trace_ray(A, scene, path.O, path.D, spj, mst, S);
+    trace_ray_path(A, scene, path.O, path.D, spj, mst, S);
     float C[3], mr[3];
     surface_colour<STEPS, FOLD>(A, L, M, scene, V, S, mst, ssj, C, mr);
     path.layer_done(A, R, j, S, C, mr, spj, ssj);
@@ -2203,7 +2259,7 @@ __device__ __forceinline__ float4 shade_pixel_env(KA& A, const KARG LightsArgs& 
     MarchState mst;
     Surface S;
     int spj = 0;
-    trace_march(A, scene, path.O, path.D, spj, mst, S);
+    trace_march_path(A, scene, path.O, path.D, spj, mst, S);
     S.cam = path.O;
     S.ray = path.D;
     env_layer<STEPS, FOLD>(A, L, M, R, E, scene, V, j, S, mst, spj, path);
@@ -2830,8 +2886,8 @@ void query(QueryArgs args) {
 // ---- caller-supplied rays (sdf_abi.h "Rays": sdf_render_rays, sdf_camera_rays) --
 // The path of shade_pixel_reflect (ENV: shade_pixel_env) whose layer 0 is read
 // from memory instead of being formed from (x, y): every layer, the first
-// included, is what those functions' loops run for j >= 1 -- trace_ray and
-// surface_colour, or trace_march and env_layer, the very device functions --
+// included, is what those functions' loops run for j >= 1 -- trace_ray_path and
+// surface_colour, or trace_march_path and env_layer, the very device functions --
 // from the lane's own eye.  In exact precision nothing is contracted, so the
 // ray of a pixel gives the pixel's bits (tests/test_gpu_rays.py holds them).
 template <bool STEPS, bool FOLD, bool ENV, class Scene, class View>
@@ -2849,13 +2905,13 @@ __device__ __forceinline__ float4 shade_ray(KA& A, const KARG LightsArgs& L,
     Surface S;
     int spj = 0;
     if constexpr (ENV) {
-      trace_march(A, scene, path.O, path.D, spj, mst, S);
+      trace_march_path(A, scene, path.O, path.D, spj, mst, S);
       S.cam = path.O;
       S.ray = path.D;
       env_layer<STEPS, FOLD>(A, L, M, R, E, scene, V, j, S, mst, spj, path);
     } else {
       int ssj = 0;
-      trace_ray(A, scene, path.O, path.D, spj, mst, S);
+      trace_ray_path(A, scene, path.O, path.D, spj, mst, S);
       float C[3], mr[3];
       surface_colour<STEPS, FOLD>(A, L, M, scene, V, S, mst, ssj, C, mr);
       path.layer_done(A, R, j, S, C, mr, spj, ssj);

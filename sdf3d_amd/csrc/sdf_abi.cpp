@@ -244,14 +244,35 @@ static double cluster_sphere(const double (*c)[3], const double* r, int n, doubl
   return RB;
 }
 
-// Bounding spheres and the cluster bound read by the fixed-scene kernels'
-// culling (kernel_args.h "exact bounding-volume culling").  Radii are computed
-// in double and rounded up.
-void prepare_bounds(const sdf_scene& s, sdf::KernelArgs& a, bool exact = false) {
+// Host-only constants of the culling margins (no kernel reads them).  The
+// cached gaps (render_kernel.inc FixedScene::march) compare computed path
+// points o + D t, each rounded by up to sqrt 3 2^-24 (|D t|_inf + |p|_inf);
+// at most four such points lie between a stored gap and its use, and
+// 4 sqrt 3 2^-24 < 2^-21: kCullPath holds twice that.
+constexpr double kCullPath = 0x1p-20;
+constexpr double kCullMaxCoord = 0x1p22;
+
+// Bounding spheres and the cluster bound read by the kernels' culling
+// (kernel_args.h "exact bounding-volume culling").  Radii are computed in
+// double, around the fp32 centre the kernels read, and rounded up.
+//
+// `cached`: the plan's kernel keeps gaps along a path (FixedScene).  Each
+// bound's absolute margin is then kCullAbs + kCullPath (|c|_inf + R + k +
+// reach), the second term covering the fp32 rounding of the path points
+// o + D t between which a gap is carried (DESIGN.md "Culling margins at large
+// coordinates"); `reach` is the longest ray segment of the plan, its
+// max_dist.  The generic kernel makes every test afresh at the point it
+// evaluates and needs no such term: sdf_scene_bounds reports its bounds.
+// Returns false, with cluster_first = count, when the cullable primitives
+// reach beyond kCullMaxCoord, where neither argument is made: the caller
+// must then take the unculled path.
+bool prepare_bounds(const sdf_scene& s, sdf::KernelArgs& a, bool exact = false,
+                    bool cached = false, double reach = 0.0) {
   std::memset(a.bound, 0, sizeof(a.bound));
   a.cluster_first = s.count;
   double cen[SDF_MAX_PRIMS][3], rad[SDF_MAX_PRIMS];
   bool cull[SDF_MAX_PRIMS];
+  double span = 0;   // the largest |c|_inf + R + k of a cullable primitive
   for (int i = 0; i < s.count; ++i) {
     const sdf_primitive& pr = s.prims[i];
     const float* q = pr.p;
@@ -272,9 +293,17 @@ void prepare_bounds(const sdf_scene& s, sdf::KernelArgs& a, bool exact = false) 
       }
       case SDF_PRIM_TORUS: R = double(q[3]) + q[4]; break;
       case SDF_PRIM_CAPSULE: {
-        for (int j = 0; j < 3; ++j) c[j] = 0.5 * (double(q[j]) + q[3 + j]);
-        const double dx = double(q[3]) - q[0], dy = double(q[4]) - q[1], dz = double(q[5]) - q[2];
-        R = 0.5 * std::sqrt(dx * dx + dy * dy + dz * dz) + q[6];
+        // the sphere about the midpoint, enlarged by what the midpoint
+        // loses when it is rounded to the fp32 centre the kernels read: up to
+        // half an ulp of the coordinates per axis, whatever the capsule's size
+        double half2 = 0, off2 = 0;
+        for (int j = 0; j < 3; ++j) {
+          const double m = 0.5 * (double(q[j]) + q[3 + j]), h = 0.5 * (double(q[3 + j]) - q[j]);
+          c[j] = double(float(m));
+          half2 += h * h;
+          off2 += (c[j] - m) * (c[j] - m);
+        }
+        R = std::sqrt(half2) + q[6] + std::sqrt(off2);
         break;
       }
       case SDF_PRIM_CYLINDER: R = std::sqrt(double(q[3]) * q[3] + double(q[4]) * q[4]); break;
@@ -286,17 +315,22 @@ void prepare_bounds(const sdf_scene& s, sdf::KernelArgs& a, bool exact = false) 
     const double k = pr.op == SDF_OP_SMOOTH_UNION ? pr.k : 0.0;
     for (int j = 0; j < 3; ++j) { cen[i][j] = c[j]; a.bound[i][j] = float(c[j]); }
     rad[i] = R;
+    const double reachi =
+        std::max({std::fabs(c[0]), std::fabs(c[1]), std::fabs(c[2])}) + R + k;
+    if (cull[i]) span = std::max(span, reachi);
+    const double margin = sdf::kCullAbs + (cached ? kCullPath * (reachi + reach) : 0.0);
     // K' = (k + R + margin) / (1 - kCullRel), rounded up (render_kernel.inc wave_near)
-    a.bound[i][3] = float((k + R + sdf::kCullAbs) / (1.0 - sdf::kCullRel) * (1.0 + 1e-6));
+    a.bound[i][3] = float((k + R + margin) / (1.0 - sdf::kCullRel) * (1.0 + 1e-6));
     // exact kernel (the prepared block's `reserved`, unused there): the
     // offset of the gap an evaluated primitive's own value leaves in the
     // culling cache, k + margin + 1e-4 R (render_kernel.inc step_cached),
     // rounded up
     if (exact && sdf::cullable(kind, pr.op))
-      a.prims[i].reserved = float((k + sdf::kCullAbs + 1e-4 * R) * (1.0 + 1e-6));
+      a.prims[i].reserved = float((k + margin + 1e-4 * R) * (1.0 + 1e-6));
   }
   int first = s.count;
   while (first > 0 && cull[first - 1]) --first;
+  if (first < s.count && !(span + reach <= kCullMaxCoord)) return false;
   a.cluster_first = first;
   if (first < s.count) {
     double C[3];
@@ -307,9 +341,13 @@ void prepare_bounds(const sdf_scene& s, sdf::KernelArgs& a, bool exact = false) 
     for (int i = first; i < s.count; ++i)
       if (s.prims[i].op == SDF_OP_SMOOTH_UNION) kmax = std::max(kmax, double(s.prims[i].k));
     for (int j = 0; j < 3; ++j) a.cluster[j] = float(C[j]);
-    a.cluster[3] = float((kmax + RC * (1.0 + 1e-6) + 1e-6 + sdf::kCullAbs) /
+    const double cmax = std::max({std::fabs(C[0]), std::fabs(C[1]), std::fabs(C[2])});
+    const double margin =
+        sdf::kCullAbs + (cached ? kCullPath * (cmax + RC + kmax + reach) : 0.0);
+    a.cluster[3] = float((kmax + RC * (1.0 + 1e-6) + 1e-6 + margin) /
                          (1.0 - sdf::kCullRel) * (1.0 + 1e-6));
   }
+  return true;
 }
 
 }  // namespace
@@ -445,15 +483,18 @@ int make_render_plan(const sdf_scene* scene, const sdf_camera* camera, const sdf
   a.bulb_bail2 = scene->bulb_bailout * scene->bulb_bailout;
   a.bulb_iterations = scene->bulb_iterations;
   prepare_prims(*scene, a.prims);
-  if (scene->kind == SDF_SCENE_PRIMITIVES)
-    prepare_bounds(*scene, a, params->precision == SDF_PRECISION_EXACT);
+  // the generic kernel on request, and beyond the culling's proven range
+  // (there unculled); only the specialised kernels carry gaps along a path
+  const bool prims = scene->kind == SDF_SCENE_PRIMITIVES;
+  const bool exact = params->precision == SDF_PRECISION_EXACT;
+  const bool cached = params->dispatch == SDF_DISPATCH_AUTO;
+  const bool cull_proven = !prims || prepare_bounds(*scene, a, exact, cached, params->max_dist);
   a.bulb_inv_scale = 1.0f / scene->bulb_scale;
   a.rgba = rgba;
   a.steps = steps;
 
-  const bool generic = params->dispatch != SDF_DISPATCH_AUTO &&
-                       scene->kind == SDF_SCENE_PRIMITIVES;
-  if (params->dispatch == SDF_DISPATCH_UNCULLED) a.cluster_first = a.prim_count;
+  const bool generic = (!cached || !cull_proven) && prims;
+  if (params->dispatch == SDF_DISPATCH_UNCULLED || !cull_proven) a.cluster_first = a.prim_count;
   plan->variant = generic ? kVariantGeneric : select_variant(*scene);
   plan->exact = params->precision == SDF_PRECISION_EXACT;
   // no built-in specialisation: a run-time compiled one (jit.cpp)
