@@ -7,7 +7,7 @@
 //
 //   sdf_main [--palette] [--reflect B[,strength]] [--sky [--no-sun]] [--fog START,END[,r,g,b]]
 //            [--pick X,Y] [--projection pinhole|equirect]
-//            [--mesh FILE.obj --grid x0,y0,z0,x1,y1,z1,N]
+//            [--mesh FILE.obj|FILE.ply --grid x0,y0,z0,x1,y1,z1,N [--mesh-colors]]
 //            [width height frames out.ppm scene [samples [lights]]]
 //     scene: ref | csg8 | bulb; samples: 1 (default), 2 or 4 sub-samples per
 //     axis, resolved in the render kernel (single-GPU path only: the frame
@@ -42,11 +42,16 @@
 //     exact precision.  equirect: a full panorama from the camera's place,
 //     longitude across and latitude up, its directions built on the host and
 //     normalised by the kernel
-//     --mesh FILE.obj --grid x0,y0,z0,x1,y1,z1,N (anywhere on the line): after
+//     --mesh FILE.obj|FILE.ply --grid x0,y0,z0,x1,y1,z1,N (anywhere on the line): after
 //     the last frame, the scene's surface inside the box from (x0,y0,z0) to
 //     (x1,y1,z1), N cells per axis, as a triangle mesh with normals in a
 //     Wavefront OBJ file (sdf::extract_mesh: sdf_mesh_count and sdf_mesh_emit;
-//     single-GPU path only)
+//     single-GPU path only); a FILE ending in .ply is written as binary PLY.
+//     With --mesh-colors every vertex carries its baked colour (sdf::bake:
+//     sdf_shade_points at the vertices, lifted by one cell diagonal, under the
+//     frame's lights and, with --palette, its materials; no specular term, which
+//     would depend on the viewer).  --palette stays the switch it is above: it
+//     takes no count, the palette has one entry per primitive
 //
 // Multi-GPU: launched once per GPU by any launcher that sets RANK,
 // WORLD_SIZE and LOCAL_RANK (e.g. `torchrun --nproc-per-node 8 --no-python
@@ -220,6 +225,7 @@ int main(int argc, char** argv) {
   std::string projection, mesh_path;
   double box[6] = {0, 0, 0, 0, 0, 0};
   int mesh_n = 0;
+  bool mesh_colors = false;
   int pick_x = 0, pick_y = 0;
   sdf_reflect reflect = {0, 1.0f, -1, 0};
   sdf_environment environment = sdf::sky(0);
@@ -253,9 +259,11 @@ int main(int argc, char** argv) {
       } else if (std::string(argv[i]) == "--mesh") {
         mesh_path = i + 1 < argc ? argv[++i] : "";
         if (mesh_path.empty()) {
-          std::fprintf(stderr, "sdf_main: --mesh FILE.obj\n");
+          std::fprintf(stderr, "sdf_main: --mesh FILE.obj|FILE.ply\n");
           return 1;
         }
+      } else if (std::string(argv[i]) == "--mesh-colors") {
+        mesh_colors = true;
       } else if (std::string(argv[i]) == "--grid") {
         char tail = 0;
         if (!(i + 1 < argc && std::sscanf(argv[++i], "%lf,%lf,%lf,%lf,%lf,%lf,%d%c", &box[0], &box[1],
@@ -302,7 +310,11 @@ int main(int argc, char** argv) {
     }
     argc = n;
     if (mesh_path.empty() != (mesh_n == 0)) {
-      std::fprintf(stderr, "sdf_main: --mesh FILE.obj needs --grid x0,y0,z0,x1,y1,z1,N and vice versa\n");
+      std::fprintf(stderr, "sdf_main: --mesh FILE.obj|FILE.ply needs --grid x0,y0,z0,x1,y1,z1,N and vice versa\n");
+      return 1;
+    }
+    if (mesh_colors && mesh_path.empty()) {
+      std::fprintf(stderr, "sdf_main: --mesh-colors needs --mesh FILE --grid ...\n");
       return 1;
     }
     if (no_sun) environment.flags &= ~SDF_ENV_SUN;
@@ -423,8 +435,13 @@ int main(int argc, char** argv) {
     }
     if (!mesh_path.empty()) {
       const double lo[3] = {box[0], box[1], box[2]}, hi[3] = {box[3], box[4], box[5]};
-      const sdf::Mesh m = sdf::extract_mesh(f, sdf::box_grid(lo, hi, mesh_n), true, false, stream);
-      sdf::write_obj(mesh_path, m);
+      const sdf_grid g = sdf::box_grid(lo, hi, mesh_n);
+      const sdf::Mesh m = sdf::extract_mesh(f, g, true, false, stream);
+      std::vector<float> colors;
+      if (mesh_colors) colors = sdf::bake(f, m, g, lights, light_flags, materials, nullptr, -1.0f, stream);
+      const bool ply = mesh_path.size() > 4 && mesh_path.compare(mesh_path.size() - 4, 4, ".ply") == 0;
+      if (ply) sdf::write_ply(mesh_path, m, colors);
+      else sdf::write_obj(mesh_path, m, colors);
       std::printf("mesh: %lld vertices, %lld triangles, %lld of %lld bricks evaluated; wrote %s\n",
                   (long long)m.counts[0], (long long)m.counts[1], (long long)m.counts[2],
                   (long long)m.counts[3], mesh_path.c_str());

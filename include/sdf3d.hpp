@@ -606,15 +606,23 @@ inline sdf_grid box_grid(const double (&lo)[3], const double (&hi)[3], int n, fl
   return g;
 }
 // A Wavefront OBJ file of the mesh: 1-based indices, `vn` lines when the mesh
-// has normals (sdf3d_amd/meshio.py reads it back).
-inline void write_obj(const std::string& path, const Mesh& m) {
+// has normals (sdf3d_amd/meshio.py reads it back).  `colors` (4 floats per
+// vertex, as bake returns them; empty: none): every `v` line carries r g b
+// behind the position.
+inline void write_obj(const std::string& path, const Mesh& m,
+                      const std::vector<float>& colors = {}) {
   FILE* fp = std::fopen(path.c_str(), "w");
   if (!fp) throw Error(SDF_E_INVALID_ARG, "cannot open " + path);
   const size_t nv = m.verts.size() / 3, nt = m.tris.size() / 3;
   const bool vn = m.normals.size() == m.verts.size() && nv > 0;
+  const bool vc = colors.size() == 4 * nv && nv > 0;
   std::fprintf(fp, "# %zu vertices, %zu triangles\n", nv, nt);
-  for (size_t i = 0; i < nv; ++i)
-    std::fprintf(fp, "v %.9g %.9g %.9g\n", m.verts[3 * i], m.verts[3 * i + 1], m.verts[3 * i + 2]);
+  for (size_t i = 0; i < nv; ++i) {
+    std::fprintf(fp, "v %.9g %.9g %.9g", m.verts[3 * i], m.verts[3 * i + 1], m.verts[3 * i + 2]);
+    if (vc)
+      std::fprintf(fp, " %.9g %.9g %.9g", colors[4 * i], colors[4 * i + 1], colors[4 * i + 2]);
+    std::fputc('\n', fp);
+  }
   if (vn)
     for (size_t i = 0; i < nv; ++i)
       std::fprintf(fp, "vn %.9g %.9g %.9g\n", m.normals[3 * i], m.normals[3 * i + 1],
@@ -623,6 +631,123 @@ inline void write_obj(const std::string& path, const Mesh& m) {
     const int a = m.tris[3 * i] + 1, b = m.tris[3 * i + 1] + 1, c = m.tris[3 * i + 2] + 1;
     if (vn) std::fprintf(fp, "f %d//%d %d//%d %d//%d\n", a, a, b, b, c, c);
     else std::fprintf(fp, "f %d %d %d\n", a, b, c);
+  }
+  std::fclose(fp);
+}
+
+// ---- shading at caller-supplied points (sdf_abi.h "Points") ---------------------
+// Lights, shadows, occlusion and materials of the frame's scene at n points of
+// the caller's own, without a primary march: `points` (device, n x 3 packed
+// floats), `normals` (the same, used as given, or null: evaluated at the point),
+// `eye` (3 floats, or null: no specular term), `lift` (the points move that far
+// along their normals first).  `out`: device buffers, null for what is not
+// wanted (sdf_point_shade).  An empty `materials` gives every primitive
+// f.material, an empty `lights` the frame's one.  A wave shades 64 consecutive
+// points.  Asynchronous on `stream`.
+inline void shade_points(const Frame& f, const std::vector<sdf_light>& lights, int32_t light_flags,
+                         const std::vector<sdf_material>& materials, const float* points,
+                         const float* normals, int64_t n, const float* eye, float lift,
+                         const sdf_point_shade& out, hipStream_t stream = nullptr) {
+  const std::vector<sdf_material> same(
+      f.scene.kind == SDF_SCENE_PRIMITIVES ? static_cast<size_t>(f.scene.count) : 1, f.material);
+  const std::vector<sdf_material>& m = materials.empty() ? same : materials;
+  const std::vector<sdf_light> one(1, f.light);
+  const std::vector<sdf_light>& l = lights.empty() ? one : lights;
+  sdf_points p{};
+  p.points = points;
+  p.normals = normals;
+  p.n = n;
+  p.lift = lift;
+  if (eye) {
+    p.flags = SDF_POINTS_EYE;
+    for (int c = 0; c < 3; ++c) p.eye[c] = eye[c];
+  }
+  check(sdf_shade_points(&f.scene, l.data(), static_cast<int32_t>(l.size()), light_flags, m.data(),
+                         static_cast<int32_t>(m.size()), &f.params, &p, &out, stream),
+        "sdf_shade_points");
+}
+// Vertex colours of a mesh extracted with `grid` (4 floats per vertex, alpha 1):
+// shade_points at the vertices with the mesh's normals when it has them, lifted
+// by the length of the cell diagonal (a surface-nets vertex lies within half a
+// diagonal of the surface) unless `lift` >= 0 says otherwise.  Blocking.
+inline std::vector<float> bake(const Frame& f, const Mesh& m, const sdf_grid& grid,
+                               const std::vector<sdf_light>& lights = {}, int32_t light_flags = 0,
+                               const std::vector<sdf_material>& materials = {},
+                               const float* eye = nullptr, float lift = -1.0f,
+                               hipStream_t stream = nullptr) {
+  check_abi();
+  const size_t nv = m.verts.size() / 3;
+  std::vector<float> colors(4 * nv);
+  if (nv == 0) return colors;
+  if (lift < 0.0f) {
+    double d2 = 0.0;
+    for (int c = 0; c < 3; ++c) d2 += double(grid.cell[c]) * double(grid.cell[c]);
+    lift = static_cast<float>(std::sqrt(d2));
+  }
+  const bool vn = m.normals.size() == m.verts.size();
+  // colours | verts | normals: the colours first, 16-byte aligned as rgba must be
+  const size_t oc = 0, ov = nv * 16, on = ov + nv * 12, end = on + (vn ? nv * 12 : 0);
+  char* buf = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf), end);
+  int rc = SDF_OK;
+  try {
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(buf + ov, m.verts.data(), nv * 12, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && vn)
+      e = hipMemcpyAsync(buf + on, m.normals.data(), nv * 12, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) {
+      sdf_point_shade out{};
+      out.rgba = reinterpret_cast<float*>(buf + oc);
+      shade_points(f, lights, light_flags, materials, reinterpret_cast<const float*>(buf + ov),
+                   vn ? reinterpret_cast<const float*>(buf + on) : nullptr,
+                   static_cast<int64_t>(nv), eye, lift, out, stream);
+      e = hipMemcpyAsync(colors.data(), buf + oc, nv * 16, hipMemcpyDeviceToHost, stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  } catch (const Error& err) {
+    rc = err.code;
+  }
+  (void)hipFree(buf);
+  check(rc, "sdf_shade_points");
+  check_hip(e, "bake");
+  return colors;
+}
+// A colour component as a byte by the RGBA8 rule of sdf_abi.h: trunc(min(max(c,
+// 0), 1) * 255 + 0.5) in fp32, NaN -> 0.
+inline unsigned char color_u8(float c) {
+  if (!(c == c)) return 0;
+  const float x = c < 0.0f ? 0.0f : (c > 1.0f ? 1.0f : c);
+  const volatile float y = x * 255.0f;   // rounded before the sum: no fusion
+  return static_cast<unsigned char>(y + 0.5f);
+}
+// A binary little-endian PLY file of the mesh: float x y z, float nx ny nz when
+// the mesh has normals, uchar red green blue when `colors` (4 floats per vertex)
+// has one per vertex, then the triangles (sdf3d_amd/meshio.py reads it back).
+inline void write_ply(const std::string& path, const Mesh& m,
+                      const std::vector<float>& colors = {}) {
+  FILE* fp = std::fopen(path.c_str(), "wb");
+  if (!fp) throw Error(SDF_E_INVALID_ARG, "cannot open " + path);
+  const size_t nv = m.verts.size() / 3, nt = m.tris.size() / 3;
+  const bool vn = m.normals.size() == m.verts.size() && nv > 0;
+  const bool vc = colors.size() == 4 * nv && nv > 0;
+  std::fprintf(fp, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\n"
+                   "property float x\nproperty float y\nproperty float z\n", nv);
+  if (vn) std::fprintf(fp, "property float nx\nproperty float ny\nproperty float nz\n");
+  if (vc) std::fprintf(fp, "property uchar red\nproperty uchar green\nproperty uchar blue\n");
+  std::fprintf(fp, "element face %zu\nproperty list uchar int vertex_indices\nend_header\n", nt);
+  for (size_t i = 0; i < nv; ++i) {
+    std::fwrite(&m.verts[3 * i], 4, 3, fp);
+    if (vn) std::fwrite(&m.normals[3 * i], 4, 3, fp);
+    if (vc) {
+      const unsigned char c[3] = {color_u8(colors[4 * i]), color_u8(colors[4 * i + 1]),
+                                  color_u8(colors[4 * i + 2])};
+      std::fwrite(c, 1, 3, fp);
+    }
+  }
+  for (size_t i = 0; i < nt; ++i) {
+    const unsigned char three = 3;
+    std::fwrite(&three, 1, 1, fp);
+    std::fwrite(&m.tris[3 * i], 4, 3, fp);
   }
   std::fclose(fp);
 }

@@ -89,7 +89,11 @@ extern "C" {
                                    likewise;
                                 still 12: sdf_validate_grad, sdf_sample_grad,
                                    sdf_grad_workspace_bytes (sdf_grad_out),
-                                   additions likewise */
+                                   additions likewise;
+                                still 12: sdf_validate_points and
+                                   sdf_shade_points (sdf_points,
+                                   sdf_point_shade, SDF_POINTS_*), additions
+                                   likewise */
 
 /* ---- status codes ------------------------------------------------------ */
 #define SDF_OK               0
@@ -240,6 +244,26 @@ typedef struct {
   int32_t flags;          /* SDF_RAYS_* */
   int32_t reserved;
 } sdf_rays;               /* 32 bytes */
+
+/* Shading at caller-supplied points (sdf_shade_points; "Points" below):
+ * device pointers. */
+#define SDF_POINTS_EYE 0x1      /* eye is set: the specular term is evaluated */
+typedef struct {
+  const float* points;    /* device, n x 3 packed fp32 */
+  const float* normals;   /* device, n x 3 packed fp32, optional: used as given */
+  int64_t n;
+  float eye[3];           /* with SDF_POINTS_EYE */
+  float lift;             /* finite, >= 0: P = Q + N lift */
+  int32_t flags;          /* SDF_POINTS_* */
+  int32_t reserved;       /* 0 */
+} sdf_points;             /* 48 bytes */
+typedef struct {
+  float*   rgba;      /* n x 4: the colour sum, alpha 1; 16-byte aligned */
+  float*   ao;        /* n: the occlusion term */
+  float*   shadow;    /* n x nlights: light i's soft-shadow factor sh_i */
+  float*   material;  /* n x 9: the blended amb, dif, ref */
+  int32_t* steps;     /* n x nlights: light i's shadow-march count */
+} sdf_point_shade;    /* 40 bytes; any pointer may be NULL, at least one is not */
 
 /* Isosurface meshes (sdf_mesh_count, sdf_mesh_emit; "Meshes" below) */
 #define SDF_MESH_DENSE 0x1          /* evaluate every brick: no distance-bound skipping (cross-check) */
@@ -634,9 +658,10 @@ typedef struct {
  *     ray data.
  *   - asynchronous on `stream`.  SDF_ABI_VERSION stays 12: detect the entry
  *     points by the symbol.
- *   - occlusion and soft-shadow queries, per-ray distance limits, sorting or
- *     compacting rays, tilings and several devices and an ambient-occlusion
- *     output are not offered; gradients are sdf_sample_grad ("Gradients"). */
+ *   - per-ray distance limits, sorting or compacting rays, tilings and several
+ *     devices are not offered; gradients are sdf_sample_grad ("Gradients"),
+ *     occlusion, soft shadows and shaded colours at points sdf_shade_points
+ *     ("Points"). */
 
 /* Rays (sdf_render_rays: the shading pipeline of "Environment" on rays of the
  * caller's own -- an orthographic view, a fisheye, a panorama, a stereo pair,
@@ -776,8 +801,73 @@ typedef struct {
  *   - asynchronous on `stream`.  SDF_ABI_VERSION stays 12: detect the entry
  *     points by the symbol.
  *   - marching cubes tables, sharp-feature (QEF) placement, mesh
- *     simplification, adaptive grids, several devices and vertex colours are
- *     not offered. */
+ *     simplification, adaptive grids and several devices are not offered;
+ *     vertex colours are sdf_shade_points at the vertices ("Points"). */
+
+/* Points (sdf_shade_points: the shading pipeline of "Materials" entered at a
+ * point of the caller's own instead of behind a primary march -- vertex colours
+ * for an exported mesh, lightmap texels, irradiance probes, a per-vertex
+ * occlusion term).  Entry i of every output belongs to point i.  The blocks
+ * above are reused word for word, so exact precision can be checked bit for bit
+ * (tests/points_ref.c states it over the CPU oracle).  Exact precision rounds
+ * every operation once and fuses nothing; fast precision may contract and uses
+ * the hardware reciprocal square root, as everywhere else:
+ *   - normal: Q = points[i].  With `normals` NULL, N is what sdf_sample returns
+ *     as the normal at Q (normal_mode, normal_eps); otherwise N = normals[i]
+ *     unchanged, unit or not.
+ *   - lift: P = Q when lift == 0 (the bits of Q); otherwise P.c = RN(Q.c + RN(N.c
+ *     lift)).  N is not evaluated again at P.  A surface-nets vertex lies up to
+ *     half a cell diagonal off the surface, often inside it, and a shadow march
+ *     that starts inside the solid means nothing: lift it out first.
+ *   - `ao` is the render's occlusion term at (P, N) when SDF_FLAG_AO is set and
+ *     ao_taps > 0, else 1.
+ *   - `material` is the "Materials" fold at P, all 9 components (amb, dif, ref);
+ *     for a Mandelbulb materials[0]'s.
+ *   - light i: incident = normalize(L_i - P).  sh_i is the render's shadow march
+ *     from o = P + N shadow_offset eps along incident when SDF_FLAG_SHADOW is
+ *     set, and its iteration count goes to `steps`; else sh_i = 1 and the count
+ *     is 0.  dif_i = clamp(N . incident, 0, 1) sh_i.  With SDF_POINTS_EYE: view =
+ *     normalize(eye - P), x_i = max(N . normalize(incident + view), 0), and
+ *     spec_i is the precision's own pow of "Lights".  Without the flag no view
+ *     is formed and spec_i = +0 enters the sum as a value.  `shadow` and `steps`
+ *     hold entry i * nlights + light.  With `shadow` or `steps` asked for, every
+ *     shadow march runs to the reference's break, as a render's with step
+ *     counts does; `rgba` has the same bits either way.
+ *   - `rgba` is the "Lights" / "Materials" colour sum with the point's blended
+ *     components, alpha 1.  The buffer must be 16-byte aligned (a point's colour
+ *     is stored as one word); the other outputs need their elements' 4 bytes.
+ *   - identity with the render: in exact precision, with `normals` NULL, lift 0
+ *     and eye = O_0, and with P_0 = O_0 + D_0 d formed as the render forms it,
+ *     `rgba` is sdf_render_materials's pixel bit for bit, `steps` for one light
+ *     its steps[..][1], and `ao` and dif channels 0 and 1 of SDF_FORMAT_SHADE32F.
+ *   - outputs not asked for cost nothing, each decision a uniform branch: no
+ *     light loop without rgba, shadow and steps; no fold without rgba and
+ *     material; no occlusion taps without rgba and ao.
+ *   - params: the march, shadow, normal, AO, precision and dispatch fields are
+ *     used.  width, height, samples and output_format are ignored: a copy with
+ *     those at sdf_defaults' values is what is validated, with a default camera.
+ *   - dispatch follows the queries': a built-in variant when the scene matches
+ *     one, under SDF_DISPATCH_AUTO a run-time specialised points kernel for any
+ *     other primitive list (counted by sdf_jit_count; the generic kernel with
+ *     SDF3D_JIT=0), GENERIC and UNCULLED as there.
+ *   - SDF_E_INVALID_ARG, decided before any device call (sdf_validate_points is
+ *     that check without the outputs): pts or out NULL; every output NULL; an
+ *     rgba that is not 16-byte aligned; NULL
+ *     points with n > 0; n < 0 or n > 2^30; unknown flag bits or a nonzero
+ *     reserved; a lift that is not finite, negative or above 1e15; with
+ *     SDF_POINTS_EYE an eye component that is not finite or above 1e15 in
+ *     magnitude; anything sdf_validate_materials rejects with a default camera
+ *     (its SDF_E_UNSUPPORTED cases, such as differing shininess, stay
+ *     SDF_E_UNSUPPORTED).  n = 0 is SDF_OK: nothing is launched, no buffer is
+ *     touched and no device is needed.
+ *   - device data: points must be finite and at most 1e15 in magnitude, the
+ *     caller's duty as under "Queries"; supplied normals are used as the
+ *     arithmetic says.  No address or loop bound depends on either.
+ *   - a wave shades 64 consecutive points: order them in coherent groups.
+ *   - asynchronous on `stream`.  SDF_ABI_VERSION stays 12: detect the entry
+ *     points by the symbol.
+ *   - reflections and an environment at points, per-point eyes, output formats
+ *     other than fp32 and several devices are not offered. */
 
 /* Gradients (sdf_sample_grad: how the scene function f changes with the points
  * and with the scene's own parameters -- fitting primitives to a point cloud,
@@ -1121,6 +1211,17 @@ int sdf_render_rays(const sdf_scene* scene, const sdf_light* lights, int32_t nli
                     void* stream);
 int sdf_camera_rays(const sdf_camera* camera, const sdf_params* params, float* origins,
                     float* dirs, void* stream);
+
+/* Shading at caller-supplied points ("Points" above).  Additions:
+ * SDF_ABI_VERSION stays 12, detect them by the symbol.  sdf_validate_points is
+ * the host-only check sdf_shade_points makes first (no device call). */
+int sdf_validate_points(const sdf_scene* scene, const sdf_light* lights, int32_t nlights,
+                        int32_t light_flags, const sdf_material* materials, int32_t nmaterials,
+                        const sdf_params* params, const sdf_points* pts);
+int sdf_shade_points(const sdf_scene* scene, const sdf_light* lights, int32_t nlights,
+                     int32_t light_flags, const sdf_material* materials, int32_t nmaterials,
+                     const sdf_params* params, const sdf_points* pts,
+                     const sdf_point_shade* out, void* stream);
 
 /* Isosurface meshes ("Meshes" above).  Additions: SDF_ABI_VERSION stays 12,
  * detect them by the symbol.  sdf_validate_mesh is the host-only check both

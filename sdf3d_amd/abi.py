@@ -21,6 +21,7 @@ ENV_SKY = 0x1         # SDF_ENV_SKY: a missed layer's colour is the sky along it
 ENV_SUN = 0x2         # SDF_ENV_SUN: with ENV_SKY, a glow around sun_dir
 ENV_FOG = 0x4         # SDF_ENV_FOG: linear distance fog on every layer that is not sky
 RAYS_UNIT = 0x1       # SDF_RAYS_UNIT: sdf_render_rays uses dirs as given (unit vectors)
+POINTS_EYE = 0x1      # SDF_POINTS_EYE: sdf_shade_points evaluates the specular term from `eye`
 MESH_DENSE = 0x1      # SDF_MESH_DENSE: sdf_mesh_count evaluates every brick (no skipping)
 
 # status codes
@@ -115,6 +116,20 @@ class sdf_rays(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class sdf_points(C.Structure):
+    """The points of sdf_shade_points: device pointers to n x 3 packed fp32
+    (normals may be NULL: the normal is evaluated at the point)."""
+    _fields_ = [("points", C.c_void_p), ("normals", C.c_void_p), ("n", C.c_int64),
+                ("eye", C.c_float * 3), ("lift", C.c_float), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class sdf_point_shade(C.Structure):
+    """Outputs of sdf_shade_points: device pointers, any may be NULL (not all)."""
+    _fields_ = [("rgba", C.c_void_p), ("ao", C.c_void_p), ("shadow", C.c_void_p),
+                ("material", C.c_void_p), ("steps", C.c_void_p)]
+
+
 class sdf_grid(C.Structure):
     """The lattice of sdf_mesh_count / sdf_mesh_emit: n cells of `cell` from `origin`."""
     _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float * 3), ("n", C.c_int32 * 3),
@@ -162,6 +177,7 @@ STRUCT_SIZES = {
     "sdf_light": 32, "sdf_material": 40, "sdf_params": 80, "sdf_tiling": 24,
     "sdf_driver_config": 36, "sdf_reflect": 16, "sdf_environment": 96, "sdf_hits": 32,
     "sdf_rays": 32, "sdf_grid": 48, "sdf_mesh_out": 48, "sdf_grad_out": 24,
+    "sdf_points": 48, "sdf_point_shade": 40,
 }
 MAX_QUERY = 1 << 30   # rays or points of one sdf_trace / sdf_sample call
 
@@ -246,6 +262,12 @@ SIGNATURES = {
                                   _P(sdf_material), C.c_int32, _P(sdf_reflect),
                                   _P(sdf_environment), _P(sdf_params), _P(sdf_rays), C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
+    "sdf_validate_points": (C.c_int, [_P(sdf_scene), _P(sdf_light), C.c_int32, C.c_int32,
+                                      _P(sdf_material), C.c_int32, _P(sdf_params),
+                                      _P(sdf_points)]),
+    "sdf_shade_points": (C.c_int, [_P(sdf_scene), _P(sdf_light), C.c_int32, C.c_int32,
+                                   _P(sdf_material), C.c_int32, _P(sdf_params), _P(sdf_points),
+                                   _P(sdf_point_shade), C.c_void_p]),
     "sdf_camera_rays": (C.c_int, [_P(sdf_camera), _P(sdf_params), C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
     "sdf_tiles_decode_checked": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _P(sdf_tiling),

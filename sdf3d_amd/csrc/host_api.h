@@ -95,6 +95,7 @@ struct RenderUnit {
   int (*query)(const QueryArgs& q, int variant, void* stream);   // by QueryArgs::kind
   int (*rays)(const RaysArgs& q, int variant, void* stream);     // sdf_render_rays
   int (*mesh)(const MeshArgs& m, int variant, void* stream, int emit);   // mesh_count / mesh_emit
+  int (*points)(const PointsArgs& q, int variant, void* stream);   // sdf_shade_points
   // one kernel each, in the units of the primitive scenes alone (null in the
   // Mandelbulb's): the ray generator of sdf_camera_rays, and the gradient
   // kernel followed by grad_reduce into `grad_prims`
@@ -117,6 +118,7 @@ int launch_render_jit(const RenderArgs& a, const RenderPlan& plan, void* stream)
 int launch_query_jit(const QueryArgs& q, const RenderPlan& plan, void* stream);
 int launch_rays_jit(const RaysArgs& q, const RenderPlan& plan, void* stream);
 int launch_mesh_jit(const MeshArgs& m, const RenderPlan& plan, void* stream, int emit);
+int launch_points_jit(const PointsArgs& q, const RenderPlan& plan, void* stream);
 int jit_compiled_count();
 
 // One kernel launch for a prepared scene, through the built-in kernel of the
@@ -231,6 +233,30 @@ inline bool rays_args_fit(const RaysArgs& q) {
   return q.n > 0 && q.n <= (1ll << 30) && q.in0 && q.in1 && q.a.rgba && q.r.on &&
          (q.flags & ~SDF_RAYS_UNIT) == 0 && lights_fit(r) && materials_fit(r) && reflect_fit(r) &&
          env_fit(r);
+}
+
+// ---- the points kernels' launch geometry and argument contract --------------
+// Shared by launch_points_scene and launch_points_jit.  64 points to a wave;
+// sdf_shade_points holds n to 2^30, so the grid fits.
+inline dim3 points_grid(const PointsArgs& q) {
+  return dim3((unsigned)((q.n + 64 * kWgWaves - 1) / (64 * kWgWaves)));
+}
+// every shadow march runs to the reference's break (the STEPS instantiation)
+inline bool points_steps(const PointsArgs& q) { return q.shadow || q.steps; }
+// what a points launch may be handed: the lights and the table of a materials
+// render (a Mandelbulb: no table), at most 2^30 points with a buffer, an output
+inline bool points_args_fit(const PointsArgs& q) {
+  RenderArgs r{};
+  r.a.format = SDF_FORMAT_RGBA32F;
+  r.a.prim_count = q.a.prim_count;
+  r.a.scene_kind = q.a.scene_kind;
+  r.l.n = q.l.n;
+  r.m.n = q.m.n;
+  const bool prims = q.a.scene_kind == SDF_SCENE_PRIMITIVES;
+  return q.n > 0 && q.n <= (1ll << 30) && q.points &&
+         (q.rgba || q.ao || q.shadow || q.material || q.steps) &&
+         (q.flags & ~SDF_POINTS_EYE) == 0 && q.l.n > 0 && lights_fit(r) && materials_fit(r) &&
+         (prims ? q.m.n == q.a.prim_count && q.m.n > 0 : q.m.n == 0);
 }
 
 // ---- the query kernels' launch geometry and argument contract ---------------

@@ -195,6 +195,32 @@ struct RaysArgs {
   int32_t flags;  // SDF_RAYS_*
   int32_t reserved;
 };
+// ---- shading at caller-supplied points (sdf_shade_points) ----------------------
+// The argument block of the points kernels (render_kernel.inc shade_points),
+// their own: `a` carries the scene, the march and shading parameters (its camera,
+// frame size and outputs are unused; a.ao_taps is 0 when no output needs the
+// occlusion term); l and m are a materials render's.  `points` holds n x 3
+// packed floats, `normals` the same or null (the normal's taps run at the
+// point).  Which outputs are written is a uniform branch on their pointers
+// (any may be null, not all): rgba n x 4, ao n, shadow and steps n x l.n,
+// material n x 9.
+struct PointsArgs {
+  KernelArgs a;   // first: the scene evaluators read it at the start of the segment
+  LightsArgs l;
+  MaterialArgs m;   // n = 0: a Mandelbulb, the one material of `a`
+  const float* points;
+  const float* normals;
+  float* rgba;
+  float* ao;
+  float* shadow;
+  float* material;
+  int32_t* steps;
+  long long n;    // points
+  float eye[3];   // with SDF_POINTS_EYE
+  float lift;
+  int32_t flags;  // SDF_POINTS_*
+  int32_t reserved;
+};
 // ---- isosurface meshes (sdf_mesh_count, sdf_mesh_emit) -------------------------
 // The workspace of a mesh extraction (sdf_abi.h "Meshes"), O(bricks): per
 // brick of 8 x 8 x 8 cells its 512-bit activity mask (word l2: the 8 x 8 slice
@@ -309,6 +335,7 @@ static_assert(sizeof(KernelArgs) <= 4096, "KernelArgs exceeds the 4 KiB kernel-a
 static_assert(sizeof(RenderArgs) <= 4096, "RenderArgs exceeds the 4 KiB kernel-argument limit");
 static_assert(sizeof(QueryArgs) <= 4096, "QueryArgs exceeds the 4 KiB kernel-argument limit");
 static_assert(sizeof(RaysArgs) <= 4096, "RaysArgs exceeds the 4 KiB kernel-argument limit");
+static_assert(sizeof(PointsArgs) <= 4096, "PointsArgs exceeds the 4 KiB kernel-argument limit");
 static_assert(sizeof(MeshArgs) <= 4096, "MeshArgs exceeds the 4 KiB kernel-argument limit");
 static_assert(sizeof(GradArgs) <= 4096, "GradArgs exceeds the 4 KiB kernel-argument limit");
 // Tiles a wave takes per queue request, queues per launch (workgroup b uses

@@ -1644,8 +1644,10 @@ __device__ __forceinline__ void trace_march(KA& A, const Scene& scene, const V3 
 }
 
 // The normal and the ambient occlusion at the point S.P a march ended on
-// (`mst` its culling state there).
-template <class Scene>
+// (`mst` its culling state there).  NORMAL = false: the normal is S.N as the
+// caller set it; AO = false: no occlusion taps, S.ao = 1 (shade_points takes
+// the two at different points).
+template <class Scene, bool NORMAL = true, bool AO = true>
 __device__ __forceinline__ void trace_shape(KA& A, const Scene& scene, MarchState& mst,
                                             Surface& S) {
   const V3 P = S.P;
@@ -1654,7 +1656,9 @@ __device__ __forceinline__ void trace_shape(KA& A, const Scene& scene, MarchStat
   // normal, :134-155 (central) or tetrahedral
   V3 N;
   const float h = A.normal_eps;
-  if (SDF_ABLATE_NO_NORMAL) {
+  if constexpr (!NORMAL) {
+    N = S.N;
+  } else if (SDF_ABLATE_NO_NORMAL) {
     N = mk(0.0f, 1.0f, 0.0f);   // stage ablation only (tools/ablate.py): wrong pixels
   } else if (A.normal_mode == SDF_NORMAL_TETRA) {
     // taps at |h (+-1,+-1,+-1)| = |h| sqrt 3 from P: path length tt
@@ -1673,6 +1677,11 @@ __device__ __forceinline__ void trace_shape(KA& A, const Scene& scene, MarchStat
   // ambient occlusion (extension), evaluated before the shadow march so its
   // taps are side trips from P (independent of the shadow: same result)
   float ao = 1.0f;
+  if constexpr (!AO) {
+    S.N = N;
+    S.ao = 1.0f;
+    return;
+  }
   const bool use_ao = (A.flags & SDF_FLAG_AO) && A.ao_taps > 0;
   if (use_ao) {
     float occ = 0.0f, sca = 1.0f;
@@ -1787,10 +1796,19 @@ __device__ __forceinline__ void trace_ray_path(KA& A, const Scene& scene, const 
 // The terms of the light at Lp for the surface S: dif = clamp(N.L, 0, 1) *
 // shadow and spec_x = max(N.H, 0); `mst` is the culling state at P (advanced
 // along the shadow ray), `ss` counts the shadow march's iterations from 0.
-template <bool STEPS, class Scene, class View>
+//
+// `hook` (surface_colour's, handed on) sees what a render keeps to itself:
+// NoLightHook, the default, is empty, and every kernel without one of its own
+// compiles to the code it had before there were hooks (PointsHook below: what a
+// hook has).
+struct NoLightHook {
+  static constexpr bool kOn = false;   // every use of a hook stands behind if constexpr (kOn)
+};
+template <bool STEPS, class Scene, class View, class Hook = NoLightHook>
 __device__ __forceinline__ void light_terms(KA& A, const Scene& scene, const View& V,
                                             const Surface& S, const V3 Lp, MarchState& mst,
-                                            int& ss, float& dif_out, float& spec_x_out) {
+                                            int& ss, float& dif_out, float& spec_x_out,
+                                            const Hook* hook = nullptr) {
   const V3 cam = S.cam, P = S.P, N = S.N;
   const float tP = S.tP;
   const float max_dist = A.max_dist, eps = A.eps;
@@ -1915,6 +1933,7 @@ __device__ __forceinline__ void light_terms(KA& A, const Scene& scene, const Vie
     }
     sh = gclamp(s, 0.0f, 1.0f);
   }
+  if constexpr (Hook::kOn) hook->shadow(sh);
   dif_out = gclamp(ndl, 0.0f, 1.0f) * sh;
   spec_x_out = spec_x;
 }
@@ -2043,18 +2062,27 @@ __device__ __forceinline__ float4 shade_pixel_materials(KA& A, const KARG Lights
 //
 // It is shade_pixel_materials's (FOLD) and shade_pixel_lights's statements
 // after trace_surface, for the reflect and env kernels' layers.
-template <bool STEPS, bool FOLD, class Scene, class View>
+//
+// `hook` (NoLightHook: none) may skip the fold and the loop, take spec_i = +0
+// for a surface without an eye, and see the blended components and each
+// light's shadow factor and count: shade_points's outputs.
+template <bool STEPS, bool FOLD, class Scene, class View, class Hook = NoLightHook>
 __device__ __forceinline__ void surface_colour(KA& A, const KARG LightsArgs& L,
                                                const KARG MaterialArgs& M, const Scene& scene,
                                                const View& V, const Surface& S,
                                                const MarchState& mst, int& ss, float (&acc)[3],
-                                               float (&mr)[3]) {
+                                               float (&mr)[3], const Hook* hook = nullptr) {
   float md[3];
   if constexpr (FOLD) {
     float m[9];
 #pragma unroll
     for (int c = 0; c < 9; c++) m[c] = M.m[0][c];
-    scene.material_fold(S.P, M, m);
+    if constexpr (Hook::kOn) {
+      if (hook->fold()) scene.material_fold(S.P, M, m);
+      hook->material(m);
+    } else {
+      scene.material_fold(S.P, M, m);
+    }
 #pragma unroll
     for (int c = 0; c < 3; c++) {
       acc[c] = shade_ambient(shade_tint(L.la, m[c]), S.ao);
@@ -2073,13 +2101,28 @@ __device__ __forceinline__ void surface_colour(KA& A, const KARG LightsArgs& L,
   const int n = L.n;
 #pragma unroll 1
   for (int i = 0; i < n; i++) {
+    if constexpr (Hook::kOn) {
+      if (!hook->lights()) break;   // a uniform: no light loop at all
+    }
     MarchState ms = mst;
     int ssi = 0;
     float dif, spec_x;
-    light_terms<STEPS>(A, scene, V, S, mk(L.pos[i][0], L.pos[i][1], L.pos[i][2]), ms, ssi, dif,
-                       spec_x);
+    if constexpr (Hook::kOn) {
+      light_terms<STEPS>(A, scene, V, S, mk(L.pos[i][0], L.pos[i][1], L.pos[i][2]), ms, ssi, dif,
+                         spec_x, hook);
+      hook->light(i, ssi);
+    } else {
+      light_terms<STEPS>(A, scene, V, S, mk(L.pos[i][0], L.pos[i][1], L.pos[i][2]), ms, ssi, dif,
+                         spec_x);
+    }
     ss += ssi;
-    const float spec = spec_pow<SDF_EXACT>(spec_x, A.shininess);
+    float spec;
+    if constexpr (Hook::kOn) {
+      spec = 0.0f;
+      if (hook->eye()) spec = spec_pow<SDF_EXACT>(spec_x, A.shininess);
+    } else {
+      spec = spec_pow<SDF_EXACT>(spec_x, A.shininess);
+    }
 #pragma unroll
     for (int c = 0; c < 3; c++) {
       const float d = tint ? shade_tint(dif, L.color[i][c]) : dif;
@@ -2982,6 +3025,129 @@ __global__ __launch_bounds__(64 * kWgWaves) __attribute__((amdgpu_waves_per_eu(S
 void render_rays_env(RaysArgs args) {
   (void)args;
   rays_body<Scene, STEPS, FOLD, true>();
+}
+
+// ---- shading at caller-supplied points (sdf_abi.h "Points": sdf_shade_points) ---
+// The materials pipeline entered at a point instead of behind a primary march:
+// the Surface {P, N, ao} is built from memory and the normal's taps, then
+// surface_colour -- the very fold and light loop of the reflect layers, with the
+// eye in S.cam -- gives the colour, and its hook hands out what a render keeps
+// to itself.  The view light_terms takes tells it only whether every shadow
+// march runs to the reference's break (STEPS: `shadow` or `steps` asked for).
+struct PointsView {
+  const void* full;   // non-null: they do
+  __device__ __forceinline__ const void* steps() const { return full; }
+};
+// Whether the fold and the loop run and whether there is an eye (uniforms), and
+// where the lane's point has its material, shadow factors and counts stored.
+struct PointsHook {
+  static constexpr bool kOn = true;
+  bool want_fold, want_lights, want_eye;
+  float* material_out;   // the point's 9 components, or null
+  float* shadow_out;     // the point's L.n factors, or null
+  int32_t* steps_out;    // the point's L.n counts, or null
+  mutable float sh = 1.0f;
+  __device__ __forceinline__ bool fold() const { return want_fold; }
+  __device__ __forceinline__ void material(const float (&m)[9]) const {
+    if (material_out) {
+#pragma unroll
+      for (int c = 0; c < 9; c++) material_out[c] = m[c];
+    }
+  }
+  __device__ __forceinline__ bool lights() const { return want_lights; }
+  __device__ __forceinline__ bool eye() const { return want_eye; }
+  __device__ __forceinline__ void shadow(float s) const { sh = s; }
+  __device__ __forceinline__ void light(int i, int count) const {
+    if (shadow_out) shadow_out[i] = sh;
+    if (steps_out) steps_out[i] = count;
+  }
+};
+
+// lane = point i of the buffers, a wave 64 consecutive points, loaded as
+// rays_body loads its rays (3 dwords per lane at stride 12: a wave's loads and
+// stores cover one contiguous span).  Every decision on what is evaluated is a
+// uniform of the argument block.  A ragged last wave leaves with its lanes
+// beyond n idle, as there.  No address or loop bound depends on point data.
+template <class Scene, bool STEPS, bool FOLD>
+__device__ __forceinline__ void points_body() {
+  const KARG char* const seg = (const KARG char*)__builtin_amdgcn_kernarg_segment_ptr();
+  const KARG PointsArgs& Q = *(const KARG PointsArgs*)seg;
+  KA& A = Q.a;
+  const long long i = (long long)blockIdx.x * (64 * kWgWaves) + threadIdx.x;
+  if (i >= Q.n) return;
+  const Scene scene(A);
+  const KARG LightsArgs& L = *(const KARG LightsArgs*)(seg + __builtin_offsetof(PointsArgs, l));
+  const KARG MaterialArgs& M = *(const KARG MaterialArgs*)(seg + __builtin_offsetof(PointsArgs, m));
+  const bool want_rgba = Q.rgba != nullptr;
+  const bool want_lights = want_rgba || Q.shadow != nullptr || Q.steps != nullptr;
+  const bool want_fold = want_rgba || Q.material != nullptr;
+  // the occlusion taps run only when an output needs them (the host zeroes
+  // a.ao_taps otherwise)
+  const bool want_ao = (A.flags & SDF_FLAG_AO) && A.ao_taps > 0;
+  const float lift = Q.lift;
+
+  const float* const q = Q.points + 3 * i;
+  MarchState mst;
+  Surface S;
+  S.P = mk(q[0], q[1], q[2]);
+  S.tP = 0.0f;   // a fresh culling state at path length 0, as sdf_sample's normal has
+  S.N = mk(0.0f, 0.0f, 0.0f);
+  if (Q.normals) {
+    const float* const nn = Q.normals + 3 * i;
+    S.N = mk(nn[0], nn[1], nn[2]);
+  } else if (want_lights || want_ao || lift != 0.0f) {
+    trace_shape<Scene, true, false>(A, scene, mst, S);
+  }
+  if (lift != 0.0f) {
+    // P = Q + N lift; the culling state of the taps at Q is not one of P
+    S.P = mk(S.P.x + S.N.x * lift, S.P.y + S.N.y * lift, S.P.z + S.N.z * lift);
+    mst = MarchState();
+  }
+  trace_shape<Scene, false, true>(A, scene, mst, S);
+  S.cam = mk(Q.eye[0], Q.eye[1], Q.eye[2]);
+  S.ray = mk(0.0f, 0.0f, 0.0f);
+  S.d = 0.0f;
+  if (Q.ao) Q.ao[i] = S.ao;
+  if (!want_lights && !want_fold) return;
+
+  PointsHook hook{want_fold, want_lights, want_rgba && (Q.flags & SDF_POINTS_EYE) != 0,
+                  Q.material ? Q.material + 9 * i : nullptr,
+                  Q.shadow ? Q.shadow + (long long)L.n * i : nullptr,
+                  Q.steps ? Q.steps + (long long)L.n * i : nullptr};
+  float C[3], mr[3];
+  int ss = 0;
+  const PointsView V{Q.steps ? (const void*)Q.steps : (const void*)Q.shadow};
+  surface_colour<STEPS, FOLD>(A, L, M, scene, V, S, mst, ss, C, mr, &hook);
+  if constexpr (!FOLD) {
+    // a Mandelbulb: the one material of the launch
+    if (Q.material) {
+      float* const o = Q.material + 9 * i;
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        o[c] = A.mat_amb[c];
+        o[3 + c] = A.mat_dif[c];
+        o[6 + c] = A.mat_ref[c];
+      }
+    }
+  }
+  if (want_rgba) reinterpret_cast<float4*>(Q.rgba)[i] = make_float4(C[0], C[1], C[2], 1.0f);
+}
+
+// the points instantiations (sdf_shade_points), with every shadow march run to
+// the reference's break (STEPS) and without.  No path state lives across the
+// light loop, so the registers are the materials kernels': CSG8 exact 96 VGPRs
+// at their 5 waves per SIMD; CSG8 fast at their 6 waves 80 VGPRs and 12-28
+// bytes of scratch per lane, at 5 waves no scratch, and no points kernel is
+// to use scratch, so 5 in both precisions (DESIGN.md, shade_points: the
+// register figures)
+#ifndef SDF_POINTS_WAVES_PER_EU
+#define SDF_POINTS_WAVES_PER_EU 5
+#endif
+template <class Scene, bool STEPS, bool FOLD>
+__global__ __launch_bounds__(64 * kWgWaves) __attribute__((amdgpu_waves_per_eu(SDF_POINTS_WAVES_PER_EU, SDF_POINTS_WAVES_PER_EU)))
+void shade_points(PointsArgs args) {
+  (void)args;
+  points_body<Scene, STEPS, FOLD>();
 }
 
 #if !SDF_TU_BULB && !defined(__HIPCC_RTC__)

@@ -220,6 +220,30 @@ static int launch_rays(const RaysArgs& q, int variant, void* stream) {
   });
 }
 
+// one launch of scene kernel S for sdf_shade_points: 64 points to a wave, the
+// instantiation whose shadow marches all run to the reference's break only
+// when `shadow` or `steps` is asked for.  It refuses what the kernels would
+// trust blindly (host_api.h points_args_fit).
+template <class S>
+static int launch_points_scene(const PointsArgs& q, hipStream_t s) {
+  constexpr bool kFold = !SDF_TU_BULB;   // a primitive list to fold materials over
+  if (q.n <= 0) return 0;
+  if (!points_args_fit(q)) return (int)hipErrorInvalidValue;
+  const dim3 block(64 * kWgWaves), grid(points_grid(q));
+  (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
+  if (points_steps(q))
+    hipLaunchKernelGGL((SDF_NS::shade_points<S, true, kFold>), grid, block, 0, s, q);
+  else
+    hipLaunchKernelGGL((SDF_NS::shade_points<S, false, kFold>), grid, block, 0, s, q);
+  return (int)hipGetLastError();
+}
+
+static int launch_points(const PointsArgs& q, int variant, void* stream) {
+  return with_scene(variant, [&](auto scene) {
+    return launch_points_scene<typename decltype(scene)::type>(q, (hipStream_t)stream);
+  });
+}
+
 #if !SDF_TU_BULB
 // sdf_camera_rays: the render's grid of 8x8 tiles over width x height; one
 // kernel, whatever the variant
@@ -262,13 +286,13 @@ static int launch_frames(const FramesArgs& a, int variant, void* stream, int nbl
 #if SDF_TU_BULB
 const RenderUnit& bulb_unit() {
   static const RenderUnit u = {launch_render, launch_frames, launch_query, launch_rays,
-                               launch_mesh,   nullptr,       nullptr};
+                               launch_mesh,   launch_points, nullptr,      nullptr};
   return u;
 }
 #else
 const RenderUnit& unit() {
-  static const RenderUnit u = {launch_render, launch_frames,      launch_query, launch_rays,
-                               launch_mesh,   launch_camera_rays, launch_grad};
+  static const RenderUnit u = {launch_render, launch_frames, launch_query,       launch_rays,
+                               launch_mesh,   launch_points, launch_camera_rays, launch_grad};
   return u;
 }
 #endif

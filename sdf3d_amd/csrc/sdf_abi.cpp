@@ -1260,16 +1260,19 @@ int validate_query(const sdf_scene* scene, const sdf_camera* camera, const sdf_p
 // culling bounds and the march parameters (and `camera` hoisted where the call
 // has one), no outputs, and beside it the variant, the precision, the JIT flag
 // and the signature.  A render's plan, made with sdf_defaults' camera, light
-// and material standing in for what such a call does not have.
+// and material standing in for what such a call does not have (`light`,
+// `material`: the call's own, where it shades -- sdf_shade_points).
 int scene_plan(const sdf_scene* scene, const sdf_camera* camera, const sdf_params& q,
-               sdf::RenderPlan* plan) {
+               sdf::RenderPlan* plan, const sdf_light* light = nullptr,
+               const sdf_material* material = nullptr) {
   sdf_camera c;
   sdf_light l;
   sdf_material m;
   sdf_defaults(nullptr, &c, &l, &m, nullptr, 0, 0);
   int unused = 0;   // a render's plan refuses a null framebuffer
-  const int rc = sdf::make_render_plan(scene, camera ? camera : &c, &l, &m, &q, nullptr, &unused,
-                                       nullptr, plan);
+  const int rc = sdf::make_render_plan(scene, camera ? camera : &c, light ? light : &l,
+                                       material ? material : &m, &q, nullptr, &unused, nullptr,
+                                       plan);
   if (rc == SDF_OK) plan->a.rgba = nullptr;
   return rc;
 }
@@ -1638,6 +1641,84 @@ int sdf_camera_rays(const sdf_camera* camera, const sdf_params* params, float* o
   a->out0 = origins;
   a->out1 = dirs;
   return sdf::launch_built_in(*plan, &sdf::RenderUnit::camera_rays, *a, stream);
+}
+
+// ---- shading at caller-supplied points (sdf_abi.h "Points") --------------------
+static_assert(sizeof(sdf_points) == 48, "sdf_points layout");
+static_assert(sizeof(sdf_point_shade) == 40, "sdf_point_shade layout");
+
+namespace {
+// The params a points call is validated and run with: the caller's, with the
+// frame's fields (a list of points has none) at sdf_defaults' values.
+sdf_params points_params(const sdf_params& p) {
+  sdf_params d;
+  sdf_defaults(nullptr, nullptr, nullptr, nullptr, &d, 0, 0);
+  sdf_params q = p;
+  q.width = d.width;
+  q.height = d.height;
+  q.samples = d.samples;
+  q.output_format = d.output_format;
+  return q;
+}
+}  // namespace
+
+int sdf_validate_points(const sdf_scene* scene, const sdf_light* lights, int32_t nlights,
+                        int32_t light_flags, const sdf_material* materials, int32_t nmaterials,
+                        const sdf_params* params, const sdf_points* pts) {
+  if (!pts || !scene || !params) return SDF_E_INVALID_ARG;
+  if ((pts->flags & ~SDF_POINTS_EYE) || pts->reserved != 0) return SDF_E_INVALID_ARG;
+  if (pts->n < 0 || pts->n > kMaxQuery || (pts->n > 0 && !pts->points)) return SDF_E_INVALID_ARG;
+  if (!(pts->lift >= 0.0f && pts->lift <= 1e15f)) return SDF_E_INVALID_ARG;
+  if (pts->flags & SDF_POINTS_EYE)
+    for (int c = 0; c < 3; ++c)
+      if (!(std::fabs(pts->eye[c]) <= 1e15f)) return SDF_E_INVALID_ARG;
+  sdf_camera c;
+  sdf_defaults(nullptr, &c, nullptr, nullptr, nullptr, 0, 0);
+  const sdf_params q = points_params(*params);
+  return sdf_validate_materials(scene, &c, lights, nlights, light_flags, materials, nmaterials, &q,
+                                nullptr);
+}
+
+int sdf_shade_points(const sdf_scene* scene, const sdf_light* lights, int32_t nlights,
+                     int32_t light_flags, const sdf_material* materials, int32_t nmaterials,
+                     const sdf_params* params, const sdf_points* pts,
+                     const sdf_point_shade* out, void* stream) {
+  if (!out) return SDF_E_INVALID_ARG;
+  if (!out->rgba && !out->ao && !out->shadow && !out->material && !out->steps)
+    return SDF_E_INVALID_ARG;
+  // the kernels store a point's colour as one 16-byte word
+  if (reinterpret_cast<uintptr_t>(out->rgba) % 16 != 0) return SDF_E_INVALID_ARG;
+  int rc = sdf_validate_points(scene, lights, nlights, light_flags, materials, nmaterials, params,
+                               pts);
+  if (rc != SDF_OK) return rc;
+  if (pts->n == 0) return SDF_OK;   // nothing to launch, no device needed
+  // the scene's plan (scene blocks, culling bounds, march and shading parameters,
+  // dispatch; no camera, no frame, no outputs) under light 0 and material 0,
+  // with the lights and the table of a materials launch and the point buffers
+  std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
+  rc = scene_plan(scene, nullptr, points_params(*params), plan.get(), &lights[0], &materials[0]);
+  if (rc != SDF_OK) return rc;
+  fill_lights(*plan, lights, nlights, light_flags);
+  if (scene->kind == SDF_SCENE_PRIMITIVES) fill_materials(*plan, materials, nmaterials);
+  std::unique_ptr<sdf::PointsArgs> a(new sdf::PointsArgs());
+  a->a = plan->a;
+  // the occlusion taps run only for an output that needs them
+  if (!out->rgba && !out->ao) a->a.ao_taps = 0;
+  a->l = plan->lights;
+  a->m = plan->materials;
+  a->points = pts->points;
+  a->normals = pts->normals;
+  a->rgba = out->rgba;
+  a->ao = out->ao;
+  a->shadow = out->shadow;
+  a->material = out->material;
+  a->steps = out->steps;
+  a->n = pts->n;
+  for (int i = 0; i < 3; ++i) a->eye[i] = (pts->flags & SDF_POINTS_EYE) ? pts->eye[i] : 0.0f;
+  a->lift = pts->lift;
+  a->flags = pts->flags;
+  a->reserved = 0;
+  return sdf::launch_planned(*plan, sdf::launch_points_jit, &sdf::RenderUnit::points, *a, stream);
 }
 
 int sdf_jit_count(void) { return sdf::jit_compiled_count(); }

@@ -9,6 +9,7 @@ all arithmetic runs in the HIP kernels of ``libsdf3d.so``.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import NamedTuple
 
 from . import abi
@@ -120,6 +121,18 @@ class Grad(NamedTuple):
     dist: object
     grad_points: object
     grad_prims: object
+
+
+class Shade(NamedTuple):
+    """What ``Renderer.shade_points`` returns (sdf_point_shade): device tensors,
+    None for an output that was not asked for.  `rgba` (n, 4), `ao` (n,),
+    `shadow` (n, L) and `steps` (n, L) int32 for the L lights, `material` (n, 9):
+    the blended amb, dif and ref."""
+    rgba: object
+    ao: object
+    shadow: object
+    material: object
+    steps: object
 
 
 def grid(origin, cell, n, iso: float = 0.0, dense: bool = False) -> abi.sdf_grid:
@@ -576,6 +589,78 @@ class Renderer:
                 self._stream(stream))
         abi.check(rc, "sdf_render_rays")
         return rgba, st
+
+    # ---- shading at caller-supplied points (sdf_abi.h "Points") -------------
+    def shade_points(self, frame: Frame, points, normals=None, eye=None, lift: float = 0.0,
+                     lights=None, materials=None, rgba: bool = True, ao: bool = False,
+                     shadow: bool = False, material: bool = False, steps: bool = False,
+                     stream=None, light_flags: int = 0) -> "Shade":
+        """Lights, shadows, occlusion and materials of ``frame.scene`` at n points
+        of the caller's own (sdf_shade_points), without a primary march: `points`
+        is a contiguous float32 (n, 3) tensor on this renderer's device, `normals`
+        the same (used as given) or None (the normal is evaluated at the point).
+        `eye` (three floats) switches the specular term on; without it there is
+        none.  `lift` moves each point along its normal before anything is
+        shaded (vertices of ``mesh`` lie up to half a cell diagonal inside the
+        surface).  `lights`, `light_flags` and `materials` are ``render``'s, with
+        its defaults.  Returns ``Shade(rgba, ao, shadow, material, steps)``, None
+        for what was not asked for; what is not asked for is not computed.  A
+        wave shades 64 consecutive points.  Asynchronous on `stream`."""
+        torch = self.torch
+        pts = self._n3(points, "points")
+        n = pts.shape[0]
+        nrm = None if normals is None else self._n3(normals, "normals")
+        if nrm is not None and nrm.shape != pts.shape:
+            raise ValueError("points and normals must have the same shape")
+        if not (rgba or ao or shadow or material or steps):
+            raise ValueError("shade_points needs at least one output")
+        if materials is None:
+            prims = frame.scene.kind == abi.SCENE_PRIMITIVES
+            materials = [frame.material] * (frame.scene.count if prims else 1)
+        materials = list(materials)
+        marr = (abi.sdf_material * max(len(materials), 1))(*materials)
+        lights = [frame.light] if lights is None else list(lights)
+        arr = (abi.sdf_light * max(len(lights), 1))(*lights)
+        nl = len(lights)
+
+        def new(want, tail, dtype=torch.float32):
+            return torch.empty((n, *tail), dtype=dtype, device=self.device) if want else None
+        out = Shade(new(rgba, (4,)), new(ao, ()), new(shadow, (nl,)), new(material, (9,)),
+                    new(steps, (nl,), torch.int32))
+        if n == 0:
+            return out
+        p = abi.sdf_points()
+        p.points = pts.data_ptr()
+        p.normals = nrm.data_ptr() if nrm is not None else None
+        p.n = n
+        if eye is not None:
+            p.flags = abi.POINTS_EYE
+            for c in range(3):
+                p.eye[c] = float(eye[c])
+        p.lift = float(lift)
+        ps = abi.sdf_point_shade(*[C.c_void_p(x.data_ptr()) if x is not None else None
+                                   for x in out])
+        with self._on_device():
+            rc = self.lib.sdf_shade_points(C.byref(frame.scene), arr, nl, int(light_flags), marr,
+                                           len(materials), C.byref(frame.params), C.byref(p),
+                                           C.byref(ps), self._stream(stream))
+        abi.check(rc, "sdf_shade_points")
+        return out
+
+    def bake(self, frame: Frame, mesh: "Mesh", cell, eye=None, lift=None, lights=None,
+             materials=None, stream=None, light_flags: int = 0):
+        """Vertex colours of a ``Mesh`` of ``frame.scene`` extracted with cells of
+        size `cell` (a scalar, or one per axis): ``shade_points`` at the vertices,
+        with the mesh's normals when it has them.  The default `lift` is the
+        length of the cell diagonal: a surface-nets vertex lies within half a
+        diagonal of the surface, so one diagonal puts it outside for a field
+        whose Lipschitz constant is 1.  Returns a float32 (V, 4) tensor."""
+        cell = (cell,) * 3 if isinstance(cell, (int, float)) else tuple(cell)
+        if lift is None:
+            lift = math.sqrt(sum(float(c) * float(c) for c in cell))
+        return self.shade_points(frame, mesh.verts, normals=mesh.normal, eye=eye, lift=lift,
+                                 lights=lights, materials=materials, stream=stream,
+                                 light_flags=light_flags).rgba
 
     def camera_rays(self, frame: Frame, stream=None):
         """The rays ``render`` marches (sdf_camera_rays): (origins, dirs), each a
