@@ -20,6 +20,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from cases import custom_scene
 from sdf3d_amd import abi
 
 SMOOTH = (abi.OP_SMOOTH_UNION, abi.OP_SMOOTH_SUBTRACT, abi.OP_SMOOTH_INTERSECT)
@@ -225,11 +226,10 @@ def coverage_frame(kind: int, op: int):
 
 
 def named_frame(name: str):
-    """REF, C1, C4 (built-in dispatch) or jit<seed>: test_gpu_jit.custom_scene
-    with that test's generator and primitive count, on the generic kernel."""
+    """REF, C1, C4 (built-in dispatch) or jit<seed>: cases.custom_scene
+    with test_gpu_jit.py's generator and primitive count, on the generic kernel."""
     from sdf3d_amd import scenes
     if name.startswith("jit"):
-        from test_gpu_jit import custom_scene
         seed = int(name[3:])
         f = custom_scene(np.random.default_rng(100 + seed), 2 + seed % 7)
         f.params.dispatch = abi.DISPATCH_UNCULLED

@@ -25,7 +25,9 @@ import ctypes as C
 
 import numpy as np
 
+import fast_paths as FP
 import oracle
+from cases import random_csg8
 from sdf3d_amd import abi
 
 f32 = np.float32
@@ -340,9 +342,7 @@ RENDER_CASES = ["C4-p0", "C4-p1", "csg8-1", "csg8-4", "C4-generic", "C4-carved",
 
 def base_frame(case, wh=WH):
     """The untranslated frame of a render case, exact precision."""
-    import fast_paths as FP
     if case.startswith("csg8-"):
-        from test_gpu_parity import random_csg8
         seed = int(case.split("-")[1])
         f = random_csg8(np.random.default_rng(seed), [0.5, 1.0, 2.5][seed % 3],
                         [0.05, 0.3, 1.0][(seed // 3) % 3])

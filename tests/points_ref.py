@@ -15,8 +15,11 @@ from typing import NamedTuple
 
 import numpy as np
 
+import materials_ref as MR
 import oracle
-from sdf3d_amd import abi
+from cases import LIGHTS, points_scene
+from gpu_support import fenced, same, untouched
+from sdf3d_amd import abi, scenes
 
 f32 = np.float32
 HERE = Path(__file__).resolve().parent
@@ -118,3 +121,114 @@ def hit_points(cam, rays, d):
     d = np.asarray(d, dtype=f32)[..., None]
     with np.errstate(all="ignore"):
         return (np.asarray(cam, f32) + (np.asarray(rays, f32) * d).astype(f32)).astype(f32)
+
+
+# ---- the kernel's side: what tests/test_gpu_points.py and tools/points_probe.py share ------------
+
+EXACT, FAST = abi.PRECISION_EXACT, abi.PRECISION_FAST
+A = abi.DISPATCH_AUTO
+CLR = abi.LIGHTS_COLOR
+W, H = MR.SHAPE
+N = W * H
+OUTS = ("rgba", "ao", "shadow", "material", "steps")
+GUARD = 64   # guard rows in front of and behind every output (a wave's worth)
+
+
+def the_frame(name, pose, prec=EXACT, dispatch=A):
+    if name in ("PJ", "PJC"):
+        return points_scene(prec, counted=name == "PJC")
+    f = scenes.config(name, W, H, precision=prec, pose=pose)
+    f.params.dispatch = dispatch
+    return f
+
+
+def mats_of(f, pal=True):
+    if f.scene.kind != abi.SCENE_PRIMITIVES:
+        return [f.material]
+    return scenes.palette(f.scene.count) if pal else [f.material] * f.scene.count
+
+
+def kernel_shade(rd, f, P, normals=None, eye=None, lift=0.0, lights=None, flags=0,
+                 materials=None, outs=OUTS):
+    """sdf_shade_points into fenced buffers (gpu_support.fenced) whose GUARD
+    rows, in front of every output and behind it, are checked: a RefShade of
+    NumPy arrays (None for an output not in `outs`; dif is not an output)."""
+    import torch
+    dev = lambda a: torch.from_numpy(np.array(a, dtype=f32).reshape(-1, 3)).to(rd.device)
+    pts = dev(P)
+    n = pts.shape[0]
+    nrm = None if normals is None else dev(normals)
+    lights = [f.light] if lights is None else list(lights)
+    materials = mats_of(f, False) if materials is None else list(materials)
+    nl = len(lights)
+    larr = (abi.sdf_light * nl)(*lights)
+    marr = (abi.sdf_material * len(materials))(*materials)
+    shapes = {"rgba": ((n, 4), torch.float32), "ao": ((n,), torch.float32),
+              "shadow": ((n, nl), torch.float32), "material": ((n, 9), torch.float32),
+              "steps": ((n, nl), torch.int32)}
+    mid = {k: fenced(torch, rd.device, *shapes[k], guard=GUARD, front=True) for k in outs}
+    p = abi.sdf_points()
+    p.points, p.n, p.lift = pts.data_ptr(), n, float(lift)
+    p.normals = nrm.data_ptr() if nrm is not None else None
+    if eye is not None:
+        p.flags = abi.POINTS_EYE
+        for c in range(3):
+            p.eye[c] = float(eye[c])
+    ps = abi.sdf_point_shade(*[mid[k].data_ptr() if k in mid else None for k in OUTS])
+    rc = rd.lib.sdf_shade_points(C.byref(f.scene), larr, nl, int(flags), marr, len(materials),
+                                 C.byref(f.params), C.byref(p), C.byref(ps), None)
+    torch.cuda.synchronize()
+    assert rc == abi.SDF_OK, rc
+    for k, b in mid.items():
+        assert untouched(torch, b), f"{k}: entries in front of the buffer or past its end written"
+    got = {k: (mid[k].cpu().numpy() if k in mid else None) for k in OUTS}
+    return RefShade(got["rgba"], got["ao"], got["shadow"], got["material"], got["steps"], None)
+
+
+_HITS = {}
+
+
+def frame_hits(rd, name, pose):
+    """(P (851, 3), eye) of the exact frame: P_0 = O_0 + D_0 d formed on the host
+    in unfused fp32 from trace_camera's t and camera_rays, as the render forms
+    it."""
+    if (name, pose) not in _HITS:
+        assert (W, H) == (37, 23) and N == 851 == 13 * 64 + 19
+        f = the_frame(name, pose)
+        t = rd.trace_camera(f, normal=False, prim=False, steps=False).t
+        o, d = rd.camera_rays(f)
+        rd.torch.cuda.synchronize()
+        o, d, t = o.cpu().numpy(), d.cpu().numpy(), t.cpu().numpy()
+        P = hit_points(o, d, t).reshape(N, 3)
+        eye = o.reshape(N, 3)[0].copy()
+        assert same(o.reshape(N, 3), np.tile(eye, (N, 1)))
+        P.setflags(write=False)
+        _HITS[(name, pose)] = (P, eye)
+    return _HITS[(name, pose)]
+
+
+FAST_CASES = [("C4", 0, False), ("C3", 2, True), ("REF", 0, True)]
+
+
+def fast_deviation(rd, name, pose, pal):
+    """The largest absolute deviation of each output of the fast kernel from the
+    reference replayed at the kernel's own shadow counts, over all 851 hit
+    points under three coloured lights (`material`: where no hard decision of
+    the fold is closer than materials_ref.GAP), and how many points that is."""
+    f = the_frame(name, pose, FAST)
+    mats = mats_of(f, pal)
+    P, eye = frame_hits(rd, name, pose)
+    got = kernel_shade(rd, f, P, eye=eye, lights=LIGHTS[:3], flags=CLR, materials=mats)
+    ref = shade(the_frame(name, pose), P, eye=eye, lights=LIGHTS[:3], light_flags=CLR,
+                materials=mats, steps=got.steps)
+    assert np.array_equal(ref.steps, np.minimum(got.steps, f.params.max_steps))
+    dev = {}
+    for k in ("rgba", "ao", "shadow"):
+        a, b = getattr(got, k).astype(np.float64), getattr(ref, k).astype(np.float64)
+        assert np.isfinite(a).all() and np.isfinite(b).all(), k
+        dev[k] = float(np.abs(a - b).max())
+    gap = np.array([MR.fold_at(f.scene, mats, *map(float, p))[2] for p in P], dtype=f32)
+    far = ~(gap < f32(MR.GAP))
+    dev["material"] = float(np.abs(got.material[far].astype(np.float64) -
+                                   ref.material[far].astype(np.float64)).max())
+    return dev, int(far.sum())

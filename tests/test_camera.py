@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import oracle
+from cases import nav_views
 from sdf3d_amd import scenes
 from sdf3d_amd.camera import Arcball
 
@@ -39,26 +40,6 @@ def test_pan_translates_view():
     v = a.update(0.1, dx=0.02, dy=-0.01, pan=True)
     m = v.reshape(4, 4).T
     assert m[0, 3] == pytest.approx(5.0 * 0.02) and m[1, 3] == pytest.approx(5.0 * -0.01)
-
-
-def nav_input(a: Arcball, i: int):
-    """The scripted navigation input of frame i (examples/sdf_main.cpp nav_input)."""
-    dt = 1.0 / 60.0
-    ph = i % 90
-    if ph < 30:
-        return a.update(dt, 0.004, 0.0015, orbit=True)
-    if ph < 45:
-        return a.update(dt, -0.002, 0.001, pan=True)
-    if ph < 60:
-        return a.update(dt)
-    if ph < 80:
-        return a.gamepad(dt, 0.8, -0.5, 0.2, 0.35)
-    return a.gamepad(dt, 0.1, 0.0, 0.0, 0.0)
-
-
-def nav_views(n: int) -> np.ndarray:
-    a = Arcball()
-    return np.stack([nav_input(a, i) for i in range(n)])
 
 
 def test_gamepad_deadzone_and_rate():

@@ -11,10 +11,12 @@ import materials_ref as MR
 import mesh_ref as M
 import oracle
 import query_ref as Q
+from cases import C4_GRID
+from cases import query_frame as frame_of
+from fast_paths import FAST_BOUND_N, FAST_BOUND_T, MESH_BOUND_N
+from fast_paths import MESH_BOUND_V as FAST_BOUND_V
+from gpu_support import ndiff
 from sdf3d_amd import abi, scenes
-from test_gpu_mesh import C4_GRID
-from test_gpu_mesh import FAST_BOUND_N as MESH_BOUND_N, FAST_BOUND_V
-from test_gpu_query import FAST_BOUND_N, FAST_BOUND_T, frame_of
 
 f32 = np.float32
 
@@ -97,8 +99,8 @@ def test_exact_results_pass_every_check(rays, traced, sampled, meshed):
     m = M.fast_deviation(meshed["carved"], meshed["carved"], C4_GRID[1])
     assert m["same_connectivity"] and m["vertex_over_cell"] == 0 and m["normal"] == 0
     assert m["prim_wrong"] == 0
-    assert FP.bits_differ(sampled["carved"][0], sampled["carved"][0]) == 0
-    assert FP.bits_differ(sampled["carved"][0], sampled["C4"][0]) > 0
+    assert ndiff(sampled["carved"][0], sampled["carved"][0]) == 0
+    assert ndiff(sampled["carved"][0], sampled["C4"][0]) > 0
 
 
 def test_point_deviation_counts_nonfinite_values():

@@ -197,14 +197,6 @@ def test_native_driver_multirank(tmp_path, nproc, cfg, shares, batch, streams, n
         assert max(counts) == 0, counts
 
 
-def _read_ppm(path):
-    import numpy as np
-    data = open(path, "rb").read()
-    parts = data.split(b"\n", 3)
-    w, h = map(int, parts[1].split())
-    return np.frombuffer(parts[3], dtype=np.uint8).reshape(h, w, 3)
-
-
 @pytest.mark.parametrize("world", [2, 3])
 def test_cpp_driver_multirank_arcball(tmp_path, world):
     """examples/sdf_main.cpp as `world` processes on this GPU (RANK /
@@ -221,7 +213,8 @@ def test_cpp_driver_multirank_arcball(tmp_path, world):
     import oracle
     from parity import assert_parity, compare, quantize
     from sdf3d_amd import Renderer, abi, scenes
-    from test_camera import nav_views
+    from cases import nav_views
+    from gpu_support import read_ppm
     exe = ROOT / "sdf3d_amd" / "bin" / "sdf_main"
     frames, W, H = 40, 160, 96
     out = tmp_path / "f.ppm"
@@ -240,7 +233,7 @@ def test_cpp_driver_multirank_arcball(tmp_path, world):
     for p, (so, se) in zip(procs, outs):
         assert p.returncode == 0, se[-2000:]
     assert f"rank 0 of {world}" in outs[0][0]
-    img = _read_ppm(out)
+    img = read_ppm(out)
     f = scenes.config("C3", W, H, precision=abi.PRECISION_EXACT)   # sdf_main's default
     scenes.set_view(f, nav_views(frames)[-1])
     rd = Renderer("cuda:0")

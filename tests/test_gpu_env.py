@@ -8,28 +8,28 @@ reference in fast precision -- on every dispatch path, for every output format,
 tiling, a schedule and supersampling.
 
 Shape 37 x 23 (partial 8 x 8 tiles in x and y, a last block of 7 rows); the
-supersampled cases use test_gpu_ssaa.py's shapes.  Every render writes into
+supersampled cases use cases.SHAPES.  Every render writes into
 buffers followed by sentinel rows, which must survive, and every case is
 rendered with and without a steps buffer, which must not change the colours.
 The environment is env_ref.environment: scenes.sky() with fog from 1 to 4 in
 the horizon's colour."""
 import ctypes as C
 import os
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import env_ref as ER
+import gpu_support as G
 import materials_ref as MR
 import reflect_ref as RR
 import ssaa_ref
-from parity import quantize
+from cases import LIGHTS, env_scene, fast_case, mats_of, the_frame, walk_of
+from fast_paths import ALL, WEIGHT
+from fast_paths import ENV_BOUND as FAST_BOUND
+from gpu_support import (FILL, SHAPES, bits, fenced, hi_frame, ndiff, read_ppm, rgba_of, same,
+                         sdf_main, untouched)
 from sdf3d_amd import abi, renderer as R, scenes
-from test_gpu_reflect import LIGHTS, RIGS, frame_of, mats_of, ndiff, rgba_of
-from test_gpu_ssaa import (FILL, SHAPES, _guarded, _sentinel, bits, hi_frame, owned_row_index,
-                           read_ppm, same)
 
 pytestmark = pytest.mark.gpu
 
@@ -37,91 +37,27 @@ f32 = np.float32
 EXACT, FAST = abi.PRECISION_EXACT, abi.PRECISION_FAST
 PRECS = [EXACT, FAST]
 SKY, SUN, FOG = abi.ENV_SKY, abi.ENV_SUN, abi.ENV_FOG
-ALL = SKY | SUN | FOG
 FLAG_SETS = [SKY, SKY | SUN, FOG, ALL]
-WEIGHT = abi.REFLECT_WEIGHT
 FRAMES = MR.FRAMES + [("C5", 0)]
-# Fast precision's composite against the reference replayed at the kernel's
-# per-layer step counts, on the pixels away from the miss boundary
-# (env_ref.near_boundary): the largest absolute deviation of a channel measured
-# on an MI355X over C4 pose 0, C3 pose 2 (palette) and REF pose 0 (one
-# material), bounces 1 and 2, SKY | SUN | FOG (profiles/env_C4.json
-# fast_deviation, DESIGN.md "Environment"), and the bound asserted: 4 x that,
-# the headroom test_gpu_reflect.py and test_gpu_materials.py give theirs.
-FAST_MEASURED = 1.253e-4
-FAST_BOUND = 4 * FAST_MEASURED
+RIGS = [(1, 0), (3, abi.LIGHTS_COLOR)]
 
-
-def env_scene(prec, wh=ER.SHAPE, counted=False):
-    """round box, plane, torus (smooth union) -- `counted`: torus, plane, round
-    box (smooth union): no built-in variant, so SDF_DISPATCH_AUTO compiles its
-    kernel at run time (hipRTC); signatures no other test file uses, and
-    `counted` only the test that counts its compilations."""
-    f = scenes.config("C3", *wh, precision=prec, pose=2)
-    C.memset(C.addressof(f.scene.prims), 0, C.sizeof(f.scene.prims))
-    f.scene.count = 3
-    box = (abi.PRIM_ROUND_BOX, -0.4, 0.25, 0.1, 0.2, 0.2, 0.2, 0.05)
-    tor = (abi.PRIM_TORUS, 0.45, 0.12, 0.0, 0.25, 0.08)
-    first, last = (tor, box) if counted else (box, tor)
-    scenes._prim(f.scene, 0, first[0], abi.OP_UNION, 0.0, *first[1:])
-    scenes._prim(f.scene, 1, abi.PRIM_PLANE, abi.OP_UNION, 0.0, 0.0, 1.0, 0.0, 0.0)
-    scenes._prim(f.scene, 2, last[0], abi.OP_SMOOTH_UNION, 0.08, *last[1:])
-    return f
-
-
-def the_frame(name, pose, prec=EXACT, dispatch=None):
-    if name == "EJ":
-        f = env_scene(prec)
-        f.params.dispatch = abi.DISPATCH_AUTO if dispatch is None else dispatch
-        return f
-    return frame_of(name, pose, prec, dispatch)
+def shading(reflect, env, materials=None, lights=None, flags=0):
+    return dict(reflect=reflect, env=env, materials=materials, lights=lights, light_flags=flags)
 
 
 def render(rd, frame, reflect, env, materials=None, lights=None, flags=0, t=None, steps=True,
            schedule=None):
-    """Renderer.render(env=) (sdf_render_env; env None: sdf_render_reflect)
-    into sentinel-filled buffers with guard rows behind them, which are
-    checked."""
-    import torch
-    p = frame.params
-    rows = R.buffer_rows(p.height, t)
-    shape = (rows, p.width, R.channels(p.output_format))
-    buf = _guarded(torch, rd.device, shape, R.torch_dtype(p.output_format))
-    sshape = R.steps_shape(frame, t)
-    sbuf = _guarded(torch, rd.device, sshape, torch.int32) if steps else None
-    rd.render(frame, t, out=buf[:rows], steps=sbuf[:sshape[0]] if steps else False,
-              schedule=schedule, lights=lights, light_flags=flags, materials=materials,
-              reflect=reflect, env=env)
-    torch.cuda.synchronize()
-    assert _sentinel(torch, buf[rows:]), "colour buffer: rows past the end were written"
-    if steps:
-        assert _sentinel(torch, sbuf[sshape[0]:]), "steps buffer: rows past the end were written"
-    return buf[:rows].cpu().numpy(), (sbuf[:sshape[0]].cpu().numpy() if steps else None)
+    """gpu_support.render with `env`: sdf_render_env; env None: sdf_render_reflect."""
+    return G.render(rd, frame, t, steps, schedule, **shading(reflect, env, materials, lights, flags))
 
 
 def both(rd, frame, reflect, env, materials=None, lights=None, flags=0, t=None):
-    a, _ = render(rd, frame, reflect, env, materials, lights, flags, t, steps=False)
-    b, st = render(rd, frame, reflect, env, materials, lights, flags, t, steps=True)
-    assert same(a, b), "renders with and without a steps buffer differ"
-    return a, st
+    return G.both(rd, frame, t, **shading(reflect, env, materials, lights, flags))
 
 
 # ---- the reference: one walk per case, the environments applied to it -------------
 
-_WALK, _REF = {}, {}
-
-
-def walk_of(name, pose, bounces, n, flags):
-    key = (name, pose, bounces, n, flags)
-    if key not in _WALK:
-        f = the_frame(name, pose)
-        w = RR.walk(f, mats_of(f), bounces, 1.0, LIGHTS[:n])
-        w["C"] = RR.layer_colours(f, w, flags)
-        for a in w.values():
-            if isinstance(a, np.ndarray):
-                a.setflags(write=False)
-        _WALK[key] = w
-    return _WALK[key]
+_REF = {}
 
 
 def reference(name, pose, bounces, n, flags, eflags, fog=ER.FOG_RANGE):
@@ -184,34 +120,13 @@ def test_exact_layers_and_weights_equal_reference(renderer, name, pose, eflags):
 
 # ---- 2. both precisions, from the kernel's own pieces ----------------------------
 
-def own_layers(rd, f, bounces, strength, env, mats, lights, flags):
-    """The kernel's own layer colours, weights and steps: C, W [H, W, J, 3],
-    steps [H, W, J, 2], alive [H, W, J] (a traced layer took a primary step)."""
-    Cs, Ws, Ss = [], [], []
-    for j in range(bounces + 1):
-        cj, sj = both(rd, f, RR.reflect(bounces, strength, j), env, mats, lights, flags)
-        wj, wsj = both(rd, f, RR.reflect(bounces, strength, j, WEIGHT), env, mats, lights, flags)
-        assert np.array_equal(sj, wsj)
-        assert (cj[..., 3] == 1).all() and (wj[..., 3] == 1).all()
-        Cs.append(cj[..., :3])
-        Ws.append(wj[..., :3])
-        Ss.append(sj)
-    Cj, Wj, Sj = (np.stack(v, axis=2) for v in (Cs, Ws, Ss))
-    alive = Sj[..., 0] > 0
-    # a path that has ended leaves zeros
-    for a in (Cj, Wj):
-        assert (bits(a[~alive]) == 0).all()
-    assert (Sj[~alive] == 0).all()
-    return Cj, Wj, Sj, alive
-
-
 @pytest.mark.parametrize("prec", PRECS)
 @pytest.mark.parametrize("name,pose,n,flags", [("C4", 0, 2, abi.LIGHTS_COLOR), ("SIX", 2, 1, 0),
                                                ("C5", 0, 2, abi.LIGHTS_COLOR)])
 def test_composite_is_the_fold_of_own_layers(renderer, name, pose, n, flags, prec):
     f = the_frame(name, pose, prec)
     mats, lights, env = mats_of(f), LIGHTS[:n], ER.environment(ALL)
-    Cj, Wj, Sj, alive = own_layers(renderer, f, 3, 0.75, env, mats, lights, flags)
+    Cj, Wj, Sj, alive = G.own_layers(lambda r: both(renderer, f, r, env, mats, lights, flags), 3, 0.75)
     assert alive[:, :, 0].all() and (bits(Wj[:, :, 0]) == bits(np.ones(3, f32))).all()
     assert alive[:, :, 1].mean() > 0.02
     out, st = both(renderer, f, RR.reflect(3, 0.75), env, mats, lights, flags)
@@ -245,20 +160,21 @@ def test_nothing_switched_on_is_sdf_render_reflect(renderer, fmt, prec):
     marr, nm = MR.marr(mats)
     want, want_st = both(renderer, f, r, None, mats, lights, abi.LIGHTS_COLOR)
     for steps in (False, True):
-        buf = _guarded(torch, renderer.device, shape, R.torch_dtype(fmt))
-        sbuf = _guarded(torch, renderer.device, (p.height, p.width, 2), torch.int32)
+        buf = fenced(torch, renderer.device, shape, R.torch_dtype(fmt))
+        sbuf = fenced(torch, renderer.device, (p.height, p.width, 2), torch.int32)
         rc = renderer.lib.sdf_render_env(
             C.byref(f.scene), C.byref(f.camera), larr, 3, abi.LIGHTS_COLOR, marr, nm, C.byref(r),
             None, C.byref(p), None, C.c_void_p(buf.data_ptr()),
             C.c_void_p(sbuf.data_ptr()) if steps else None, None, None)
         assert rc == abi.SDF_OK
         torch.cuda.synchronize()
-        assert same(buf[:p.height].cpu().numpy(), want) and _sentinel(torch, buf[p.height:])
+        assert same(buf.cpu().numpy(), want) and untouched(torch, buf)
+        assert untouched(torch, sbuf)
         if steps:
-            assert np.array_equal(sbuf[:p.height].cpu().numpy(), want_st)
-            assert _sentinel(torch, sbuf[p.height:])
+            assert np.array_equal(sbuf.cpu().numpy(), want_st)
         else:
-            assert _sentinel(torch, sbuf), "a null steps pointer: nothing is written"
+            assert (bits(sbuf.cpu().numpy()) == FILL).all(), \
+                "a null steps pointer: nothing is written"
 
 
 @pytest.mark.parametrize("prec", PRECS)
@@ -267,20 +183,11 @@ def test_term_streams_with_nothing_switched_on(renderer, prec):
     f = the_frame("C4", 0, prec)
     f.params.output_format = abi.FORMAT_TILES
     mats = [type(f.material).from_buffer_copy(f.material) for _ in range(f.scene.count)]
-    w, h = f.params.width, f.params.height
-    a, b = (torch.zeros(R.tiles_bytes(w, h), dtype=torch.uint8, device=renderer.device)
-            for _ in range(2))
-    renderer.render(f, out=a, lights=[LIGHTS[1]], materials=mats, reflect=(0, 1.0))
-    renderer.render(f, out=b, lights=[LIGHTS[1]], materials=mats, reflect=(0, 1.0),
-                    env=ER.environment(0))
-    torch.cuda.synchronize()
-    n = R.tiles_stream_bytes(a)
-    assert n == R.tiles_stream_bytes(b) and n > abi.TILES_HEADER_BYTES
-    assert torch.equal(a[:n], b[:n])
+    kw = dict(lights=[LIGHTS[1]], materials=mats, reflect=(0, 1.0))
+    a, b, n = G.tiles_streams(renderer, f, kw, dict(kw, env=ER.environment(0)))
     for fl in FLAG_SETS:
         with pytest.raises(abi.SdfError) as e:
-            renderer.render(f, out=b, lights=[LIGHTS[1]], materials=mats, reflect=(0, 1.0),
-                            env=ER.environment(fl))
+            renderer.render(f, out=b, env=ER.environment(fl), **kw)
         assert e.value.code == abi.SDF_E_UNSUPPORTED
     torch.cuda.synchronize()
     assert torch.equal(a[:n], b[:n]), "a refused render wrote to its buffer"
@@ -375,7 +282,7 @@ def test_runtime_specialised_scene_compiles_one_kernel(renderer, prec):
     out2, st = render(renderer, f, RR.reflect(2, 0.75), env, mats, lights, steps=True)
     assert same(out2, out) and np.array_equal(st, want_st)
     assert count() - before == (2 if jit else 0)
-    Cj, Wj, Sj, alive = own_layers(renderer, f, 2, 0.75, env, mats, lights, 0)
+    Cj, Wj, Sj, alive = G.own_layers(lambda r: both(renderer, f, r, env, mats, lights, 0), 2, 0.75)
     assert same(out, RR.composite(Cj, Wj, alive, prec)) and np.array_equal(st, Sj.sum(axis=2))
     assert count() - before == (2 if jit else 0)
     # nothing switched on is the reflect kernel of this scene: another kernel
@@ -400,11 +307,7 @@ def test_formats_convert_the_composite(renderer, prec):
     assert np.abs(full - plain).max() > 0.1
     if prec == EXACT:
         assert same(full, reference("C4", 0, 2, 2, abi.LIGHTS_COLOR, ALL)[0])
-    for fmt in (abi.FORMAT_RGBA16F, abi.FORMAT_RGBA8, abi.FORMAT_RGB32F):
-        g = f.copy()
-        g.params.output_format = fmt
-        out, _ = both(renderer, g, r, env, mats, lights, abi.LIGHTS_COLOR)
-        assert same(out, quantize(full, fmt)), fmt
+    G.check_formats(renderer, f, full, **shading(r, env, mats, lights, abi.LIGHTS_COLOR))
 
 
 @pytest.mark.parametrize("fmt", [abi.FORMAT_TILES, abi.FORMAT_SHADE32F])
@@ -434,25 +337,9 @@ def test_tilings(renderer, world, shares, prec):
     f = the_frame("C3", 2, prec)
     mats, lights, flags, env = mats_of(f), LIGHTS[:2], abi.LIGHTS_COLOR, ER.environment(ALL)
     r = RR.reflect(2, 1.0)
-    w, h = f.params.width, f.params.height
-    whole, whole_st = both(renderer, f, r, env, mats, lights, flags)
+    whole, _ = G.check_tilings(renderer, f, world, shares, **shading(r, env, mats, lights, flags))
     if prec == EXACT:
         assert same(whole, reference("C3", 2, 2, 2, flags, ALL)[0])
-    seen = np.zeros(h, dtype=int)
-    for rank in range(world):
-        t = R.tiling(rank, world, 8, shares=shares)
-        rows = owned_row_index(h, t)
-        assert len(rows) == R.owned_rows(h, t)
-        seen[rows] += 1
-        out, st = both(renderer, f, r, env, mats, lights, flags, t)
-        assert out.shape == (len(rows), w, 4)
-        assert same(out, whole[rows]) and np.array_equal(st, whole_st[rows])
-        tf = R.tiling(rank, world, 8, frame_rows=True, shares=shares)
-        fr, fr_st = both(renderer, f, r, env, mats, lights, flags, tf)
-        other = np.setdiff1d(np.arange(h), rows)
-        assert same(fr[rows], whole[rows]) and np.array_equal(fr_st[rows], whole_st[rows])
-        assert (bits(fr[other]) == FILL).all() and (bits(fr_st[other]) == FILL).all()
-    assert (seen == 1).all()
 
 
 @pytest.mark.parametrize("prec", PRECS)
@@ -460,17 +347,7 @@ def test_scheduled(renderer, prec):
     f = the_frame("C3", 2, prec)
     mats, lights, env = mats_of(f), LIGHTS[:2], ER.environment(ALL)
     r = RR.reflect(2, 1.0)
-    ref, ref_st = both(renderer, f, r, env, mats, lights)
-    sch = renderer.schedule(f.params.height, period=1)
-    try:
-        for _ in range(3):
-            out, st = render(renderer, f, r, env, mats, lights, steps=True, schedule=sch)
-            assert same(out, ref) and np.array_equal(st, ref_st)
-            out, _ = render(renderer, f, r, env, mats, lights, steps=False, schedule=sch)
-            assert same(out, ref)
-        assert sorted(sch.order()) == list(range((f.params.height + 7) // 8))
-    finally:
-        sch.close()
+    G.check_scheduled(renderer, f, **shading(r, env, mats, lights))
 
 
 _HI = {}
@@ -511,22 +388,13 @@ def test_supersampled(renderer, name, s, prec):
 
 # ---- 6. fast precision near the reference -------------------------------------------
 
-def fast_case(name, dispatch=None):
-    """(frame in fast precision, materials).  `dispatch` None: the frame's own
-    launch path (a built-in variant, EJ's run-time specialised kernel, the
-    Mandelbulb's unit).  REF and C5 take the one-material form."""
-    f = the_frame(name, {"C4": 0, "C3": 2, "REF": 0, "EJ": 2, "C5": 0}[name], FAST, dispatch)
-    mats = (RR.materials_for(f) if name in ("REF", "C5") else MR.palette_for(f))
-    return f, mats
-
-
 def fast_deviation(rd, name, bounces):
     """(largest deviation, pixels left out, pixels): the fast composite against
     the reference replayed at the kernel's own per-layer step counts, on the
     pixels away from the miss boundary, where the layers traced must agree."""
     f, mats = fast_case(name)
     lights, env = [LIGHTS[0]], ER.environment(ALL)
-    _, _, Sj, alive = own_layers(rd, f, bounces, 1.0, env, mats, lights, 0)
+    _, _, Sj, alive = G.own_layers(lambda r: both(rd, f, r, env, mats, lights, 0), bounces, 1.0)
     out, st = both(rd, f, RR.reflect(bounces, 1.0), env, mats, lights, 0)
     assert np.array_equal(st, Sj.sum(axis=2))
     return ER.fast_deviation(f, mats, lights, env, bounces, out, Sj, alive)
@@ -555,8 +423,6 @@ def test_fast_is_near_the_reference(renderer, name, bounces):
 # ---- 7. the C++ host program -------------------------------------------------------
 
 def test_cpp_host_program_sky_and_fog_options(renderer, tmp_path):
-    exe = Path(__file__).resolve().parent.parent / "sdf3d_amd" / "bin" / "sdf_main"
-    assert exe.exists(), "build() must produce sdf3d_amd/bin/sdf_main"
     f = scenes.config("C3", 160, 90, precision=EXACT)                 # sdf_main's default
     scenes.set_view(f, scenes.orbit_view(180.0, 0.0))                 # frame 1 of 2: yaw 180
     f.params.output_format = abi.FORMAT_RGBA8
@@ -565,8 +431,7 @@ def test_cpp_host_program_sky_and_fog_options(renderer, tmp_path):
     plain, _ = render(renderer, f, RR.reflect(2, 1.0), None, None, [f.light], 0, steps=False)
     assert not same(want, plain)
     out = tmp_path / "f.ppm"
-    r = subprocess.run([str(exe), "--sky", "--fog", "1,4", "--reflect", "2", "160", "90", "2",
-                        str(out), "csg8"], capture_output=True, text=True, timeout=120)
+    r = sdf_main("--sky", "--fog", "1,4", "--reflect", "2", "160", "90", "2", out, "csg8")
     assert r.returncode == 0, r.stderr
     img = read_ppm(out)
     assert img.shape == (90, 160, 3)
@@ -575,7 +440,6 @@ def test_cpp_host_program_sky_and_fog_options(renderer, tmp_path):
     env = scenes.sky(0, fog=(0.5, 3.0, (0.25, 0.5, 0.75)))
     pal = scenes.palette(8)
     fogged, _ = render(renderer, f, None, env, pal, [f.light], 0, steps=False)
-    r = subprocess.run([str(exe), "160", "90", "2", str(out), "csg8", "--palette", "--fog",
-                        "0.5,3,0.25,0.5,0.75"], capture_output=True, text=True, timeout=120)
+    r = sdf_main("160", "90", "2", out, "csg8", "--palette", "--fog", "0.5,3,0.25,0.5,0.75")
     assert r.returncode == 0, r.stderr
     assert np.array_equal(read_ppm(out), fogged[::-1, :, :3])

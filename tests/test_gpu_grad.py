@@ -21,6 +21,7 @@ import pytest
 import torch
 
 import grad_ref
+from gpu_support import PAD, fenced, untouched, with_precision
 from sdf3d_amd import abi, scenes
 from sdf3d_amd import autograd as ag
 
@@ -29,29 +30,22 @@ pytestmark = pytest.mark.gpu
 FRAMES = grad_ref.all_frames()
 POINTS = grad_ref.cube_points(200)
 SENTINEL = 12345.0
-PAD = 64
 FLOOR = grad_ref.FLOOR
 BOUND = {abi.PRECISION_EXACT: 4.0, abi.PRECISION_FAST: 8.0}
 PRECISIONS = [abi.PRECISION_EXACT, abi.PRECISION_FAST]
 GRID_CAPACITY = 1024 * 256      # lanes of the capped grid
 
 
-def with_precision(frame, prec):
-    f = frame.copy()
-    f.params.precision = prec
-    return f
-
-
 def raw_call(rd, frame, pts, upstream=None, dist=True, grad_points=True, grad_prims=True,
              workspace=True):
-    """sdf_sample_grad on buffers that are each followed by PAD sentinel
-    elements, which must survive; grad_prims starts filled with sentinels.  Returns
+    """sdf_sample_grad on fenced buffers (PAD guard elements behind each, which
+    must survive); every buffer starts filled with SENTINEL.  Returns
     (dist, grad_points, grad_prims) as CPU numpy arrays (None when not asked for)."""
     n = pts.shape[0]
     dev = rd.device
 
     def buf(want, m):
-        return torch.full((m + PAD,), SENTINEL, dtype=torch.float32, device=dev) if want else None
+        return fenced(torch, dev, (m,), torch.float32, guard=PAD).fill_(SENTINEL) if want else None
     d, gp, gt = buf(dist, n), buf(grad_points, 3 * n), buf(grad_prims, 256)
     nbytes = int(rd.lib.sdf_grad_workspace_bytes(n)) if (grad_prims and workspace) else 0
     ws = buf(nbytes > 0, nbytes // 4)
@@ -65,13 +59,12 @@ def raw_call(rd, frame, pts, upstream=None, dist=True, grad_points=True, grad_pr
     abi.check(rc, "sdf_sample_grad")
     torch.cuda.synchronize()
     res = []
-    for x, m in ((d, n), (gp, 3 * n), (gt, 256), (ws, nbytes // 4)):
+    for x in (d, gp, gt, ws):
         if x is None:
             res.append(None)
             continue
-        h = x.cpu().numpy()
-        assert np.all(h[m:] == SENTINEL), "a store went past the end of its buffer"
-        res.append(h[:m])
+        assert untouched(torch, x), "a store went past the end of its buffer"
+        res.append(x.cpu().numpy())
     if res[1] is not None:
         res[1] = res[1].reshape(n, 3)
     if res[2] is not None:

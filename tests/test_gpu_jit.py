@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+from cases import custom_scene
 from parity import assert_parity, compare
 from sdf3d_amd import abi, scenes
 
@@ -27,30 +28,6 @@ def gpu(rd, frame, steps=True):
 
 def jit_count(rd):
     return rd.lib.sdf_jit_count()
-
-
-def custom_scene(rng, n, w=160, h=90):
-    """n random primitives after the plane, random kinds and (union-family or
-    CSG) ops: signatures no built-in variant has."""
-    f = scenes.config("C3", w, h)
-    f.scene.count = 1 + n
-    kinds = [abi.PRIM_SPHERE, abi.PRIM_BOX, abi.PRIM_ROUND_BOX, abi.PRIM_TORUS,
-             abi.PRIM_CAPSULE, abi.PRIM_CYLINDER]
-    for i in range(1, 1 + n):
-        p = f.scene.prims[i]
-        p.kind = int(rng.choice(kinds))
-        p.op = int(rng.choice([abi.OP_UNION, abi.OP_SMOOTH_UNION, abi.OP_SMOOTH_UNION,
-                               abi.OP_SUBTRACT, abi.OP_INTERSECT, abi.OP_SMOOTH_SUBTRACT]))
-        p.k = float(rng.uniform(0.02, 0.4))
-        c = rng.uniform(-0.8, 0.8, 3) + np.array([0.0, 0.45, 0.0])
-        vals = list(c) + list(rng.uniform(0.08, 0.3, 6))
-        if p.kind == abi.PRIM_CAPSULE:
-            vals = list(c) + list(c + rng.uniform(-0.4, 0.4, 3)) + [float(rng.uniform(0.05, 0.15))]
-        if p.kind == abi.PRIM_ROUND_BOX:
-            vals[6] = float(rng.uniform(0.01, 0.05))
-        for j, v in enumerate(vals[:9]):
-            p.p[j] = float(v)
-    return f
 
 
 @pytest.mark.parametrize("seed", range(8))

@@ -7,23 +7,22 @@ path, for every output format, tiling, a schedule and supersampling, with the
 step counts (primary, sum of the lights' shadow counts).
 
 Shape 37 x 23 (partial 8 x 8 tiles in x and y, a last block of 7 rows); the
-supersampled cases use test_gpu_ssaa.py's shapes.  Every render writes into
+supersampled cases use cases.SHAPES.  Every render writes into
 buffers followed by sentinel rows, which must survive, and every case is
 rendered with and without a steps buffer, which must not change the colours."""
 import os
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import lights_ref as LR
 import oracle
+import gpu_support as G
 import ssaa_ref
+from cases import specialised_scene
+from gpu_support import SHAPES, hi_frame, ndiff, own_light, read_ppm, same, sdf_main
 from parity import quantize
-from sdf3d_amd import abi, renderer as R, scenes
-from test_gpu_ssaa import (FILL, SHAPES, _guarded, _sentinel, bits, hi_frame, owned_row_index,
-                           read_ppm, same)
+from sdf3d_amd import abi, scenes
 
 pytestmark = pytest.mark.gpu
 
@@ -37,42 +36,17 @@ def frame_of(cfg, pose, prec=abi.PRECISION_EXACT, wh=LR.SHAPE):
 
 
 def render(rd, frame, lights=None, flags=0, t=None, steps=True, schedule=None):
-    """Renderer.render (with `lights`: sdf_render_lights) into sentinel-filled
-    buffers with guard rows behind them, which are checked.  NumPy arrays."""
-    import torch
-    p = frame.params
-    rows = R.buffer_rows(p.height, t)
-    shape = (rows, p.width, R.channels(p.output_format))
-    buf = _guarded(torch, rd.device, shape, R.torch_dtype(p.output_format))
-    sshape = R.steps_shape(frame, t)
-    sbuf = _guarded(torch, rd.device, sshape, torch.int32) if steps else None
-    rd.render(frame, t, out=buf[:rows], steps=sbuf[:sshape[0]] if steps else False,
-              schedule=schedule, lights=lights, light_flags=flags)
-    torch.cuda.synchronize()
-    assert _sentinel(torch, buf[rows:]), "colour buffer: rows past the end were written"
-    if steps:
-        assert _sentinel(torch, sbuf[sshape[0]:]), "steps buffer: rows past the end were written"
-    return buf[:rows].cpu().numpy(), (sbuf[:sshape[0]].cpu().numpy() if steps else None)
+    """gpu_support.render with `lights`: sdf_render_lights."""
+    return G.render(rd, frame, t, steps, schedule, lights=lights, light_flags=flags)
 
 
 def both(rd, frame, lights=None, flags=0, t=None):
-    """Without a steps buffer (the shortcuts active) and with one: the same
-    colours.  Returns (rgba, steps)."""
-    a, _ = render(rd, frame, lights, flags, t, steps=False)
-    b, st = render(rd, frame, lights, flags, t, steps=True)
-    assert same(a, b), "renders with and without a steps buffer differ"
-    return a, st
-
-
-def ndiff(a, b):
-    a, b = (np.ascontiguousarray(v).view(np.uint32) for v in (a, b))
-    return int((a != b).sum())
+    return G.both(rd, frame, t, lights=lights, light_flags=flags)
 
 
 # ---- references, computed once and shared read-only ---------------------------
 
 _ORACLE = {}
-_OWN = {}
 
 
 def oracle_light(cfg, pose, i):
@@ -87,36 +61,6 @@ def oracle_light(cfg, pose, i):
         steps.setflags(write=False)
         _ORACLE[key] = (terms, steps)
     return _ORACLE[key]
-
-
-def spec_frame(f):
-    """`f` with material amb = dif = 0 and ref = 1: its colour is spec exactly
-    (fma(spec, 1, fma(dif, 0, 0 * ao)) in fast precision)."""
-    g = f.copy()
-    for c in range(3):
-        g.material.amb[c], g.material.dif[c], g.material.ref[c] = 0.0, 0.0, 1.0
-    return g
-
-
-def own_light(rd, f, light, key=None):
-    """(terms, spec, steps) of the build's own single-light renders of `f`
-    under `light`: terms from SDF_FORMAT_SHADE32F, spec from the colour of
-    spec_frame, the steps of the plain render."""
-    if key is not None and key in _OWN:
-        return _OWN[key]
-    g = LR.with_light(f, light)
-    g.params.output_format = abi.FORMAT_SHADE32F
-    terms, steps = both(rd, g)
-    h = spec_frame(LR.with_light(f, light))
-    spec = both(rd, h)[0][..., 0].copy()
-    assert np.isfinite(terms).all() and np.isfinite(spec).all()
-    if f.params.precision == abi.PRECISION_EXACT:
-        assert same(spec, LR.spec_exact(terms[..., 2], f.material.shininess))
-    for a in (terms, spec, steps):
-        a.setflags(write=False)
-    if key is not None:
-        _OWN[key] = (terms, spec, steps)
-    return terms, spec, steps
 
 
 def own_compose(rd, f, lights, flags, key=None):
@@ -193,19 +137,10 @@ def test_one_plain_light_tiles_stream(renderer, prec):
     import torch
     f = LR.with_light(frame_of("C3", 2, prec), LIGHTS[1])
     f.params.output_format = abi.FORMAT_TILES
-    w, h = f.params.width, f.params.height
-    # zeroed buffers: a stream has alignment gaps the encoder does not write
-    a, b = (torch.zeros(R.tiles_bytes(w, h), dtype=torch.uint8, device=renderer.device)
-            for _ in range(2))
-    renderer.render(f, out=a)
-    renderer.render(f, out=b, lights=[LIGHTS[1]])
-    torch.cuda.synchronize()
-    n = R.tiles_stream_bytes(a)
-    assert n == R.tiles_stream_bytes(b) and n > abi.TILES_HEADER_BYTES
-    assert torch.equal(a[:n], b[:n])
+    _, b, _ = G.tiles_streams(renderer, f, {}, dict(lights=[LIGHTS[1]]))
     g = f.copy()
     g.params.output_format = abi.FORMAT_RGBA32F
-    frame = renderer.tiles_decode(b, 1, b.numel(), w, h)
+    frame = renderer.tiles_decode(b, 1, b.numel(), f.params.width, f.params.height)
     torch.cuda.synchronize()
     assert same(frame.cpu().numpy(), render(renderer, g, steps=False)[0])
 
@@ -222,18 +157,6 @@ def test_generic_kernel_paths(renderer, dispatch, prec):
     if prec == abi.PRECISION_EXACT:
         parts = [oracle_light("C3", 2, i)[0] for i in range(3)]
         assert same(out, LR.compose(f, parts, LIGHTS[:3], abi.LIGHTS_COLOR))
-
-
-def specialised_scene(prec):
-    """plane, torus, box in hard union: no built-in variant, so
-    SDF_DISPATCH_AUTO compiles its kernel at run time (hipRTC).  As
-    test_gpu_ssaa.py's unmatched_scene, but a signature of its own (the
-    primitives in another order): that test counts its scene's compilations."""
-    f = frame_of("C3", 2, prec)
-    f.scene.count = 3
-    scenes._prim(f.scene, 1, abi.PRIM_TORUS, abi.OP_UNION, 0.0, 0.4, 0.1, 0.0, 0.2, 0.06)
-    scenes._prim(f.scene, 2, abi.PRIM_BOX, abi.OP_UNION, 0.0, -0.4, 0.15, 0.0, 0.15, 0.15, 0.15)
-    return f
 
 
 @pytest.mark.parametrize("prec", PRECS)
@@ -271,11 +194,7 @@ def test_formats_convert_the_colour(renderer, flags, prec):
     oracle_light("C4", 0, 2)
     f = frame_of("C4", 0, prec)
     full, _ = render(renderer, f, LIGHTS[:3], flags, steps=False)
-    for fmt in (abi.FORMAT_RGBA16F, abi.FORMAT_RGBA8, abi.FORMAT_RGB32F):
-        g = f.copy()
-        g.params.output_format = fmt
-        out, _ = both(renderer, g, LIGHTS[:3], flags)
-        assert same(out, quantize(full, fmt)), fmt
+    G.check_formats(renderer, f, full, lights=LIGHTS[:3], light_flags=flags)
 
 
 # ---- 6. supersampling -----------------------------------------------------------------
@@ -300,24 +219,7 @@ def test_supersampled(renderer, cfg, pose, s, prec):
 def test_tilings(renderer, world, shares, prec):
     oracle_light("C3", 2, 1)
     f = frame_of("C3", 2, prec)
-    w, h = f.params.width, f.params.height
-    lights, flags = LIGHTS[:2], abi.LIGHTS_COLOR
-    whole, whole_st = both(renderer, f, lights, flags)
-    seen = np.zeros(h, dtype=int)
-    for rank in range(world):
-        t = R.tiling(rank, world, 8, shares=shares)
-        rows = owned_row_index(h, t)
-        assert len(rows) == R.owned_rows(h, t)
-        seen[rows] += 1
-        out, st = both(renderer, f, lights, flags, t)
-        assert out.shape == (len(rows), w, 4)
-        assert same(out, whole[rows]) and np.array_equal(st, whole_st[rows])
-        tf = R.tiling(rank, world, 8, frame_rows=True, shares=shares)
-        fr, fr_st = both(renderer, f, lights, flags, tf)
-        other = np.setdiff1d(np.arange(h), rows)
-        assert same(fr[rows], whole[rows]) and np.array_equal(fr_st[rows], whole_st[rows])
-        assert (bits(fr[other]) == FILL).all() and (bits(fr_st[other]) == FILL).all()
-    assert (seen == 1).all()
+    G.check_tilings(renderer, f, world, shares, lights=LIGHTS[:2], light_flags=abi.LIGHTS_COLOR)
 
 
 # ---- 8. schedule ----------------------------------------------------------------------
@@ -326,26 +228,17 @@ def test_tilings(renderer, world, shares, prec):
 def test_scheduled(renderer, prec):
     oracle_light("C3", 2, 1)
     f = frame_of("C3", 2, prec)
-    ref, ref_st = render(renderer, f, LIGHTS[:2], 0, steps=True)
-    sch = renderer.schedule(f.params.height, period=1)
-    try:
-        for _ in range(3):
-            out, st = render(renderer, f, LIGHTS[:2], 0, steps=True, schedule=sch)
-            assert same(out, ref) and np.array_equal(st, ref_st)
-        assert sorted(sch.order()) == list(range((f.params.height + 7) // 8))
-        # one plain light under the schedule: sdf_render_scheduled itself
+
+    def one_plain_light(sch):      # under the schedule: sdf_render_scheduled itself
         one, _ = render(renderer, LR.with_light(f, LIGHTS[0]), steps=False, schedule=sch)
         two, _ = render(renderer, f, [LIGHTS[0]], 0, steps=False, schedule=sch)
         assert same(one, two)
-    finally:
-        sch.close()
+    G.check_scheduled(renderer, f, after=one_plain_light, lights=LIGHTS[:2], light_flags=0)
 
 
 # ---- 9. the C++ host program ----------------------------------------------------------
 
 def test_cpp_host_program_lights_argument(renderer, tmp_path):
-    exe = Path(__file__).resolve().parent.parent / "sdf3d_amd" / "bin" / "sdf_main"
-    assert exe.exists(), "build() must produce sdf3d_amd/bin/sdf_main"
     f = scenes.config("C3", 160, 90, precision=abi.PRECISION_EXACT)   # sdf_main's default
     scenes.set_view(f, scenes.orbit_view(180.0, 0.0))                 # frame 1 of 2: yaw 180
     # sdf_main's lights: the first carries the reference ambient, a light
@@ -360,8 +253,7 @@ def test_cpp_host_program_lights_argument(renderer, tmp_path):
     want, _ = render(renderer, f, lights, abi.LIGHTS_COLOR, steps=False)
     assert same(want, quantize(LR.compose(f, terms, lights, abi.LIGHTS_COLOR), abi.FORMAT_RGBA8))
     out = tmp_path / "f.ppm"
-    r = subprocess.run([str(exe), "160", "90", "2", str(out), "csg8", "1",
-                        "-4,3,3;-2,0.6,1,0.25,0.5,1"], capture_output=True, text=True, timeout=120)
+    r = sdf_main("160", "90", "2", out, "csg8", "1", "-4,3,3;-2,0.6,1,0.25,0.5,1")
     assert r.returncode == 0, r.stderr
     img = read_ppm(out)
     assert img.shape == (90, 160, 3)

@@ -8,27 +8,23 @@ for every output format, tiling, a schedule and supersampling, with
 sdf_render_lights's step counts.
 
 Shape 37 x 23 (partial 8 x 8 tiles in x and y, a last block of 7 rows); the
-supersampled cases use test_gpu_ssaa.py's shapes.  Every render writes into
+supersampled cases use cases.SHAPES.  Every render writes into
 buffers followed by sentinel rows, which must survive, and every case is
 rendered with and without a steps buffer, which must not change the colours.
 The SIX scenes run the generic kernel except where a test is about the path."""
-import ctypes as C
 import os
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import lights_ref as LR
 import materials_ref as MR
+import gpu_support as G
 import oracle
 import ssaa_ref
-from parity import quantize
-from sdf3d_amd import abi, renderer as R, scenes
-from test_gpu_lights import own_light
-from test_gpu_ssaa import (FILL, SHAPES, _guarded, _sentinel, bits, hi_frame, owned_row_index,
-                           read_ppm, same)
+from cases import frame_of, hard_union
+from gpu_support import SHAPES, hi_frame, ndiff, own_light, read_ppm, same, sdf_main
+from sdf3d_amd import abi, scenes
 
 pytestmark = pytest.mark.gpu
 
@@ -46,61 +42,17 @@ FAST_MEASURED = 2.21e-6
 FAST_BOUND = 4 * FAST_MEASURED
 
 
-def hard_union(prec, wh=MR.SHAPE, swapped=False):
-    """plane, capsule, box in hard union (`swapped`: plane, box, capsule): no
-    built-in variant, so SDF_DISPATCH_AUTO compiles its kernel at run time
-    (hipRTC); signatures no other test file uses, and `swapped` only the test
-    that counts its compilations."""
-    f = scenes.config("C3", *wh, precision=prec, pose=2)
-    C.memset(C.addressof(f.scene.prims), 0, C.sizeof(f.scene.prims))
-    f.scene.count = 3
-    scenes._prim(f.scene, 0, abi.PRIM_PLANE, abi.OP_UNION, 0.0, 0.0, 1.0, 0.0, 0.0)
-    cap, box = (2, 1) if swapped else (1, 2)
-    scenes._prim(f.scene, cap, abi.PRIM_CAPSULE, abi.OP_UNION, 0.0, -0.4, 0.1, 0.2, 0.3, 0.4,
-                 -0.1, 0.12)
-    scenes._prim(f.scene, box, abi.PRIM_BOX, abi.OP_UNION, 0.0, 0.5, 0.15, 0.1, 0.15, 0.15, 0.15)
-    return f
-
-
-def frame_of(name, pose, prec=EXACT, dispatch=None):
-    """The frame `name` (materials_ref.FRAMES, or HU: hard_union).  SIX and SIXH
-    run the generic kernel unless `dispatch` says otherwise."""
-    f = hard_union(prec) if name == "HU" else MR.frame_of(name, pose, prec)
-    if dispatch is None:
-        dispatch = abi.DISPATCH_GENERIC if name in ("SIX", "SIXH") else abi.DISPATCH_AUTO
-    f.params.dispatch = dispatch
-    return f
+def shading(materials=None, lights=None, flags=0):
+    return dict(materials=materials, lights=lights, light_flags=flags)
 
 
 def render(rd, frame, materials=None, lights=None, flags=0, t=None, steps=True, schedule=None):
-    """Renderer.render (with `materials`: sdf_render_materials) into
-    sentinel-filled buffers with guard rows behind them, which are checked."""
-    import torch
-    p = frame.params
-    rows = R.buffer_rows(p.height, t)
-    shape = (rows, p.width, R.channels(p.output_format))
-    buf = _guarded(torch, rd.device, shape, R.torch_dtype(p.output_format))
-    sshape = R.steps_shape(frame, t)
-    sbuf = _guarded(torch, rd.device, sshape, torch.int32) if steps else None
-    rd.render(frame, t, out=buf[:rows], steps=sbuf[:sshape[0]] if steps else False,
-              schedule=schedule, lights=lights, light_flags=flags, materials=materials)
-    torch.cuda.synchronize()
-    assert _sentinel(torch, buf[rows:]), "colour buffer: rows past the end were written"
-    if steps:
-        assert _sentinel(torch, sbuf[sshape[0]:]), "steps buffer: rows past the end were written"
-    return buf[:rows].cpu().numpy(), (sbuf[:sshape[0]].cpu().numpy() if steps else None)
+    """gpu_support.render with `materials`: sdf_render_materials."""
+    return G.render(rd, frame, t, steps, schedule, **shading(materials, lights, flags))
 
 
 def both(rd, frame, materials=None, lights=None, flags=0, t=None):
-    a, _ = render(rd, frame, materials, lights, flags, t, steps=False)
-    b, st = render(rd, frame, materials, lights, flags, t, steps=True)
-    assert same(a, b), "renders with and without a steps buffer differ"
-    return a, st
-
-
-def ndiff(a, b):
-    a, b = (np.ascontiguousarray(v).view(np.uint32) for v in (a, b))
-    return int((a != b).sum())
+    return G.both(rd, frame, t, **shading(materials, lights, flags))
 
 
 # ---- references, computed once and shared read-only ---------------------------
@@ -276,19 +228,10 @@ def test_identical_materials_are_sdf_render_lights(renderer, fmt, prec):
 
 @pytest.mark.parametrize("prec", PRECS)
 def test_identical_materials_tiles_stream(renderer, prec):
-    import torch
     f = frame_of("C4", 0, prec)
     f.params.output_format = abi.FORMAT_TILES
     mats = [type(f.material).from_buffer_copy(f.material) for _ in range(f.scene.count)]
-    w, h = f.params.width, f.params.height
-    a, b = (torch.zeros(R.tiles_bytes(w, h), dtype=torch.uint8, device=renderer.device)
-            for _ in range(2))
-    renderer.render(f, out=a, lights=[LIGHTS[1]])
-    renderer.render(f, out=b, lights=[LIGHTS[1]], materials=mats)
-    torch.cuda.synchronize()
-    n = R.tiles_stream_bytes(a)
-    assert n == R.tiles_stream_bytes(b) and n > abi.TILES_HEADER_BYTES
-    assert torch.equal(a[:n], b[:n])
+    G.tiles_streams(renderer, f, dict(lights=[LIGHTS[1]]), dict(lights=[LIGHTS[1]], materials=mats))
 
 
 @pytest.mark.parametrize("prec", PRECS)
@@ -361,11 +304,7 @@ def test_formats_convert_the_colour(renderer, flags, prec):
     f = frame_of("C4", 0, prec)
     mats = MR.palette_for(f)
     full, _ = render(renderer, f, mats, LIGHTS[:3], flags, steps=False)
-    for fmt in (abi.FORMAT_RGBA16F, abi.FORMAT_RGBA8, abi.FORMAT_RGB32F):
-        g = f.copy()
-        g.params.output_format = fmt
-        out, _ = both(renderer, g, mats, LIGHTS[:3], flags)
-        assert same(out, quantize(full, fmt)), fmt
+    G.check_formats(renderer, f, full, **shading(mats, LIGHTS[:3], flags))
 
 
 # ---- 7. supersampling --------------------------------------------------------------
@@ -394,24 +333,7 @@ def test_tilings(renderer, world, shares, prec):
     oracle_light("C3", 2, 1)
     f = frame_of("C3", 2, prec)
     mats = MR.palette_for(f)
-    w, h = f.params.width, f.params.height
-    lights, flags = LIGHTS[:2], abi.LIGHTS_COLOR
-    whole, whole_st = both(renderer, f, mats, lights, flags)
-    seen = np.zeros(h, dtype=int)
-    for rank in range(world):
-        t = R.tiling(rank, world, 8, shares=shares)
-        rows = owned_row_index(h, t)
-        assert len(rows) == R.owned_rows(h, t)
-        seen[rows] += 1
-        out, st = both(renderer, f, mats, lights, flags, t)
-        assert out.shape == (len(rows), w, 4)
-        assert same(out, whole[rows]) and np.array_equal(st, whole_st[rows])
-        tf = R.tiling(rank, world, 8, frame_rows=True, shares=shares)
-        fr, fr_st = both(renderer, f, mats, lights, flags, tf)
-        other = np.setdiff1d(np.arange(h), rows)
-        assert same(fr[rows], whole[rows]) and np.array_equal(fr_st[rows], whole_st[rows])
-        assert (bits(fr[other]) == FILL).all() and (bits(fr_st[other]) == FILL).all()
-    assert (seen == 1).all()
+    G.check_tilings(renderer, f, world, shares, **shading(mats, LIGHTS[:2], abi.LIGHTS_COLOR))
 
 
 # ---- 9. schedule -------------------------------------------------------------------
@@ -421,22 +343,12 @@ def test_scheduled(renderer, prec):
     oracle_light("C3", 2, 1)
     f = frame_of("C3", 2, prec)
     mats = MR.palette_for(f)
-    ref, ref_st = render(renderer, f, mats, LIGHTS[:2], 0, steps=True)
-    sch = renderer.schedule(f.params.height, period=1)
-    try:
-        for _ in range(3):
-            out, st = render(renderer, f, mats, LIGHTS[:2], 0, steps=True, schedule=sch)
-            assert same(out, ref) and np.array_equal(st, ref_st)
-        assert sorted(sch.order()) == list(range((f.params.height + 7) // 8))
-    finally:
-        sch.close()
+    G.check_scheduled(renderer, f, **shading(mats, LIGHTS[:2], 0))
 
 
 # ---- 10. the C++ host program -------------------------------------------------------
 
 def test_cpp_host_program_palette_option(renderer, tmp_path):
-    exe = Path(__file__).resolve().parent.parent / "sdf3d_amd" / "bin" / "sdf_main"
-    assert exe.exists(), "build() must produce sdf3d_amd/bin/sdf_main"
     f = scenes.config("C3", 160, 90, precision=EXACT)                 # sdf_main's default
     scenes.set_view(f, scenes.orbit_view(180.0, 0.0))                 # frame 1 of 2: yaw 180
     lights = LR.rig(2)
@@ -448,16 +360,13 @@ def test_cpp_host_program_palette_option(renderer, tmp_path):
     plain, _ = render(renderer, f, None, lights, abi.LIGHTS_COLOR, steps=False)
     assert not same(want, plain)
     out = tmp_path / "f.ppm"
-    r = subprocess.run([str(exe), "160", "90", "2", str(out), "csg8", "1",
-                        "-4,3,3;-2,0.6,1,0.25,0.5,1", "--palette"], capture_output=True,
-                       text=True, timeout=120)
+    r = sdf_main("160", "90", "2", out, "csg8", "1", "-4,3,3;-2,0.6,1,0.25,0.5,1", "--palette")
     assert r.returncode == 0, r.stderr
     img = read_ppm(out)
     assert img.shape == (90, 160, 3)
     assert np.array_equal(img, want[::-1, :, :3])
     # without lights on the line: the reference's one light
     one, _ = render(renderer, f, scenes.palette(8), [f.light], 0, steps=False)
-    r = subprocess.run([str(exe), "--palette", "160", "90", "2", str(out), "csg8"],
-                       capture_output=True, text=True, timeout=120)
+    r = sdf_main("--palette", "160", "90", "2", out, "csg8")
     assert r.returncode == 0, r.stderr
     assert np.array_equal(read_ppm(out), one[::-1, :, :3])

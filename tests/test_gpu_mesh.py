@@ -7,26 +7,31 @@ positions stay within a measured bound, on every dispatch path of the
 primitive scenes (tests/fast_paths.py).
 
 Grids: partial bricks, several bricks per axis, sub-second references.  Every
-output buffer is test_gpu_query.py's guarded buffer (64 sentinels behind it,
-which must survive).  A case's GPU mesh and its reference are computed once."""
+output buffer is fenced (gpu_support.out_buf: 64 guard rows behind it, which
+must survive).  A case's GPU mesh and its reference are computed once."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import fast_paths as FP
 import mesh_ref as M
+from cases import C4_GRID, JIT_SEEDS
+from cases import query_frame as frame_of
+from fast_paths import MESH_BOUND_N as FAST_BOUND_N
+from fast_paths import MESH_BOUND_V as FAST_BOUND_V
+from gpu_support import bitwise_eq, ndiff, ptr, raw_mesh, sdf_main
+from gpu_support import mesh_count as count
+from gpu_support import mesh_emit as emit
+from gpu_support import mesh_mismatches as mismatches
 from sdf3d_amd import abi, meshio, renderer as R
-from test_gpu_query import FAST, JIT_SEEDS, frame_of, guarded, ptr, same, unguard
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-C4_GRID = ((-1.13, -0.11, -1.02), (0.12, 0.08, 0.11), (19, 11, 17))
+FAST = abi.PRECISION_FAST
 C1_OFF = ((-0.31, 0.13, -0.29), (0.05, 0.06, 0.055), (12, 10, 11))
-# case -> (scene kind of test_gpu_query.frame_of, origin, cell, n, iso)
+# case -> (scene kind of cases.query_frame, origin, cell, n, iso)
 CASES = {
     "REF": ("REF", (-0.51, -0.13, -0.49), (0.0625, 0.07, 0.06), (17, 12, 16), 0.0),
     "C1": ("C1", *C1_OFF, 0.0),
@@ -42,60 +47,6 @@ CASES = {
     "C5": ("C5", (-0.61, -0.32, -0.59), (0.05, 0.05, 0.05), (24, 25, 23), 0.0),
 }
 FINE = ("C4", (-1.01, -0.05, -1.02), (0.04, 0.04, 0.04), (50, 20, 42), 0.0)
-# Fast precision against the reference on the two grids whose lattice keeps
-# min |w| >= 1e-4 (no sign can flip), measured on an MI355X
-# (profiles/mesh_C4.json fast_deviation): the largest |vertex - reference| /
-# cell over the components, and the largest normal-component difference.  The
-# bounds asserted are 4 x those, the headroom test_gpu_query.py gives its own.
-# (C1 1.788e-6 / 1.341e-6, C4 1.614e-6 / 4.195e-6; no owner differed)
-FAST_MEASURED_V = 1.789e-6
-FAST_MEASURED_N = 4.195e-6
-FAST_BOUND_V = 4 * FAST_MEASURED_V
-FAST_BOUND_N = 4 * FAST_MEASURED_N
-
-
-def stream_of(rd):
-    return C.c_void_p(rd.torch.cuda.current_stream(rd.device).cuda_stream)
-
-
-def count(rd, f, g):
-    """sdf_mesh_count through the C ABI: (workspace, its size, the four counts)."""
-    torch = rd.torch
-    nbytes = int(rd.lib.sdf_mesh_workspace_bytes(C.byref(g)))
-    assert nbytes > 0
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=rd.device)
-    cn = guarded(rd, 4, 1, torch.int64)
-    rc = rd.lib.sdf_mesh_count(C.byref(f.scene), C.byref(f.params), C.byref(g), ptr(ws), nbytes,
-                               ptr(cn), stream_of(rd))
-    abi.check(rc, "sdf_mesh_count")
-    torch.cuda.synchronize()
-    return ws, nbytes, tuple(int(x) for x in unguard(cn, 4, 1))
-
-
-def emit(rd, f, g, ws, nbytes, cap_v, cap_t, normal=True, prim=True):
-    """sdf_mesh_emit into guarded buffers of exactly the capacities given."""
-    torch = rd.torch
-    bv = guarded(rd, cap_v, 3, torch.float32)
-    bt = guarded(rd, cap_t, 3, torch.int32)
-    bn = guarded(rd, cap_v, 3, torch.float32, normal)
-    bp = guarded(rd, cap_v, 1, torch.int32, prim)
-    out = abi.sdf_mesh_out(ptr(bv), cap_v, ptr(bt), cap_t, ptr(bn), ptr(bp))
-    rc = rd.lib.sdf_mesh_emit(C.byref(f.scene), C.byref(f.params), C.byref(g), ptr(ws), nbytes,
-                              C.byref(out), stream_of(rd))
-    abi.check(rc, "sdf_mesh_emit")
-    torch.cuda.synchronize()
-    return {"verts": unguard(bv, cap_v, 3), "tris": unguard(bt, cap_t, 3),
-            "normal": unguard(bn, cap_v, 3), "prim": unguard(bp, cap_v, 1)}
-
-
-def raw_mesh(rd, f, spec, dense=False, normal=True, prim=True):
-    g = R.grid(*spec, dense=dense)
-    ws, nbytes, cn = count(rd, f, g)
-    got = emit(rd, f, g, ws, nbytes, cn[0], cn[1], normal, prim)
-    got["counts"] = cn
-    return got
-
-
 _cache = {}
 
 
@@ -111,18 +62,10 @@ def exact_run(rd, case):
         again = raw_mesh(rd, f, spec)
         n2 = rd.lib.sdf_jit_count()
         for k in ("verts", "tris", "normal", "prim"):
-            assert np.all(same(got[k], again[k])), f"{case}: {k} differs between two calls"
+            assert np.all(bitwise_eq(got[k], again[k])), f"{case}: {k} differs between two calls"
         assert got["counts"] == again["counts"]
         _cache[case] = (got, M.mesh(f, *spec), n1 - n0, n2 - n1)
     return _cache[case]
-
-
-def mismatches(got, ref):
-    bad = {}
-    for k in ("verts", "tris", "normal", "prim"):
-        a, b = got[k], ref[k]
-        bad[k] = -1 if a.shape != b.shape else int((~same(a, b)).sum())
-    return bad
 
 
 # 1. exact precision -------------------------------------------------------------
@@ -156,7 +99,7 @@ def test_skip_equals_dense(renderer):
     print(f"C4 fine: counts {got['counts']} dense {dense['counts']} reference {ref['counts']} "
           f"active bricks {ref['bricks']}")
     for k in ("verts", "tris", "normal", "prim"):
-        assert np.all(same(got[k], dense[k])), k
+        assert np.all(bitwise_eq(got[k], dense[k])), k
     assert got["counts"][:2] == dense["counts"][:2] == ref["counts"]
     assert mismatches(got, ref) == {"verts": 0, "tris": 0, "normal": 0, "prim": 0}
     assert got["counts"][3] == dense["counts"][3] == 126
@@ -167,7 +110,7 @@ def test_skip_equals_dense(renderer):
 # 3. capacities ----------------------------------------------------------------------
 def test_capacity_guards_every_store(renderer):
     """max_verts = nv - 3 and max_tris = nt - 5: exactly that prefix is written
-    and nothing beyond (unguard checks the sentinels); capacities of 0 with NULL
+    and nothing beyond (the fence behind every buffer); capacities of 0 with NULL
     buffers write nothing."""
     full, _, _, _ = exact_run(renderer, "C4")
     kind, *spec = CASES["C4"]
@@ -175,8 +118,8 @@ def test_capacity_guards_every_store(renderer):
     ws, nbytes, cn = count(renderer, f, g)
     nv, nt = cn[0] - 3, cn[1] - 5
     got = emit(renderer, f, g, ws, nbytes, nv, nt)
-    assert np.all(same(got["verts"], full["verts"][:nv])) and np.all(got["tris"] == full["tris"][:nt])
-    assert np.all(same(got["normal"], full["normal"][:nv])) and np.all(got["prim"] == full["prim"][:nv])
+    assert np.all(bitwise_eq(got["verts"], full["verts"][:nv])) and np.all(got["tris"] == full["tris"][:nt])
+    assert np.all(bitwise_eq(got["normal"], full["normal"][:nv])) and np.all(got["prim"] == full["prim"][:nv])
     out = abi.sdf_mesh_out(None, 0, None, 0, None, None)
     rc = renderer.lib.sdf_mesh_emit(C.byref(f.scene), C.byref(f.params), C.byref(g), ptr(ws), nbytes,
                                     C.byref(out), None)
@@ -191,8 +134,8 @@ def test_output_selection_does_not_change_the_bits(renderer, sel):
     full, _, _, _ = exact_run(renderer, "C4")
     kind, *spec = CASES["C4"]
     got = raw_mesh(renderer, frame_of(kind), spec, normal=sel[0], prim=sel[1])
-    assert np.all(same(got["verts"], full["verts"])) and np.all(got["tris"] == full["tris"])
-    assert got["normal"] is None if not sel[0] else np.all(same(got["normal"], full["normal"]))
+    assert np.all(bitwise_eq(got["verts"], full["verts"])) and np.all(got["tris"] == full["tris"])
+    assert got["normal"] is None if not sel[0] else np.all(bitwise_eq(got["normal"], full["normal"]))
     assert got["prim"] is None if not sel[1] else np.all(got["prim"] == full["prim"])
 
 
@@ -202,7 +145,7 @@ def test_one_cell_and_empty_grids(renderer):
     spec = ((-0.01, 0.58, -0.02), (0.05, 0.05, 0.05), (1, 1, 1), 0.0)
     got, ref = raw_mesh(renderer, f, spec), M.mesh(f, *spec)
     assert got["counts"] == (1, 0, 1, 1) and ref["counts"] == (1, 0)
-    assert np.all(same(got["verts"], ref["verts"])) and np.all(same(got["normal"], ref["normal"]))
+    assert np.all(bitwise_eq(got["verts"], ref["verts"])) and np.all(bitwise_eq(got["normal"], ref["normal"]))
     # wholly outside the scene
     spec = ((2.0, 2.0, 2.0), (0.05, 0.05, 0.05), (9, 8, 17), 0.0)
     got = raw_mesh(renderer, f, spec)
@@ -218,7 +161,7 @@ def test_renderer_mesh_is_the_abi_calls(renderer):
     renderer.torch.cuda.synchronize()
     assert m.counts == full["counts"]
     for k in ("verts", "tris", "normal", "prim"):
-        assert np.all(same(getattr(m, k).cpu().numpy(), full[k])), k
+        assert np.all(bitwise_eq(getattr(m, k).cpu().numpy(), full[k])), k
     m = renderer.mesh(frame_of(kind), origin, cell, n, iso)
     assert m.normal is None and m.prim is None and m.verts.shape == full["verts"].shape
 
@@ -226,19 +169,16 @@ def test_renderer_mesh_is_the_abi_calls(renderer):
 def test_cpp_host_program_mesh(renderer, tmp_path):
     """sdf_main --mesh FILE.obj --grid ... writes the arrays Renderer.mesh gives
     for its csg8 scene (C3's) on that grid."""
-    exe = Path(__file__).resolve().parent.parent / "sdf3d_amd" / "bin" / "sdf_main"
-    assert exe.exists(), "build() must produce sdf3d_amd/bin/sdf_main"
     obj = tmp_path / "m.obj"
-    r = subprocess.run([str(exe), "--mesh", str(obj), "--grid", "-1.25,-0.125,-1,1.25,1.125,1,20",
-                        "64", "36", "1", str(tmp_path / "f.ppm"), "csg8"], capture_output=True,
-                       text=True, timeout=120)
+    r = sdf_main("--mesh", obj, "--grid", "-1.25,-0.125,-1,1.25,1.125,1,20", "64", "36", "1",
+                 tmp_path / "f.ppm", "csg8")
     assert r.returncode == 0, r.stderr
     f = frame_of("C3")
     m = renderer.mesh(f, (-1.25, -0.125, -1.0), (0.125, 0.0625, 0.1), 20, normal=True)
     renderer.torch.cuda.synchronize()
     v, t, n = meshio.read_obj(obj)
-    assert np.all(same(v, m.verts.cpu().numpy())) and np.all(t == m.tris.cpu().numpy())
-    assert np.all(same(n, m.normal.cpu().numpy()))
+    assert np.all(bitwise_eq(v, m.verts.cpu().numpy())) and np.all(t == m.tris.cpu().numpy())
+    assert np.all(bitwise_eq(n, m.normal.cpu().numpy()))
 
 
 # 5. fast precision ------------------------------------------------------------------------
@@ -262,7 +202,7 @@ def fast_mesh(rd, case):
         assert [n[1] - n[0], n[2] - n[1], n[3] - n[2]] == [jit[0], jit[1], 0], (case, n)
     assert got["counts"] == again["counts"]
     for k in ("verts", "tris", "normal", "prim"):
-        assert np.all(same(got[k], again[k])), f"{case}: {k} differs between two fast calls"
+        assert np.all(bitwise_eq(got[k], again[k])), f"{case}: {k} differs between two fast calls"
     return got
 
 
@@ -272,7 +212,7 @@ def fast_deviation(rd, case):
     exact, ref, _, _ = exact_run(rd, case)
     got = fast_mesh(rd, case)
     r = M.fast_deviation(ref, got, CASES[case][2])
-    differ = sum(FP.bits_differ(got[k], exact[k]) for k in ("verts", "normal")) \
+    differ = sum(ndiff(got[k], exact[k]) for k in ("verts", "normal")) \
         if r["same_connectivity"] else -1
     return r, differ
 

@@ -34,9 +34,9 @@ import offsets as O
 import oracle
 import query_ref as Q
 import reflect_ref as RR
+from gpu_support import bitwise_eq, raw_mesh, sample, trace
+from gpu_support import mesh_mismatches as mismatches
 from sdf3d_amd import abi, scenes
-from test_gpu_mesh import mismatches, raw_mesh
-from test_gpu_query import same, sample, trace
 
 pytestmark = pytest.mark.gpu
 
@@ -52,8 +52,9 @@ def unculled(f):
     return g
 
 
-def ndiff(a, b):
-    return int((~same(np.asarray(a), np.asarray(b))).sum())
+def unequal(a, b):
+    """The number of entries that differ, NaN equal to NaN."""
+    return int((~bitwise_eq(np.asarray(a), np.asarray(b))).sum())
 
 
 # ---- render -------------------------------------------------------------------------
@@ -99,9 +100,9 @@ def test_render_equals_the_oracle_and_unculled(renderer, case, name):
     fast_path, _ = gpu_render(renderer, f, case, steps=False)
     plain, pst = gpu_render(renderer, unculled(f), case)
     ref, rst = reference(case, f)
-    bad = {"oracle": ndiff(got, ref), "oracle_steps": ndiff(st, rst),
-           "unculled": ndiff(got, plain), "unculled_steps": ndiff(st, pst),
-           "no_steps": ndiff(fast_path, got)}
+    bad = {"oracle": unequal(got, ref), "oracle_steps": unequal(st, rst),
+           "unculled": unequal(got, plain), "unculled_steps": unequal(st, pst),
+           "no_steps": unequal(fast_path, got)}
     print(f"{case} at {name}: {got.shape[0] * got.shape[1]} pixels; words differing {bad}")
     if bad["oracle_steps"]:
         off = (st != rst)
@@ -158,7 +159,7 @@ def test_nan_ray_layers_march_as_the_reference(renderer, entry, eflags, name):
                                            steps=True, **kw)
         renderer.torch.cuda.synchronize()
         out, st = out.cpu().numpy().reshape(ref.shape), st.cpu().numpy().reshape(rst.shape)
-        bad[label] = (ndiff(out, ref), ndiff(st, rst))
+        bad[label] = (unequal(out, ref), unequal(st, rst))
     print(f"{entry} eflags={eflags} at {name}: {int(nan.sum())} pixels with a NaN layer-1 ray; "
           f"words differing from the reference (colour, steps) {bad}")
     assert bad == {"culled": (0, 0), "unculled": (0, 0)}
@@ -199,8 +200,8 @@ def test_generic_sample_at_shell_points(renderer, kind, op, name):
     for _ in range(40):
         s, P = O.pair_scene(tmpl, O.OFFSETS[name], rng, kind, op)
         ref = O.sdf_at(s, P)
-        bad["culled"] += ndiff(probe(renderer, s, P, abi.DISPATCH_GENERIC), ref)
-        bad["unculled"] += ndiff(probe(renderer, s, P, abi.DISPATCH_UNCULLED), ref)
+        bad["culled"] += unequal(probe(renderer, s, P, abi.DISPATCH_GENERIC), ref)
+        bad["unculled"] += unequal(probe(renderer, s, P, abi.DISPATCH_UNCULLED), ref)
         far += int(O.says_far(s, 1, P)[0].sum())
         points += len(P)
         if far >= MIN_FAR:
@@ -230,8 +231,8 @@ def test_fixed_kernel_sample_at_shell_points(renderer, which, name):
     for _ in range(40):
         s, P, i = O.csg8_probe(tmpl, O.OFFSETS[name], rng, which, reach=reach)
         ref = O.sdf_at(s, P)
-        bad["fixed"] += ndiff(probe(renderer, s, P, abi.DISPATCH_AUTO), ref)
-        bad["unculled"] += ndiff(probe(renderer, s, P, abi.DISPATCH_UNCULLED), ref)
+        bad["fixed"] += unequal(probe(renderer, s, P, abi.DISPATCH_AUTO), ref)
+        bad["unculled"] += unequal(probe(renderer, s, P, abi.DISPATCH_UNCULLED), ref)
         far += int(O.says_far(s, i, P, reach=reach)[0].sum())
         far_generic += int(O.says_far(s, i, P)[0].sum())
         points += len(P)
@@ -294,8 +295,8 @@ def test_trace_equals_the_oracle_and_unculled(renderer, path, name):
     got = trace(renderer, f, o, d)
     plain = trace(renderer, unculled(f), o, d)
     keys = ("t", "steps", "normal", "prim")
-    bad = {k: ndiff(got[k], ref[k]) for k in keys}
-    bad_plain = {k: ndiff(got[k], plain[k]) for k in keys}
+    bad = {k: unequal(got[k], ref[k]) for k in keys}
+    bad_plain = {k: unequal(got[k], plain[k]) for k in keys}
     print(f"{path} at {name}: {len(o)} rays, {int(ref['hit'].sum())} hit; words differing from "
           f"the oracle {bad}, from unculled {bad_plain}")
     zero = dict.fromkeys(keys, 0)
@@ -312,8 +313,8 @@ def test_camera_rays_shade_to_the_translated_frame(renderer, name):
     o, d = renderer.camera_rays(f)
     out, st = renderer.render_rays(f, o.reshape(-1, 3), d.reshape(-1, 3), unit=True, steps=True)
     renderer.torch.cuda.synchronize()
-    bad = (ndiff(out.cpu().numpy().reshape(want.shape), want),
-           ndiff(st.cpu().numpy().reshape(wst.shape), wst))
+    bad = (unequal(out.cpu().numpy().reshape(want.shape), want),
+           unequal(st.cpu().numpy().reshape(wst.shape), wst))
     print(f"render_rays at {name}: words differing from the render (colour, steps) {bad}")
     assert bad == (0, 0)
 
@@ -354,6 +355,6 @@ def test_beyond_the_proven_range_the_frame_is_the_unculled_one(renderer, case):
     assert renderer.lib.sdf_jit_count() == n0          # no specialised kernel was asked for
     plain, pst = gpu_render(renderer, unculled(f), case)
     ref, rst = oracle.render(f)
-    bad = (ndiff(got, ref), ndiff(st, rst), ndiff(got, plain), ndiff(st, pst))
+    bad = (unequal(got, ref), unequal(st, rst), unequal(got, plain), unequal(st, pst))
     print(f"{case} beyond 2^22: words differing (oracle, its steps, unculled, its steps) {bad}")
     assert bad == (0, 0, 0, 0)

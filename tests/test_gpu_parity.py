@@ -18,7 +18,9 @@ import numpy as np
 import pytest
 
 import oracle
+from cases import random_csg8
 from golden.make_golden import FIXTURES, frame_for
+from gpu_support import read_ppm, sdf_main, with_precision
 from parity import (assert_parity, assert_parity_frame, assert_regression, compare,
                     full_size_conditioning, quantize, reading_spread, report)
 from sdf3d_amd import abi, renderer as R, scenes
@@ -42,12 +44,6 @@ def gpu(rd, frame, t=None, steps=True):
     assert np.array_equal(rgba.view(np.uint8), rgba_s.cpu().numpy().view(np.uint8)), \
         "steps=None (shadow skip) and steps=True renders differ"
     return rgba, (st.cpu().numpy() if steps else None)
-
-
-def with_precision(frame, prec):
-    f = frame.copy()
-    f.params.precision = prec
-    return f
 
 
 def log(key, rep):
@@ -409,24 +405,12 @@ def test_write_results():
         (out / "parity_fullsize.json").write_text(json.dumps(full, indent=1, sort_keys=True))
 
 
-def read_ppm(path):
-    data = Path(path).read_bytes()
-    parts = data.split(b"\n", 3)
-    assert parts[0] == b"P6"
-    w, h = map(int, parts[1].split())
-    return np.frombuffer(parts[3], dtype=np.uint8).reshape(h, w, 3)
-
-
 @pytest.mark.parametrize("scene_name,cfg", [("ref", "REF"), ("csg8", "C3")])
 def test_cpp_host_program(renderer, tmp_path, scene_name, cfg):
     """examples/sdf_main.cpp (C++ API in include/sdf3d.hpp) renders the same
     frame as the Python path; its PPM is the clamped 8-bit image."""
-    import subprocess
-    exe = Path(__file__).resolve().parent.parent / "sdf3d_amd" / "bin" / "sdf_main"
-    assert exe.exists(), "build() must produce sdf3d_amd/bin/sdf_main"
     out = tmp_path / "f.ppm"
-    r = subprocess.run([str(exe), "160", "90", "2", str(out), scene_name], capture_output=True,
-                       text=True, timeout=120)
+    r = sdf_main("160", "90", "2", out, scene_name)
     assert r.returncode == 0, r.stderr
     img = read_ppm(out)
     f = scenes.config(cfg, 160, 90, precision=abi.PRECISION_EXACT)   # sdf_main's default
@@ -523,36 +507,6 @@ def test_heatmap_every_lut_entry(renderer, max_steps):
             assert set(idx.ravel().tolist()) == set(range(256))
         if max_steps == 100 and which == 0:
             assert idx[0, 30] == 77 and idx[0, 10] == 26
-
-
-def random_csg8(rng, spread, kmax):
-    """A scene with the CSG8 signature (so the culled FixedScene variant runs)
-    but random sizes, positions and blend radii."""
-    f = scenes.config("C3", 160, 96)
-    s = f.scene
-    u = lambda a, b: float(rng.uniform(a, b))  # noqa: E731
-    c = lambda: (u(-spread, spread), u(-0.2, spread), u(-spread, spread))  # noqa: E731
-    s.prims[0].p[3] = u(-0.3, 0.3)                                  # plane offset
-    for i in range(1, 8):
-        pr = s.prims[i]
-        pr.k = u(1e-3, kmax)
-        x, y, z = c()
-        pr.p[0], pr.p[1], pr.p[2] = x, y, z
-        kind = pr.kind
-        if kind == abi.PRIM_SPHERE:
-            pr.p[3] = u(0.01, 0.6)
-        elif kind in (abi.PRIM_BOX, abi.PRIM_ROUND_BOX):
-            pr.p[3], pr.p[4], pr.p[5] = u(0.02, 0.5), u(0.02, 0.5), u(0.02, 0.5)
-            if kind == abi.PRIM_ROUND_BOX:
-                pr.p[6] = u(0.0, 0.5) * min(pr.p[3], pr.p[4], pr.p[5])
-        elif kind == abi.PRIM_TORUS:
-            pr.p[3], pr.p[4] = u(0.05, 0.5), u(0.01, 0.2)
-        elif kind == abi.PRIM_CAPSULE:
-            pr.p[3], pr.p[4], pr.p[5] = c()
-            pr.p[6] = u(0.01, 0.3)
-        elif kind == abi.PRIM_CYLINDER:
-            pr.p[3], pr.p[4] = u(0.02, 0.4), u(0.02, 0.6)
-    return f
 
 
 @pytest.mark.parametrize("seed", range(12))
@@ -656,15 +610,12 @@ def test_cpp_frame_driver(renderer, tmp_path, peer_root):
     0 = itself, decode) through a one-rank RCCL communicator whose ids travel
     through files; the last frame equals the Python path's render."""
     import os
-    import subprocess
-    exe = Path(__file__).resolve().parent.parent / "sdf3d_amd" / "bin" / "sdf_main"
     out = tmp_path / "d.ppm"
     env = dict(os.environ, SDF3D_DRIVER="1", SDF3D_ROOT_AS_PEER="1" if peer_root else "0",
                SDF3D_ID_DIR=str(tmp_path), SDF3D_RUN_ID=f"t{os.getpid()}",
                SDF3D_RCCL="/opt/rocm/lib/librccl.so.1")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([str(exe), "160", "90", "2", str(out), "csg8"], capture_output=True,
-                       text=True, timeout=120, env=env)
+    r = sdf_main("160", "90", "2", out, "csg8", env=env)
     assert r.returncode == 0, r.stderr
     assert "rank 0 of 1" in r.stdout
     img = read_ppm(out)

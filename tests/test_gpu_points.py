@@ -10,23 +10,22 @@ counts.  End to end: Renderer.bake on a mesh, and the host program's
 --mesh-colors.
 
 The point set is the 37 x 23 frame's 851 hit points: 13 full waves and 19 lanes.
-Every call writes into the middle of sentinel-filled buffers: the GUARD rows in
-front of every output and those behind it must survive."""
-import ctypes as C
-import subprocess
-from pathlib import Path
-
+Every call writes into fenced buffers (points_ref.kernel_shade): the 64 guard rows
+in front of every output and those behind it must survive."""
 import numpy as np
 import pytest
 
-import lights_ref as LR
 import materials_ref as MR
 import oracle
 import points_ref as PR
+from cases import LIGHTS
+from gpu_support import both as frame_both
+from gpu_support import ndiff, same, sdf_main
+from gpu_support import render as frame_render
+from points_ref import FAST_CASES, OUTS, fast_deviation, mats_of, the_frame
+from points_ref import frame_hits as hit_points
+from points_ref import kernel_shade as shade
 from sdf3d_amd import abi, meshio, renderer as R, scenes
-from test_gpu_materials import both as frame_both
-from test_gpu_materials import render as frame_render
-from test_gpu_ssaa import FILL
 
 pytestmark = pytest.mark.gpu
 
@@ -36,9 +35,6 @@ A, G, U = abi.DISPATCH_AUTO, abi.DISPATCH_GENERIC, abi.DISPATCH_UNCULLED
 CLR = abi.LIGHTS_COLOR
 W, H = MR.SHAPE
 N = W * H
-LIGHTS = LR.rig(8)
-OUTS = ("rgba", "ao", "shadow", "material", "steps")
-ROOT = Path(__file__).resolve().parent.parent
 
 # Fast precision against the reference replayed at the kernel's own shadow
 # counts, on all 851 hit points of C4 pose 0, C3 pose 2 (palette) and REF pose
@@ -57,129 +53,6 @@ FAST_MATERIAL_MEASURED = 8.941e-8
 FAST_MATERIAL_BOUND = 4 * FAST_MATERIAL_MEASURED
 
 
-# ---- helpers ---------------------------------------------------------------------------
-
-def same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8),
-                                                                        b.view(np.uint8))
-
-
-def ndiff(a, b):
-    return int((np.ascontiguousarray(a).view(np.uint32) != np.ascontiguousarray(b).view(np.uint32))
-               .sum())
-
-
-def points_scene(prec, counted=False):
-    """capsule, plane, torus (smooth union) -- `counted`: torus, plane, capsule:
-    no built-in variant, so SDF_DISPATCH_AUTO compiles its kernel at run time
-    (hipRTC); `counted` is used only by the test that counts its compilations."""
-    f = scenes.config("C3", W, H, precision=prec, pose=2)
-    C.memset(C.addressof(f.scene.prims), 0, C.sizeof(f.scene.prims))
-    f.scene.count = 3
-    cap = (abi.PRIM_CAPSULE, -0.4, 0.15, 0.1, 0.1, 0.5, -0.1, 0.12)
-    tor = (abi.PRIM_TORUS, 0.45, 0.12, 0.0, 0.25, 0.08)
-    first, last = (tor, cap) if counted else (cap, tor)
-    scenes._prim(f.scene, 0, first[0], abi.OP_UNION, 0.0, *first[1:])
-    scenes._prim(f.scene, 1, abi.PRIM_PLANE, abi.OP_UNION, 0.0, 0.0, 1.0, 0.0, 0.0)
-    scenes._prim(f.scene, 2, last[0], abi.OP_SMOOTH_UNION, 0.08, *last[1:])
-    f.params.dispatch = A
-    return f
-
-
-def the_frame(name, pose, prec=EXACT, dispatch=A):
-    if name in ("PJ", "PJC"):
-        return points_scene(prec, counted=name == "PJC")
-    f = scenes.config(name, W, H, precision=prec, pose=pose)
-    f.params.dispatch = dispatch
-    return f
-
-
-def mats_of(f, pal=True):
-    if f.scene.kind != abi.SCENE_PRIMITIVES:
-        return [f.material]
-    return scenes.palette(f.scene.count) if pal else [f.material] * f.scene.count
-
-
-GUARD = 64   # sentinel rows in front of and behind every output (a wave's worth)
-
-
-def fenced(torch, device, shape, dtype):
-    """A sentinel-filled allocation of GUARD + shape[0] + GUARD rows: the kernel is
-    handed rows GUARD .. GUARD + shape[0].  (GUARD rows of any output are a
-    multiple of 16 bytes, so `rgba` stays aligned.)"""
-    rows = shape[0] + 2 * GUARD
-    nbytes = rows * int(np.prod(shape[1:])) * torch.empty((), dtype=dtype).element_size()
-    raw = torch.full((nbytes,), FILL, dtype=torch.uint8, device=device)
-    return raw.view(dtype).reshape(rows, *shape[1:])
-
-
-def untouched(torch, x):
-    return bool((x.contiguous().view(-1).view(torch.uint8) == FILL).all())
-
-
-def shade(rd, f, P, normals=None, eye=None, lift=0.0, lights=None, flags=0, materials=None,
-          outs=OUTS):
-    """sdf_shade_points into the middle of sentinel-filled buffers whose guard
-    rows, in front of every output and behind it, are checked: a
-    points_ref.RefShade of NumPy arrays (None for an output not in `outs`; dif is
-    not an output)."""
-    import torch
-    dev = lambda a: torch.from_numpy(np.array(a, dtype=f32).reshape(-1, 3)).to(rd.device)
-    pts = dev(P)
-    n = pts.shape[0]
-    nrm = None if normals is None else dev(normals)
-    lights = [f.light] if lights is None else list(lights)
-    materials = mats_of(f, False) if materials is None else list(materials)
-    nl = len(lights)
-    larr = (abi.sdf_light * nl)(*lights)
-    marr = (abi.sdf_material * len(materials))(*materials)
-    shapes = {"rgba": ((n, 4), torch.float32), "ao": ((n,), torch.float32),
-              "shadow": ((n, nl), torch.float32), "material": ((n, 9), torch.float32),
-              "steps": ((n, nl), torch.int32)}
-    bufs = {k: fenced(torch, rd.device, *shapes[k]) for k in outs}
-    mid = {k: b[GUARD:GUARD + n] for k, b in bufs.items()}
-    p = abi.sdf_points()
-    p.points, p.n, p.lift = pts.data_ptr(), n, float(lift)
-    p.normals = nrm.data_ptr() if nrm is not None else None
-    if eye is not None:
-        p.flags = abi.POINTS_EYE
-        for c in range(3):
-            p.eye[c] = float(eye[c])
-    ps = abi.sdf_point_shade(*[mid[k].data_ptr() if k in mid else None for k in OUTS])
-    rc = rd.lib.sdf_shade_points(C.byref(f.scene), larr, nl, int(flags), marr, len(materials),
-                                 C.byref(f.params), C.byref(p), C.byref(ps), None)
-    torch.cuda.synchronize()
-    assert rc == abi.SDF_OK, rc
-    for k, b in bufs.items():
-        assert untouched(torch, b[:GUARD]), f"{k}: entries in front of the buffer were written"
-        assert untouched(torch, b[GUARD + n:]), f"{k}: entries past the end were written"
-    got = {k: (mid[k].cpu().numpy() if k in mid else None) for k in OUTS}
-    return PR.RefShade(got["rgba"], got["ao"], got["shadow"], got["material"], got["steps"], None)
-
-
-_HITS = {}
-
-
-def hit_points(rd, name, pose):
-    """(P (851, 3), eye) of the exact frame: P_0 = O_0 + D_0 d formed on the host
-    in unfused fp32 from trace_camera's t and camera_rays, as the render forms
-    it."""
-    if (name, pose) not in _HITS:
-        assert (W, H) == (37, 23) and N == 851 == 13 * 64 + 19
-        f = the_frame(name, pose)
-        t = rd.trace_camera(f, normal=False, prim=False, steps=False).t
-        o, d = rd.camera_rays(f)
-        rd.torch.cuda.synchronize()
-        o, d, t = o.cpu().numpy(), d.cpu().numpy(), t.cpu().numpy()
-        P = PR.hit_points(o, d, t).reshape(N, 3)
-        eye = o.reshape(N, 3)[0].copy()
-        assert same(o.reshape(N, 3), np.tile(eye, (N, 1)))
-        P.setflags(write=False)
-        _HITS[(name, pose)] = (P, eye)
-    return _HITS[(name, pose)]
-
-
 # ---- 1. identity with the render -----------------------------------------------------------
 
 # (frame, pose, dispatch, a palette instead of the frame's one material)
@@ -193,7 +66,7 @@ def test_hit_points_shade_to_the_frame(renderer, name, pose, dispatch, pal):
     pixels, its shadow counts and SHADE32F's channel 0, bit for bit."""
     f = the_frame(name, pose, EXACT, dispatch)
     mats = mats_of(f, pal)
-    want, want_st = frame_both(renderer, f, mats, [f.light], 0)
+    want, want_st = frame_both(renderer, f, materials=mats, lights=[f.light])
     P, eye = hit_points(renderer, name, pose)
     got = shade(renderer, f, P, eye=eye, materials=mats)
     print(f"differing words: rgba {ndiff(got.rgba, want.reshape(N, 4))} of {4 * N}, "
@@ -329,33 +202,6 @@ def test_renderer_shade_points_is_the_abi_call(renderer):
 
 # ---- 4. fast precision ------------------------------------------------------------------------
 
-FAST_CASES = [("C4", 0, False), ("C3", 2, True), ("REF", 0, True)]
-
-
-def fast_deviation(rd, name, pose, pal):
-    """The largest absolute deviation of each output of the fast kernel from the
-    reference replayed at the kernel's own shadow counts, over all 851 hit
-    points under three coloured lights (`material`: where no hard decision of
-    the fold is closer than materials_ref.GAP), and how many points that is."""
-    f = the_frame(name, pose, FAST)
-    mats = mats_of(f, pal)
-    P, eye = hit_points(rd, name, pose)
-    got = shade(rd, f, P, eye=eye, lights=LIGHTS[:3], flags=CLR, materials=mats)
-    ref = PR.shade(the_frame(name, pose), P, eye=eye, lights=LIGHTS[:3], light_flags=CLR,
-                   materials=mats, steps=got.steps)
-    assert np.array_equal(ref.steps, np.minimum(got.steps, f.params.max_steps))
-    dev = {}
-    for k in ("rgba", "ao", "shadow"):
-        a, b = getattr(got, k).astype(np.float64), getattr(ref, k).astype(np.float64)
-        assert np.isfinite(a).all() and np.isfinite(b).all(), k
-        dev[k] = float(np.abs(a - b).max())
-    gap = np.array([MR.fold_at(f.scene, mats, *map(float, p))[2] for p in P], dtype=f32)
-    far = ~(gap < f32(MR.GAP))
-    dev["material"] = float(np.abs(got.material[far].astype(np.float64) -
-                                   ref.material[far].astype(np.float64)).max())
-    return dev, int(far.sum())
-
-
 @pytest.mark.parametrize("name,pose,pal", FAST_CASES)
 def test_fast_within_the_measured_bound(renderer, name, pose, pal):
     """Every point counts: the reference is replayed at the kernel's own shadow
@@ -411,16 +257,13 @@ def test_cpp_host_program_mesh_colors(renderer, tmp_path):
     bytes, which read_ply reads back."""
     import math
     import torch
-    exe = ROOT / "sdf3d_amd" / "bin" / "sdf_main"
-    assert exe.exists(), "build() must produce sdf3d_amd/bin/sdf_main"
     ply = tmp_path / "m.ply"
     n = BAKE_N
     lo = [float(x) for x in BAKE_ORIGIN]
     hi = [a + BAKE_CELL * n for a in lo]
-    r = subprocess.run([str(exe), "--palette", "--mesh", str(ply), "--mesh-colors", "--grid",
-                        ",".join(repr(x) for x in (*lo, *hi)) + f",{n}", "64", "36", "1",
-                        str(tmp_path / "f.ppm"), "csg8"], capture_output=True, text=True,
-                       timeout=120)
+    r = sdf_main("--palette", "--mesh", ply, "--mesh-colors", "--grid",
+                 ",".join(repr(x) for x in (*lo, *hi)) + f",{n}", "64", "36", "1",
+                 tmp_path / "f.ppm", "csg8")
     assert r.returncode == 0, r.stderr
     # the grid the program makes of the box: its extent over n in fp64, rounded once
     cell = tuple(float(f32((b - a) / n)) for a, b in zip(lo, hi))

@@ -18,52 +18,19 @@ import pytest
 import fast_paths as FP
 import materials_ref as MR
 import query_ref as Q
+from cases import JIT_SEEDS
+from cases import query_frame as frame_of
+from fast_paths import FAST_BOUND_N, FAST_BOUND_T
+from gpu_support import bitwise_eq, dev, ndiff, out_buf, ptr, sample, sdf_main, taken, trace
 from sdf3d_amd import abi, scenes
-from test_gpu_jit import custom_scene
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 EXACT, FAST = abi.PRECISION_EXACT, abi.PRECISION_FAST
-PAD, FILL_F, FILL_I = 64, -777.25, -777
-# REF, C1 and C4 are the built-in variants 1, 2 and 3; J<seed>: test_gpu_jit.py's
-# custom_scene(100 + seed), signatures with CSG operators that no built-in
-# variant has (run-time specialised under SDF_DISPATCH_AUTO)
+# REF, C1 and C4 are the built-in variants 1, 2 and 3; J<seed>: cases.JIT_SEEDS,
+# run-time specialised under SDF_DISPATCH_AUTO
 KINDS = ["REF", "C1", "C4", "C4-generic", "C4-unculled", "J0", "J4", "J6", "C5"]
-JIT_SEEDS = {"J0": 0, "J4": 4, "J6": 6}
-# Fast precision against the reference (query_ref.fast_deviation) on the
-# 200-ray set over REF, C4 and C5, measured on an MI355X
-# (profiles/query_C4.json fast_deviation, DESIGN.md "query"): the largest
-# deviation of `t` from the replay at the kernel's own step counts, relative to
-# max(1, |t|), and the largest absolute difference of a normal's component on
-# the rays whose steps agree with the oracle's.  The bounds asserted are 4 x
-# those, the headroom test_gpu_env.py, test_gpu_reflect.py and
-# test_gpu_materials.py give theirs (compiler versions contract differently;
-# the inputs are fixed).
-# (REF 4.72e-7 / 1.25e-6, C4 5.03e-6 / 5.96e-6, C5 1.919e-5 / 6.752e-5; no ray's
-# step count differed from the oracle's, no owner was wrong, none was left out)
-FAST_MEASURED_T = 1.919e-5
-FAST_MEASURED_N = 6.752e-5
-FAST_BOUND_T = 4 * FAST_MEASURED_T
-FAST_BOUND_N = 4 * FAST_MEASURED_N
-
-
-def frame_of(kind, prec=EXACT, wh=(64, 36)):
-    if kind in JIT_SEEDS:
-        seed = JIT_SEEDS[kind]
-        f = custom_scene(np.random.default_rng(100 + seed), 2 + seed % 7, *wh)
-    elif kind == "C4-carved":       # run-time specialised, with C4's arithmetic (fast_paths.py)
-        f = FP.PATHS[kind](prec, wh)
-    else:
-        f = scenes.config(kind.split("-")[0], *wh)
-        if kind.endswith("-generic"):
-            f.params.dispatch = abi.DISPATCH_GENERIC
-        if kind.endswith("-unculled"):
-            f.params.dispatch = abi.DISPATCH_UNCULLED
-    f.params.precision = prec
-    return f
-
-
 def all_rays():
     o, d = Q.ray_set()
     ho, hd = Q.hand_rays()
@@ -71,64 +38,6 @@ def all_rays():
 
 
 ZERO = Q.N_RAYS + Q.ZERO_DIR     # the zero direction's index in all_rays()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype.itemsize == 4 else a.dtype)
-
-
-def same(a, b):
-    """Bit for bit, NaN equal to NaN."""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.dtype.kind == "f":
-        return (bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))
-    return a == b
-
-
-def dev(rd, a):
-    return rd.torch.from_numpy(np.ascontiguousarray(a)).to(rd.device)
-
-
-def guarded(rd, n, comps, dtype, want=True):
-    """n * comps elements followed by PAD sentinels, all set to the sentinel."""
-    torch = rd.torch
-    if not want:
-        return None
-    fill = FILL_F if dtype == torch.float32 else FILL_I
-    return torch.full((n * comps + PAD,), fill, dtype=dtype, device=rd.device)
-
-
-def unguard(buf, n, comps):
-    """The first n entries, after checking that the sentinels behind them survived."""
-    if buf is None:
-        return None
-    a = buf.cpu().numpy()
-    fill = FILL_F if a.dtype == np.float32 else FILL_I
-    assert np.all(a[n * comps:] == fill), "sentinels behind an output were overwritten"
-    a = a[:n * comps]
-    return a.reshape(n, comps) if comps > 1 else a
-
-
-def ptr(x):
-    return C.c_void_p(x.data_ptr()) if x is not None else None
-
-
-def trace(rd, f, o, d, n=None, t=True, steps=True, normal=True, prim=True):
-    """sdf_trace of the first n rays through the C ABI into guarded buffers."""
-    torch = rd.torch
-    n = len(o) if n is None else n
-    O, D = dev(rd, o), dev(rd, d)
-    bt = guarded(rd, n, 1, torch.float32, t)
-    bs = guarded(rd, n, 1, torch.int32, steps)
-    bn = guarded(rd, n, 3, torch.float32, normal)
-    bp = guarded(rd, n, 1, torch.int32, prim)
-    h = abi.sdf_hits(ptr(bt), ptr(bs), ptr(bn), ptr(bp))
-    rc = rd.lib.sdf_trace(C.byref(f.scene), C.byref(f.params), ptr(O), ptr(D), n, C.byref(h),
-                          C.c_void_p(torch.cuda.current_stream(rd.device).cuda_stream))
-    abi.check(rc, "sdf_trace")
-    torch.cuda.synchronize()
-    return {"t": unguard(bt, n, 1), "steps": unguard(bs, n, 1), "normal": unguard(bn, n, 3),
-            "prim": unguard(bp, n, 1)}
 
 
 _cache = {}
@@ -146,13 +55,13 @@ def exact_run(rd, kind):
         again = trace(rd, f, o, d)
         n2 = rd.lib.sdf_jit_count()
         for k in got:
-            assert np.all(same(got[k], again[k])), f"{kind}: {k} differs between two calls"
+            assert np.all(bitwise_eq(got[k], again[k])), f"{kind}: {k} differs between two calls"
         _cache[kind] = (got, Q.trace(f, o, d), n1 - n0, n2 - n1)
     return _cache[kind]
 
 
 def report(kind, got, ref, rays):
-    bad = {k: int((~same(got[k], ref[k]))[rays].sum()) for k in ("t", "steps", "normal", "prim")}
+    bad = {k: int((~bitwise_eq(got[k], ref[k]))[rays].sum()) for k in ("t", "steps", "normal", "prim")}
     print(f"{kind}: {len(rays)} rays, {int(ref['hit'][rays].sum())} hit; mismatches {bad}")
     return bad
 
@@ -205,25 +114,25 @@ def test_exact_nonfinite_directions_equal_the_reference(renderer, kind):
     mixed = trace(renderer, f, o, d)
     rest = np.array([i for i in range(64) if i not in at])
     for k in mixed:
-        assert np.all(same(mixed[k][rest], full[k][rest])), k
-        assert np.all(same(mixed[k][at], got[k][:4])), k
+        assert np.all(bitwise_eq(mixed[k][rest], full[k][rest])), k
+        assert np.all(bitwise_eq(mixed[k][at], got[k][:4])), k
 
 
 # 2. independence of n and lane ----------------------------------------------------
 @pytest.mark.parametrize("n", [1, 63, 64, 65])
 def test_results_do_not_depend_on_n(renderer, n):
     """The first n results equal those of the 205-ray run, bit for bit, and the
-    64 sentinels behind each output are untouched (unguard)."""
+    guard behind each output is untouched (gpu_support.taken)."""
     full, _, _, _ = exact_run(renderer, "C4")
     o, d = all_rays()
     got = trace(renderer, frame_of("C4"), o, d, n=n)
     for k in got:
-        assert len(got[k]) == n and np.all(same(got[k], full[k][:n])), k
+        assert len(got[k]) == n and np.all(bitwise_eq(got[k], full[k][:n])), k
 
 
 def test_no_rays_write_nothing(renderer):
     o, d = all_rays()
-    got = trace(renderer, frame_of("C4"), o, d, n=0)      # unguard checks every element
+    got = trace(renderer, frame_of("C4"), o, d, n=0)      # every element is guard
     assert all(len(v) == 0 for v in got.values())
     empty = renderer.torch.zeros((0, 3), dtype=renderer.torch.float32, device=renderer.device)
     h = renderer.trace(frame_of("C4"), empty, empty)
@@ -243,7 +152,7 @@ def test_output_selection_does_not_change_the_bits(renderer, sel):
     got = trace(renderer, frame_of("C4"), o, d, **{k: k in sel for k in full})
     for k in full:
         if k in sel:
-            assert np.all(same(got[k], full[k])), k
+            assert np.all(bitwise_eq(got[k], full[k])), k
         else:
             assert got[k] is None
 
@@ -255,7 +164,7 @@ def test_renderer_trace_is_the_abi_call(renderer):
     h = renderer.trace(frame_of("C4"), dev(renderer, o), dev(renderer, d))
     renderer.torch.cuda.synchronize()
     for k in full:
-        assert np.all(same(getattr(h, k).cpu().numpy(), full[k])), k
+        assert np.all(bitwise_eq(getattr(h, k).cpu().numpy(), full[k])), k
     h = renderer.trace(frame_of("C4"), dev(renderer, o), dev(renderer, d), normal=False,
                        prim=False)
     assert h.normal is None and h.prim is None and h.t.shape == (len(o),)
@@ -303,7 +212,7 @@ def check_camera_rays(renderer, name, wh):
         if prec == EXACT:
             O, D = Q.camera_rays(f)
             ref = Q.hits(f, O, D)
-            bad = {k: int((~same(got[k].reshape(ref[k].shape), ref[k])).sum())
+            bad = {k: int((~bitwise_eq(got[k].reshape(ref[k].shape), ref[k])).sum())
                    for k in ("t", "steps", "normal", "prim")}
             print(f"{name} {wh}: {int(ref['hit'].sum())} of {W * H} pixels hit; mismatches {bad}")
             assert bad == {"t": 0, "steps": 0, "normal": 0, "prim": 0}
@@ -326,24 +235,24 @@ def test_points_equal_the_oracle(renderer, kind):
     f = frame_of(kind)
     P = Q.grid()
     n = len(P)
-    bd = guarded(renderer, n, 1, torch.float32)
-    bn = guarded(renderer, n, 3, torch.float32)
+    bd = out_buf(renderer, n, 1, torch.float32)
+    bn = out_buf(renderer, n, 3, torch.float32)
     Pd = dev(renderer, P)
     rc = renderer.lib.sdf_sample(C.byref(f.scene), C.byref(f.params), ptr(Pd), n, ptr(bd),
                                  ptr(bn), None)
     abi.check(rc, "sdf_sample")
     torch.cuda.synchronize()
-    dist, nrm = unguard(bd, n, 1), unguard(bn, n, 3)
+    dist, nrm = taken(renderer, bd), taken(renderer, bn)
     rdist, rnrm = Q.scene_sdf(f, P), Q.normals(f, P)
     assert (rdist < 0).sum() >= 5 and (P[:, 1] < 0).sum() >= 100    # inside, and below the floor
-    bad = (int((~same(dist, rdist)).sum()), int((~same(nrm, rnrm)).sum()))
+    bad = (int((~bitwise_eq(dist, rdist)).sum()), int((~bitwise_eq(nrm, rnrm)).sum()))
     print(f"{kind}: {n} points, {int((rdist < 0).sum())} inside; mismatches dist, normal {bad}")
     assert bad == (0, 0)
     d2, n2 = renderer.sample(f, dev(renderer, P), normal=True)
     d1, none = renderer.sample(f, dev(renderer, P))
     torch.cuda.synchronize()
-    assert none is None and np.all(same(d2.cpu().numpy(), dist))
-    assert np.all(same(d1.cpu().numpy(), dist)) and np.all(same(n2.cpu().numpy(), nrm))
+    assert none is None and np.all(bitwise_eq(d2.cpu().numpy(), dist))
+    assert np.all(bitwise_eq(d1.cpu().numpy(), dist)) and np.all(bitwise_eq(n2.cpu().numpy(), nrm))
 
 
 # 6. fast precision, buffer rays --------------------------------------------------------
@@ -361,7 +270,7 @@ def counted(rd, key, call):
     if key is not None:
         assert (n1 - n0, n2 - n1) == (FP.first_use(key), 0), (key, n1 - n0, n2 - n1)
     for k in got:
-        assert np.all(same(got[k], again[k])), f"{key}: {k} differs between two calls"
+        assert np.all(bitwise_eq(got[k], again[k])), f"{key}: {k} differs between two calls"
     return got
 
 
@@ -383,7 +292,7 @@ def test_fast_rays_within_the_measured_bound(renderer, name):
                   lambda: trace(renderer, f, o, d))
     r = Q.fast_deviation(frame_of(name), o, d, got, MR.GAP)
     exact = exact_run(renderer, name)[0]
-    differ = {k: FP.bits_differ(got[k], exact[k][:len(o)]) for k in ("t", "normal")}
+    differ = {k: ndiff(got[k], exact[k][:len(o)]) for k in ("t", "normal")}
     print(f"{name}: fast deviation {r}; bounds t {FAST_BOUND_T:.3e} normal {FAST_BOUND_N:.3e}; "
           f"words differing from the exact result {differ}")
     assert r["prim_left_out"] <= 0.02 * r["hit"]
@@ -394,20 +303,6 @@ def test_fast_rays_within_the_measured_bound(renderer, name):
 
 
 # 6b. fast precision, points ------------------------------------------------------------
-def sample(rd, f, P, n=None, normal=True):
-    """sdf_sample of the first n points through the C ABI into guarded buffers."""
-    torch = rd.torch
-    n = len(P) if n is None else n
-    Pd = dev(rd, P)
-    bd = guarded(rd, n, 1, torch.float32)
-    bn = guarded(rd, n, 3, torch.float32, normal)
-    rc = rd.lib.sdf_sample(C.byref(f.scene), C.byref(f.params), ptr(Pd), n, ptr(bd), ptr(bn),
-                           C.c_void_p(torch.cuda.current_stream(rd.device).cuda_stream))
-    abi.check(rc, "sdf_sample")
-    torch.cuda.synchronize()
-    return {"dist": unguard(bd, n, 1), "normal": unguard(bn, n, 3)}
-
-
 @pytest.mark.parametrize("kind", ["REF", "C4", "C4-generic", "C4-unculled", "C4-carved", "C5"])
 def test_fast_points_within_the_bound(renderer, kind):
     """Fast sdf_sample on the 17 x 13 x 11 grid, on all five launch paths,
@@ -425,7 +320,7 @@ def test_fast_points_within_the_bound(renderer, kind):
     got = counted(renderer, ("sample", kind) if kind in FP.JIT else None,
                   lambda: sample(renderer, f, P))
     exact = sample(renderer, frame_of(kind), P)
-    differ = {k: FP.bits_differ(got[k], exact[k]) for k in got}
+    differ = {k: ndiff(got[k], exact[k]) for k in got}
     r = FP.point_deviation(frame_of(kind), P, got["dist"], got["normal"])
     print(f"{kind}: fast deviation {r}; bounds dist {FAST_BOUND_T:.3e} normal {FAST_BOUND_N:.3e}; "
           f"words differing from the exact result {differ}")
@@ -437,19 +332,15 @@ def test_fast_points_within_the_bound(renderer, kind):
         for n in (1, 63, 64, 65):
             part = sample(renderer, f, P, n=n)
             for k in part:
-                assert len(part[k]) == n and np.all(same(part[k], got[k][:n])), (k, n)
+                assert len(part[k]) == n and np.all(bitwise_eq(part[k], got[k][:n])), (k, n)
         only = sample(renderer, f, P, normal=False)
-        assert only["normal"] is None and np.all(same(only["dist"], got["dist"]))
+        assert only["normal"] is None and np.all(bitwise_eq(only["dist"], got["dist"]))
 
 
 # 7. the C++ host program -----------------------------------------------------------------
 def test_cpp_host_program_pick(renderer, tmp_path):
     """sdf_main --pick X,Y prints the record Renderer.trace_camera gives for
     that pixel (the last frame's camera; frame 1 of 2 is yaw 180)."""
-    import subprocess
-    from pathlib import Path
-    exe = Path(__file__).resolve().parent.parent / "sdf3d_amd" / "bin" / "sdf_main"
-    assert exe.exists(), "build() must produce sdf3d_amd/bin/sdf_main"
     f = scenes.config("C3", 160, 90)                                  # sdf_main's csg8
     scenes.set_view(f, scenes.orbit_view(180.0, 0.0))
     h = renderer.trace_camera(f)
@@ -461,14 +352,12 @@ def test_cpp_host_program_pick(renderer, tmp_path):
     ys, xs = np.nonzero(prim < 0)
     picks.append((int(xs[0]), int(ys[0])))
     for x, y in picks:
-        r = subprocess.run([str(exe), "--pick", f"{x},{y}", "160", "90", "2",
-                            str(tmp_path / "f.ppm"), "csg8"], capture_output=True, text=True,
-                           timeout=120)
+        r = sdf_main("--pick", f"{x},{y}", "160", "90", "2", tmp_path / "f.ppm", "csg8")
         assert r.returncode == 0, r.stderr
         line = [l for l in r.stdout.splitlines() if l.startswith(f"pick {x},{y}: ")]
         assert len(line) == 1, r.stdout
         v = line[0].split(": ")[1].split()
         assert len(v) == 6
-        assert np.all(same(f32(v[0]), h.t[y, x].cpu().numpy()))
+        assert np.all(bitwise_eq(f32(v[0]), h.t[y, x].cpu().numpy()))
         assert int(v[1]) == int(h.steps[y, x]) and int(v[2]) == int(prim[y, x])
-        assert np.all(same(np.array(v[3:], dtype=f32), h.normal[y, x].cpu().numpy()))
+        assert np.all(bitwise_eq(np.array(v[3:], dtype=f32), h.normal[y, x].cpu().numpy()))

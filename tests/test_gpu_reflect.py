@@ -7,14 +7,11 @@ within a measured bound against the reference in fast precision -- on every
 dispatch path, for every output format, tiling, a schedule and supersampling.
 
 Shape 37 x 23 (partial 8 x 8 tiles in x and y, a last block of 7 rows); the
-supersampled cases use test_gpu_ssaa.py's shapes.  Every render writes into
+supersampled cases use cases.SHAPES.  Every render writes into
 buffers followed by sentinel rows, which must survive, and every case is
 rendered with and without a steps buffer, which must not change the colours.
 The SIX scenes run the generic kernel except where a test is about the path."""
-import ctypes as C
 import os
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -22,11 +19,11 @@ import pytest
 import lights_ref as LR
 import materials_ref as MR
 import reflect_ref as RR
+import gpu_support as G
 import ssaa_ref
-from parity import quantize
+from cases import frame_of, mats_of, mirror_scene
+from gpu_support import SHAPES, bits, hi_frame, ndiff, read_ppm, rgba_of, same, sdf_main
 from sdf3d_amd import abi, renderer as R, scenes
-from test_gpu_ssaa import (FILL, SHAPES, _guarded, _sentinel, bits, hi_frame, owned_row_index,
-                           read_ppm, same)
 
 pytestmark = pytest.mark.gpu
 
@@ -46,80 +43,19 @@ FAST_MEASURED = 1.615e-4
 FAST_BOUND = 4 * FAST_MEASURED
 
 
-def mirror_scene(prec, wh=RR.SHAPE, swapped=False):
-    """plane, round box (hard union), torus (smooth union) -- `swapped`: plane,
-    torus, round box: no built-in variant, so SDF_DISPATCH_AUTO compiles its
-    kernel at run time (hipRTC); signatures no other test file uses, and
-    `swapped` only the test that counts its compilations."""
-    f = scenes.config("C3", *wh, precision=prec, pose=2)
-    C.memset(C.addressof(f.scene.prims), 0, C.sizeof(f.scene.prims))
-    f.scene.count = 3
-    scenes._prim(f.scene, 0, abi.PRIM_PLANE, abi.OP_UNION, 0.0, 0.0, 1.0, 0.0, 0.0)
-    box, tor = (2, 1) if swapped else (1, 2)
-    scenes._prim(f.scene, box, abi.PRIM_ROUND_BOX, abi.OP_UNION, 0.0, -0.4, 0.25, 0.1, 0.2, 0.2,
-                 0.2, 0.05)
-    scenes._prim(f.scene, tor, abi.PRIM_TORUS, abi.OP_SMOOTH_UNION, 0.08, 0.45, 0.12, 0.0, 0.25,
-                 0.08)
-    return f
-
-
-def frame_of(name, pose, prec=EXACT, dispatch=None):
-    """The frame `name` (materials_ref.FRAMES, C5, or RJ: mirror_scene).  SIX
-    and SIXH run the generic kernel unless `dispatch` says otherwise."""
-    if name == "RJ":
-        f = mirror_scene(prec)
-    elif name == "C5":
-        f = scenes.config("C5", *RR.SHAPE, precision=prec, pose=pose)
-    else:
-        f = MR.frame_of(name, pose, prec)
-    if dispatch is None:
-        dispatch = abi.DISPATCH_GENERIC if name in ("SIX", "SIXH") else abi.DISPATCH_AUTO
-    f.params.dispatch = dispatch
-    return f
-
-
-def mats_of(f):
-    return MR.palette_for(f) if f.scene.kind == abi.SCENE_PRIMITIVES else [f.material]
+def shading(reflect, materials=None, lights=None, flags=0):
+    return dict(reflect=reflect, materials=materials, lights=lights, light_flags=flags)
 
 
 def render(rd, frame, reflect, materials=None, lights=None, flags=0, t=None, steps=True,
            schedule=None):
-    """Renderer.render (with `reflect`: sdf_render_reflect; None with
-    `materials`: sdf_render_materials) into sentinel-filled buffers with guard
-    rows behind them, which are checked."""
-    import torch
-    p = frame.params
-    rows = R.buffer_rows(p.height, t)
-    shape = (rows, p.width, R.channels(p.output_format))
-    buf = _guarded(torch, rd.device, shape, R.torch_dtype(p.output_format))
-    sshape = R.steps_shape(frame, t)
-    sbuf = _guarded(torch, rd.device, sshape, torch.int32) if steps else None
-    rd.render(frame, t, out=buf[:rows], steps=sbuf[:sshape[0]] if steps else False,
-              schedule=schedule, lights=lights, light_flags=flags, materials=materials,
-              reflect=reflect)
-    torch.cuda.synchronize()
-    assert _sentinel(torch, buf[rows:]), "colour buffer: rows past the end were written"
-    if steps:
-        assert _sentinel(torch, sbuf[sshape[0]:]), "steps buffer: rows past the end were written"
-    return buf[:rows].cpu().numpy(), (sbuf[:sshape[0]].cpu().numpy() if steps else None)
+    """gpu_support.render with `reflect`: sdf_render_reflect; None with
+    `materials`: sdf_render_materials."""
+    return G.render(rd, frame, t, steps, schedule, **shading(reflect, materials, lights, flags))
 
 
 def both(rd, frame, reflect, materials=None, lights=None, flags=0, t=None):
-    a, _ = render(rd, frame, reflect, materials, lights, flags, t, steps=False)
-    b, st = render(rd, frame, reflect, materials, lights, flags, t, steps=True)
-    assert same(a, b), "renders with and without a steps buffer differ"
-    return a, st
-
-
-def ndiff(a, b):
-    a, b = (np.ascontiguousarray(v).view(np.uint32) for v in (a, b))
-    return int((a != b).sum())
-
-
-def rgba_of(rgb):
-    out = np.ones(rgb.shape[:2] + (4,), dtype=f32)
-    out[..., :3] = rgb
-    return out
+    return G.both(rd, frame, t, **shading(reflect, materials, lights, flags))
 
 
 # ---- the reference, computed once per case and shared read-only ----------------
@@ -180,27 +116,6 @@ def test_exact_mandelbulb_equals_reference(renderer, n, flags):
 
 # ---- 2. both precisions, from the kernel's own pieces ----------------------------
 
-def own_layers(rd, f, bounces, strength, mats, lights, flags):
-    """The kernel's own layer colours, weights and steps: C, W [H, W, J, 3],
-    steps [H, W, J, 2], alive [H, W, J] (a traced layer took a primary step)."""
-    Cs, Ws, Ss = [], [], []
-    for j in range(bounces + 1):
-        cj, sj = both(rd, f, RR.reflect(bounces, strength, j), mats, lights, flags)
-        wj, wsj = both(rd, f, RR.reflect(bounces, strength, j, WEIGHT), mats, lights, flags)
-        assert np.array_equal(sj, wsj)
-        assert (cj[..., 3] == 1).all() and (wj[..., 3] == 1).all()
-        Cs.append(cj[..., :3])
-        Ws.append(wj[..., :3])
-        Ss.append(sj)
-    Cj, Wj, Sj = (np.stack(v, axis=2) for v in (Cs, Ws, Ss))
-    alive = Sj[..., 0] > 0
-    # a path that has ended leaves zeros
-    for a in (Cj, Wj):
-        assert (bits(a[~alive]) == 0).all()
-    assert (Sj[~alive] == 0).all()
-    return Cj, Wj, Sj, alive
-
-
 @pytest.mark.parametrize("prec", PRECS)
 @pytest.mark.parametrize("name,pose,n,flags", [("C4", 0, 2, abi.LIGHTS_COLOR), ("SIX", 2, 1, 0),
                                                ("C5", 0, 2, abi.LIGHTS_COLOR)])
@@ -208,7 +123,7 @@ def test_composite_is_the_fold_of_own_layers(renderer, name, pose, n, flags, pre
     assert reference(name, pose, 3, n, flags, 0.75)[2]["alive"][:, :, 2].mean() > 0.02
     f = frame_of(name, pose, prec)
     mats, lights = mats_of(f), LIGHTS[:n]
-    Cj, Wj, Sj, alive = own_layers(renderer, f, 3, 0.75, mats, lights, flags)
+    Cj, Wj, Sj, alive = G.own_layers(lambda r: both(renderer, f, r, mats, lights, flags), 3, 0.75)
     assert alive[:, :, 0].all() and (bits(Wj[:, :, 0]) == bits(np.ones(3, f32))).all()
     assert alive[:, :, 1].mean() > 0.02 and alive[:, :, 3].any()
     out, st = both(renderer, f, RR.reflect(3, 0.75), mats, lights, flags)
@@ -238,19 +153,11 @@ def test_no_bounce_is_sdf_render_materials(renderer, fmt, prec):
 
 @pytest.mark.parametrize("prec", PRECS)
 def test_no_bounce_tiles_stream(renderer, prec):
-    import torch
     f = frame_of("C4", 0, prec)
     f.params.output_format = abi.FORMAT_TILES
     mats = [type(f.material).from_buffer_copy(f.material) for _ in range(f.scene.count)]
-    w, h = f.params.width, f.params.height
-    a, b = (torch.zeros(R.tiles_bytes(w, h), dtype=torch.uint8, device=renderer.device)
-            for _ in range(2))
-    renderer.render(f, out=a, lights=[LIGHTS[1]], materials=mats)
-    renderer.render(f, out=b, lights=[LIGHTS[1]], materials=mats, reflect=(0, 1.0))
-    torch.cuda.synchronize()
-    n = R.tiles_stream_bytes(a)
-    assert n == R.tiles_stream_bytes(b) and n > abi.TILES_HEADER_BYTES
-    assert torch.equal(a[:n], b[:n])
+    kw = dict(lights=[LIGHTS[1]], materials=mats)
+    G.tiles_streams(renderer, f, kw, dict(kw, reflect=(0, 1.0)))
 
 
 @pytest.mark.parametrize("prec", PRECS)
@@ -312,7 +219,7 @@ def test_runtime_specialised_scene_compiles_one_kernel(renderer, prec):
     out2, st = render(renderer, f, RR.reflect(2, 0.75), mats, lights, steps=True)
     assert same(out2, out) and np.array_equal(st, want_st)
     assert count() - before == (2 if jit else 0)
-    Cj, Wj, Sj, alive = own_layers(renderer, f, 2, 0.75, mats, lights, 0)
+    Cj, Wj, Sj, alive = G.own_layers(lambda r: both(renderer, f, r, mats, lights, 0), 2, 0.75)
     assert same(out, RR.composite(Cj, Wj, alive, prec)) and np.array_equal(st, Sj.sum(axis=2))
     assert count() - before == (2 if jit else 0)
     g = f.copy()
@@ -332,11 +239,7 @@ def test_formats_convert_the_composite(renderer, prec):
     full, _ = render(renderer, f, r, mats, lights, abi.LIGHTS_COLOR, steps=False)
     plain, _ = render(renderer, f, None, mats, lights, abi.LIGHTS_COLOR, steps=False)
     assert np.abs(full - plain).max() > 0.1
-    for fmt in (abi.FORMAT_RGBA16F, abi.FORMAT_RGBA8, abi.FORMAT_RGB32F):
-        g = f.copy()
-        g.params.output_format = fmt
-        out, _ = both(renderer, g, r, mats, lights, abi.LIGHTS_COLOR)
-        assert same(out, quantize(full, fmt)), fmt
+    G.check_formats(renderer, f, full, **shading(r, mats, lights, abi.LIGHTS_COLOR))
 
 
 @pytest.mark.parametrize("fmt", [abi.FORMAT_TILES, abi.FORMAT_SHADE32F])
@@ -365,23 +268,7 @@ def test_tilings(renderer, world, shares, prec):
     f = frame_of("C3", 2, prec)
     mats, lights, flags = mats_of(f), LIGHTS[:2], abi.LIGHTS_COLOR
     r = RR.reflect(2, 1.0)
-    w, h = f.params.width, f.params.height
-    whole, whole_st = both(renderer, f, r, mats, lights, flags)
-    seen = np.zeros(h, dtype=int)
-    for rank in range(world):
-        t = R.tiling(rank, world, 8, shares=shares)
-        rows = owned_row_index(h, t)
-        assert len(rows) == R.owned_rows(h, t)
-        seen[rows] += 1
-        out, st = both(renderer, f, r, mats, lights, flags, t)
-        assert out.shape == (len(rows), w, 4)
-        assert same(out, whole[rows]) and np.array_equal(st, whole_st[rows])
-        tf = R.tiling(rank, world, 8, frame_rows=True, shares=shares)
-        fr, fr_st = both(renderer, f, r, mats, lights, flags, tf)
-        other = np.setdiff1d(np.arange(h), rows)
-        assert same(fr[rows], whole[rows]) and np.array_equal(fr_st[rows], whole_st[rows])
-        assert (bits(fr[other]) == FILL).all() and (bits(fr_st[other]) == FILL).all()
-    assert (seen == 1).all()
+    G.check_tilings(renderer, f, world, shares, **shading(r, mats, lights, flags))
 
 
 @pytest.mark.parametrize("prec", PRECS)
@@ -389,15 +276,7 @@ def test_scheduled(renderer, prec):
     f = frame_of("C3", 2, prec)
     mats, lights = mats_of(f), LIGHTS[:2]
     r = RR.reflect(2, 1.0)
-    ref, ref_st = render(renderer, f, r, mats, lights, steps=True)
-    sch = renderer.schedule(f.params.height, period=1)
-    try:
-        for _ in range(3):
-            out, st = render(renderer, f, r, mats, lights, steps=True, schedule=sch)
-            assert same(out, ref) and np.array_equal(st, ref_st)
-        assert sorted(sch.order()) == list(range((f.params.height + 7) // 8))
-    finally:
-        sch.close()
+    G.check_scheduled(renderer, f, **shading(r, mats, lights))
 
 
 @pytest.mark.parametrize("prec", PRECS)
@@ -441,7 +320,7 @@ def test_fast_is_near_the_reference(renderer, name, bounces):
     is 4 x the largest, FAST_BOUND = 6.46e-4."""
     f, mats = fast_case(name)
     lights = [LIGHTS[0]]
-    _, _, Sj, alive = own_layers(renderer, f, bounces, 1.0, mats, lights, 0)
+    _, _, Sj, alive = G.own_layers(lambda r: both(renderer, f, r, mats, lights, 0), bounces, 1.0)
     out, st = both(renderer, f, RR.reflect(bounces, 1.0), mats, lights, 0)
     assert np.array_equal(st, Sj.sum(axis=2))
     force = np.zeros(alive.shape + (RR.FORCE,), dtype=np.int32)
@@ -461,8 +340,6 @@ def test_fast_is_near_the_reference(renderer, name, bounces):
 # ---- 7. the C++ host program -------------------------------------------------------
 
 def test_cpp_host_program_reflect_option(renderer, tmp_path):
-    exe = Path(__file__).resolve().parent.parent / "sdf3d_amd" / "bin" / "sdf_main"
-    assert exe.exists(), "build() must produce sdf3d_amd/bin/sdf_main"
     f = scenes.config("C3", 160, 90, precision=EXACT)                 # sdf_main's default
     scenes.set_view(f, scenes.orbit_view(180.0, 0.0))                 # frame 1 of 2: yaw 180
     f.params.output_format = abi.FORMAT_RGBA8
@@ -471,15 +348,13 @@ def test_cpp_host_program_reflect_option(renderer, tmp_path):
     plain, _ = render(renderer, f, None, pal, [f.light], 0, steps=False)
     assert not same(want, plain)
     out = tmp_path / "f.ppm"
-    r = subprocess.run([str(exe), "160", "90", "2", str(out), "csg8", "--palette", "--reflect",
-                        "2"], capture_output=True, text=True, timeout=120)
+    r = sdf_main("160", "90", "2", out, "csg8", "--palette", "--reflect", "2")
     assert r.returncode == 0, r.stderr
     img = read_ppm(out)
     assert img.shape == (90, 160, 3)
     assert np.array_equal(img, want[::-1, :, :3])
     # a strength, the option in front, and one material for every primitive
     half, _ = render(renderer, f, RR.reflect(1, 0.5), None, [f.light], 0, steps=False)
-    r = subprocess.run([str(exe), "--reflect", "1,0.5", "160", "90", "2", str(out), "csg8"],
-                       capture_output=True, text=True, timeout=120)
+    r = sdf_main("--reflect", "1,0.5", "160", "90", "2", out, "csg8")
     assert r.returncode == 0, r.stderr
     assert np.array_equal(read_ppm(out), half[::-1, :, :3])

@@ -25,8 +25,9 @@ import pytest
 
 import offsets as O
 import oracle
+from bounds_ref import check_containment
+from cases import random_scene
 from sdf3d_amd import abi, scenes
-from test_bounds import check_containment, random_scene
 
 NAMES = list(O.OFFSETS)
 
@@ -78,11 +79,11 @@ def test_translation_moves_everything_and_scales_nothing(name):
 @pytest.mark.parametrize("seed", range(3))
 @pytest.mark.parametrize("name", NAMES)
 def test_translated_scenes_are_contained(name, seed):
-    """Random scenes of every kind (test_bounds.random_scene) moved by T: every
+    """Random scenes of every kind (cases.random_scene) moved by T: every
     primitive's true sphere, float64 from its fp32 parameters, lies inside the
     sphere the kernel reads, |c_f - c_true| + R_true <= K'(1 - kCullRel) -
     kCullAbs - k, and the cullable ones inside the cluster sphere -- with no
-    tolerance at all (test_bounds.check_containment)."""
+    tolerance at all (bounds_ref.check_containment)."""
     rng = np.random.default_rng(7000 + seed)
     while True:     # a draw that ends in a hard-union sphere culls little: one with a subject
         scene = random_scene(rng, abi.SDF_MAX_PRIMS)

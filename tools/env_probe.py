@@ -38,6 +38,7 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 sys.path.insert(0, str(ROOT / "tools"))
 
+import gpu_support as G  # noqa: E402
 from lights_probe import measure  # noqa: E402  (the same windows and alternation)
 
 
@@ -53,15 +54,15 @@ def ratios(ms, base="reflect"):
     return out
 
 
-def miss_shares(np, rd, RR, f, bounces, mats, lights, env):
+def miss_shares(np, rd, f, bounces, mats, lights, env):
     """Per layer: pixels reached, pixels that miss there, and the share of the
     reached 8 x 8 tiles whose reached lanes all miss (from layer = j renders
     with SKY and step counts: a sky layer counts no shadow step)."""
     out = []
+    _, _, Sj, _ = G.own_layers(lambda r: G.both(rd, f, lights=lights, materials=mats, reflect=r,
+                                                env=env), bounces, 1.0)
     for j in range(bounces + 1):
-        _, st = rd.render(f, steps=True, lights=lights, materials=mats,
-                          reflect=RR.reflect(bounces, 1.0, j), env=env)
-        st = st.cpu().numpy()
+        st = Sj[:, :, j]
         alive, miss = st[..., 0] > 0, (st[..., 0] > 0) & (st[..., 1] == 0)
         H, W = alive.shape
         th, tw = (H + 7) // 8, (W + 7) // 8
@@ -127,7 +128,7 @@ def main():
                                                                   **kw))
                 r = {"config": config, "precision": prec, "bounces": b}
                 r.update(ratios(measure(torch, legs, s, a.window, a.repeats)))
-                r["layers"] = miss_shares(np, rd, RR, f, b, mats, lights, envs["sky"])
+                r["layers"] = miss_shares(np, rd, f, b, mats, lights, envs["sky"])
                 rec["results"].append(r)
                 print(json.dumps(r), flush=True)
             del out
@@ -142,10 +143,8 @@ def main():
             mats = RR.materials_for(f) if name == "REF" else MR.palette_for(f)
             lights = LR.rig(1)
             for b in (1, 2):
-                Ss = [rd.render(f, steps=True, lights=lights, materials=mats,
-                                reflect=RR.reflect(b, 1.0, j), env=env)[1].cpu().numpy()
-                      for j in range(b + 1)]
-                Sj = np.stack(Ss, axis=2)
+                _, _, Sj, _ = G.own_layers(lambda r: G.both(rd, f, lights=lights, materials=mats,
+                                                            reflect=r, env=env), b, 1.0)
                 got = rd.render(f, lights=lights, materials=mats, reflect=(b, 1.0),
                                 env=env)[0].cpu().numpy()
                 d, left_out, pixels = ER.fast_deviation(f, mats, lights, env, b, got, Sj,

@@ -124,7 +124,7 @@ def main():
         torch.cuda.empty_cache()
 
     if not a.no_deviation:
-        from test_gpu_points import FAST_CASES, fast_deviation
+        from points_ref import FAST_CASES, fast_deviation
         dev = {}
         for name, pose, pal in FAST_CASES:
             d, far = fast_deviation(rd, name, pose, pal)

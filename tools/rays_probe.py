@@ -20,7 +20,7 @@ frame bit for bit in exact precision (asserted); in fast precision the number
 of differing words is recorded (the frame render contracts layer 0 around a
 uniform eye).  Recorded too -- at the tests' 37 x 23 shape -- the largest
 deviation of the fast rays composite from the reference replayed at the
-kernel's step counts (tests/test_gpu_rays.py asserts test_gpu_env.FAST_BOUND).
+kernel's step counts (tests/test_gpu_rays.py asserts fast_paths.ENV_BOUND).
 
     python tools/rays_probe.py --out profiles/rays_C4.json
 """
@@ -140,7 +140,7 @@ def main():
     if not a.no_deviation:
         # fast precision's composite of the camera's rays against the reference,
         # at the tests' shape and by the tests' own comparison
-        from test_gpu_rays import rays_fast_deviation
+        from gpu_support import rays_fast_deviation
         dev = {}
         for name in ("C4", "C3", "REF"):
             for b in (1, 2):

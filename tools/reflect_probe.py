@@ -43,6 +43,7 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 sys.path.insert(0, str(ROOT / "tools"))
 
+import gpu_support as G  # noqa: E402
 from lights_probe import measure  # noqa: E402  (the same windows and alternation)
 
 
@@ -58,19 +59,10 @@ def ratios(ms, base="materials"):
     return out
 
 
-def own_layers(np, rd, RR, f, bounces, mats, lights):
-    """The kernel's own C_j, W_j, steps and alive planes (layer = j renders)."""
-    Cs, Ws, Ss = [], [], []
-    for j in range(bounces + 1):
-        c, st = rd.render(f, steps=True, lights=lights, materials=mats,
-                          reflect=RR.reflect(bounces, 1.0, j))
-        w, _ = rd.render(f, lights=lights, materials=mats,
-                         reflect=RR.reflect(bounces, 1.0, j, 1))
-        Cs.append(c.cpu().numpy()[..., :3].copy())
-        Ws.append(w.cpu().numpy()[..., :3].copy())
-        Ss.append(st.cpu().numpy())
-    Cj, Wj, Sj = (np.stack(v, axis=2) for v in (Cs, Ws, Ss))
-    return Cj, Wj, Sj, Sj[..., 0] > 0
+def kernel_layers(rd, f, bounces, mats, lights):
+    """The kernel's own C_j, W_j, steps and alive planes (tests/gpu_support.py)."""
+    return G.own_layers(lambda r: G.both(rd, f, lights=lights, materials=mats, reflect=r),
+                        bounces, 1.0)
 
 
 def tile_shares(np, alive):
@@ -146,7 +138,7 @@ def main():
                 legs[name] = (lambda r=r: r.render(f, materials=mats, reflect=(2, 1.0), **kw))
             r = {"precision": prec, "lights": L}
             r.update(ratios(measure(torch, legs, s, a.window, a.repeats)))
-            Cj, Wj, Sj, alive = own_layers(np, rd, RR, f, 2, mats, lights)
+            Cj, Wj, Sj, alive = kernel_layers(rd, f, 2, mats, lights)
             share = tile_shares(np, alive)
             r["live_tile_share"] = share
             r["live_pixel_share"] = [round(float(alive[..., j].mean()), 5) for j in range(3)]
@@ -171,7 +163,7 @@ def main():
         mats = RR.materials_for(f) if name == "REF" else MR.palette_for(f)
         lights = LR.rig(1)
         for b in (1, 2):
-            _, _, Sj, alive = own_layers(np, rd, RR, f, b, mats, lights)
+            _, _, Sj, alive = kernel_layers(rd, f, b, mats, lights)
             got = rd.render(f, lights=lights, materials=mats,
                             reflect=(b, 1.0))[0].cpu().numpy()
             force = np.zeros(alive.shape + (RR.FORCE,), dtype=np.int32)
