@@ -7,7 +7,8 @@
 //
 //   sdf_main [--palette] [--reflect B[,strength]] [--sky [--no-sun]] [--fog START,END[,r,g,b]]
 //            [--pick X,Y] [--projection pinhole|equirect]
-//            [--mesh FILE.obj|FILE.ply --grid x0,y0,z0,x1,y1,z1,N [--mesh-colors]]
+//            [--mesh FILE.obj|FILE.ply --grid x0,y0,z0,x1,y1,z1,N [--mesh-colors]
+//             [--mesh-sharp [R,K]]]
 //            [width height frames out.ppm scene [samples [lights]]]
 //     scene: ref | csg8 | bulb; samples: 1 (default), 2 or 4 sub-samples per
 //     axis, resolved in the render kernel (single-GPU path only: the frame
@@ -50,7 +51,10 @@
 //     With --mesh-colors every vertex carries its baked colour (sdf::bake:
 //     sdf_shade_points at the vertices, lifted by one cell diagonal, under the
 //     frame's lights and, with --palette, its materials; no specular term, which
-//     would depend on the viewer).  --palette stays the switch it is above: it
+//     would depend on the viewer).  With --mesh-sharp the vertices lie on the
+//     scene's edges and corners instead of chamfering them (sdf_mesh_emit_sharp:
+//     R refinement steps per crossing and K steps of the fit, 4,16 when not
+//     given; not for a Mandelbulb).  --palette stays the switch it is above: it
 //     takes no count, the palette has one entry per primitive
 //
 // Multi-GPU: launched once per GPU by any launcher that sets RANK,
@@ -226,6 +230,8 @@ int main(int argc, char** argv) {
   double box[6] = {0, 0, 0, 0, 0, 0};
   int mesh_n = 0;
   bool mesh_colors = false;
+  sdf_mesh_sharp mesh_sharp = {0, 0, 0, 0};   // --mesh-sharp [R,K]
+  bool use_mesh_sharp = false;
   int pick_x = 0, pick_y = 0;
   sdf_reflect reflect = {0, 1.0f, -1, 0};
   sdf_environment environment = sdf::sky(0);
@@ -264,6 +270,18 @@ int main(int argc, char** argv) {
         }
       } else if (std::string(argv[i]) == "--mesh-colors") {
         mesh_colors = true;
+      } else if (std::string(argv[i]) == "--mesh-sharp") {
+        use_mesh_sharp = true;
+        mesh_sharp.refine = 4;
+        mesh_sharp.iterations = 16;
+        // R,K when the next word is two numbers; anything else is the next option
+        int r = 0, k = 0;
+        char tail = 0;
+        if (i + 1 < argc && std::sscanf(argv[i + 1], "%d,%d%c", &r, &k, &tail) == 2) {
+          mesh_sharp.refine = r;
+          mesh_sharp.iterations = k;
+          ++i;
+        }
       } else if (std::string(argv[i]) == "--grid") {
         char tail = 0;
         if (!(i + 1 < argc && std::sscanf(argv[++i], "%lf,%lf,%lf,%lf,%lf,%lf,%d%c", &box[0], &box[1],
@@ -313,8 +331,8 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "sdf_main: --mesh FILE.obj|FILE.ply needs --grid x0,y0,z0,x1,y1,z1,N and vice versa\n");
       return 1;
     }
-    if (mesh_colors && mesh_path.empty()) {
-      std::fprintf(stderr, "sdf_main: --mesh-colors needs --mesh FILE --grid ...\n");
+    if ((mesh_colors || use_mesh_sharp) && mesh_path.empty()) {
+      std::fprintf(stderr, "sdf_main: --mesh-colors and --mesh-sharp need --mesh FILE --grid ...\n");
       return 1;
     }
     if (no_sun) environment.flags &= ~SDF_ENV_SUN;
@@ -436,7 +454,8 @@ int main(int argc, char** argv) {
     if (!mesh_path.empty()) {
       const double lo[3] = {box[0], box[1], box[2]}, hi[3] = {box[3], box[4], box[5]};
       const sdf_grid g = sdf::box_grid(lo, hi, mesh_n);
-      const sdf::Mesh m = sdf::extract_mesh(f, g, true, false, stream);
+      const sdf::Mesh m =
+          sdf::extract_mesh(f, g, true, false, stream, use_mesh_sharp ? &mesh_sharp : nullptr);
       std::vector<float> colors;
       if (mesh_colors) colors = sdf::bake(f, m, g, lights, light_flags, materials, nullptr, -1.0f, stream);
       const bool ply = mesh_path.size() > 4 && mesh_path.compare(mesh_path.size() - 4, 4, ".ply") == 0;

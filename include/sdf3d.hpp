@@ -533,7 +533,9 @@ inline std::array<float, 16 * SDF_MAX_PRIMS> sample_grad(
 // The level set f(p) = grid.iso of the frame's scene inside `grid` as an
 // indexed triangle mesh on the host: sdf_mesh_count, buffers sized from its
 // counts, sdf_mesh_emit, and the copies back.  Blocking.  `normals`: one normal
-// per vertex (sdf_sample's); `prims`: the primitive that owns each vertex.
+// per vertex (sdf_sample's); `prims`: the primitive that owns each vertex;
+// `sharp`: vertices on the scene's edges and corners (sdf_mesh_emit_sharp,
+// "Sharp meshes"; nullptr: the plain surface-nets vertices).
 struct Mesh {
   std::vector<float> verts;     // 3 per vertex
   std::vector<int32_t> tris;    // 3 vertex numbers per triangle
@@ -542,9 +544,10 @@ struct Mesh {
   int64_t counts[4];            // vertices, triangles, bricks evaluated, bricks in all
 };
 inline Mesh extract_mesh(const Frame& f, const sdf_grid& grid, bool normals = false,
-                         bool prims = false, hipStream_t stream = nullptr) {
+                         bool prims = false, hipStream_t stream = nullptr,
+                         const sdf_mesh_sharp* sharp = nullptr) {
   check_abi();
-  check(sdf_validate_mesh(&f.scene, &f.params, &grid), "sdf_validate_mesh");
+  check(sdf_validate_mesh_sharp(&f.scene, &f.params, &grid, sharp), "sdf_validate_mesh_sharp");
   const int64_t bytes = sdf_mesh_workspace_bytes(&grid);
   if (bytes < 0) check(static_cast<int>(bytes), "sdf_mesh_workspace_bytes");
   Mesh m{};
@@ -572,7 +575,7 @@ inline Mesh extract_mesh(const Frame& f, const sdf_grid& grid, bool normals = fa
       out.max_tris = m.counts[1];
       out.normal = normals ? reinterpret_cast<float*>(buf + on) : nullptr;
       out.prim = prims ? reinterpret_cast<int32_t*>(buf + op) : nullptr;
-      rc = sdf_mesh_emit(&f.scene, &f.params, &grid, ws, bytes, &out, stream);
+      rc = sdf_mesh_emit_sharp(&f.scene, &f.params, &grid, sharp, ws, bytes, &out, stream);
       if (rc == SDF_OK) e = hipStreamSynchronize(stream);
       const hipMemcpyKind k = hipMemcpyDeviceToHost;
       if (rc == SDF_OK && e == hipSuccess) {
@@ -590,7 +593,7 @@ inline Mesh extract_mesh(const Frame& f, const sdf_grid& grid, bool normals = fa
   (void)hipFree(buf);
   (void)hipFree(counts);
   (void)hipFree(ws);
-  check(rc, "sdf_mesh_count / sdf_mesh_emit");
+  check(rc, "sdf_mesh_count / sdf_mesh_emit_sharp");
   check_hip(e, "extract_mesh");
   return m;
 }

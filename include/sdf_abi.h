@@ -93,7 +93,10 @@ extern "C" {
                                 still 12: sdf_validate_points and
                                    sdf_shade_points (sdf_points,
                                    sdf_point_shade, SDF_POINTS_*), additions
-                                   likewise */
+                                   likewise;
+                                still 12: sdf_validate_mesh_sharp and
+                                   sdf_mesh_emit_sharp (sdf_mesh_sharp),
+                                   additions likewise */
 
 /* ---- status codes ------------------------------------------------------ */
 #define SDF_OK               0
@@ -281,6 +284,13 @@ typedef struct {
   float*   normal;                      /* device, optional, 3 per vertex */
   int32_t* prim;                        /* device, optional, 1 per vertex */
 } sdf_mesh_out;                         /* 48 bytes */
+/* Sharp-feature vertices (sdf_mesh_emit_sharp; "Sharp meshes" below) */
+typedef struct {
+  int32_t refine;      /* 0 .. 8: regula-falsi steps per crossing edge      */
+  int32_t iterations;  /* 0 .. 64: descent steps of the vertex fit          */
+  int32_t flags;       /* 0                                                 */
+  int32_t reserved;    /* 0                                                 */
+} sdf_mesh_sharp;      /* 16 bytes */
 
 /* Gradients (sdf_sample_grad; "Gradients" below) */
 typedef struct {
@@ -800,9 +810,67 @@ typedef struct {
  *     positive capacity, a negative capacity.  Capacities of 0 write nothing.
  *   - asynchronous on `stream`.  SDF_ABI_VERSION stays 12: detect the entry
  *     points by the symbol.
- *   - marching cubes tables, sharp-feature (QEF) placement, mesh
- *     simplification, adaptive grids and several devices are not offered;
- *     vertex colours are sdf_shade_points at the vertices ("Points"). */
+ *   - marching cubes tables, mesh simplification, adaptive grids and several
+ *     devices are not offered; sharp edges and corners are "Sharp meshes"
+ *     below; vertex colours are sdf_shade_points at the vertices ("Points"). */
+
+/* Sharp meshes (sdf_mesh_emit_sharp: an optional second half of the two-call
+ * protocol of "Meshes", after the same sdf_mesh_count on the same workspace.  A
+ * surface-nets vertex is the mean of its cell's edge crossings, which chamfers
+ * every crease of a hard CSG solid by about a cell; here each crossing is
+ * refined along its edge, takes the scene's analytic gradient ("Gradients") as
+ * its normal, and the vertex is fitted to those tangent planes inside its cell
+ * (dual contouring on the surface-nets topology).  Everything not named below
+ * is "Meshes" word for word: lattice, activity, edges, numbering, triangles,
+ * prim, the guarded stores, skipping, params and dispatch.  Exact precision
+ * rounds every operation once (RN) in the order written and fuses nothing,
+ * divisions are IEEE; fast precision may contract and use the hardware
+ * reciprocal.  tests/mesh_sharp_ref.py states the block in NumPy:
+ *   - identity: sharp NULL, or refine == 0 and iterations == 0, is sdf_mesh_emit
+ *     itself, the same kernel and the same bits.  In every case triangles, prim
+ *     and the vertex numbering are sdf_mesh_emit's, and normal is what
+ *     sdf_sample gives at the vertex written here.
+ *   - refinement, per crossing edge (A, B, a, w_A, w_B of "Meshes"): (ta, wa,
+ *     tb, wb) = (0, w_A, 1, w_B), tau = RN(w_A / RN(w_A - w_B)); then `refine`
+ *     times, always all of them: p = A with p.a = RN(A_a + RN(tau cell[a])); wm =
+ *     RN(f(p) - iso), f bit for bit sdf_sample's value; if (wm < 0) == (wa < 0)
+ *     then (ta, wa) = (tau, wm), else (tb, wb) = (tau, wm); tau = RN(ta +
+ *     RN(RN(tb - ta) RN(wa / RN(wa - wb)))).  One end of the bracket is < 0 and
+ *     the other is not, so wa - wb is never 0; a NaN goes where the comparisons
+ *     and the arithmetic send it.
+ *   - normal of the crossing: n = the gradient of the scene at the final edge
+ *     point p (formed from the final tau as above), in exact precision bit for
+ *     bit what sdf_sample_grad writes to grad_points for p with upstream NULL;
+ *     not normalised.
+ *   - mass point: q (q_a = tau, q_u = s, q_v = t), S, m and g_c = RN(S_c /
+ *     (float)m) as in "Meshes" with the refined tau.
+ *   - fit, over the crossing edges in increasing e, every sum starting at 0:
+ *     r_c = RN(RN(q_c - g_c) cell[c]); b = RN(RN(RN(n_0 r_0) + RN(n_1 r_1)) +
+ *     RN(n_2 r_2)); A_ij += RN(n_i n_j) for the six i <= j; B_i += RN(n_i b).
+ *     tr = RN(RN(A_00 + A_11) + A_22), alpha = RN(1 / tr).  x = 0; `iterations`
+ *     times, from the x of the step before: d_i = RN(B_i - RN(RN(RN(A_i0 x_0) +
+ *     RN(A_i1 x_1)) + RN(A_i2 x_2))) (A symmetric), then x_i = RN(x_i + RN(alpha
+ *     d_i)).  Gradient descent and no SVD: a direction the normals do not
+ *     constrain (along a flat face, along an edge) never leaves the mass
+ *     point.  If tr is not > 0, or tr or a component of x is not finite, x = 0.
+ *   - vertex: l_c = min(max(RN(g_c + RN(x_c / cell[c])), 0), 1) with the GLSL
+ *     selects (max(x, y) = x < y ? y : x, min(x, y) = y < x ? y : x); vertex.c =
+ *     RN(p_c(corner 000) + RN(l_c cell[c])).  No vertex leaves its cell, so the
+ *     mesh keeps the guarantees of surface nets; with x = 0 it is
+ *     sdf_mesh_emit's vertex bit for bit.
+ *   - dispatch: the lattice, the refinement's f and the signs come from the
+ *     variant sdf_mesh_count ran (built-in, run-time specialised -- one more
+ *     kernel per signature, counted by sdf_jit_count --, generic, unculled); the
+ *     gradient is always the generic fold of "Gradients".
+ *   - SDF_E_INVALID_ARG, decided before any device call (sdf_validate_mesh_sharp
+ *     is that check of scene, params, grid and sharp): everything sdf_mesh_emit
+ *     rejects; refine outside 0 .. 8, iterations outside 0 .. 64, nonzero flags
+ *     or reserved.  SDF_E_UNSUPPORTED: a Mandelbulb with a sharp that is neither
+ *     NULL nor (0, 0): it has no analytic gradient.  Capacities of 0 write
+ *     nothing and launch nothing.
+ *   - a full QEF or SVD solve, feature-angle thresholds, vertices outside their
+ *     cell, intersection-free guarantees beyond surface nets' and sharp
+ *     placement for the Mandelbulb are not offered. */
 
 /* Points (sdf_shade_points: the shading pipeline of "Materials" entered at a
  * point of the caller's own instead of behind a primary march -- vertex colours
@@ -1235,6 +1303,13 @@ int sdf_mesh_count(const sdf_scene* scene, const sdf_params* params, const sdf_g
 int sdf_mesh_emit(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
                   void* workspace, int64_t workspace_bytes, const sdf_mesh_out* out,
                   void* stream);
+/* Sharp-feature vertices ("Sharp meshes" above).  Additions likewise.  `sharp`
+ * may be NULL: sdf_mesh_emit. */
+int sdf_validate_mesh_sharp(const sdf_scene* scene, const sdf_params* params,
+                            const sdf_grid* grid, const sdf_mesh_sharp* sharp);
+int sdf_mesh_emit_sharp(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
+                        const sdf_mesh_sharp* sharp, void* workspace, int64_t workspace_bytes,
+                        const sdf_mesh_out* out, void* stream);
 
 /* Gradients ("Gradients" above).  Additions: SDF_ABI_VERSION stays 12, detect
  * them by the symbol.  sdf_validate_grad is the host-only check of scene and

@@ -142,6 +142,13 @@ class sdf_mesh_out(C.Structure):
                 ("max_tris", C.c_int64), ("normal", C.c_void_p), ("prim", C.c_void_p)]
 
 
+class sdf_mesh_sharp(C.Structure):
+    """Sharp-feature vertices of sdf_mesh_emit_sharp: regula-falsi steps per crossing
+    edge (0 .. 8) and descent steps of the vertex fit (0 .. 64); (0, 0) is sdf_mesh_emit."""
+    _fields_ = [("refine", C.c_int32), ("iterations", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class sdf_grad_out(C.Structure):
     """Outputs of sdf_sample_grad: device pointers, any may be NULL (not all);
     grad_prims holds SDF_MAX_PRIMS x 16 floats, the slots of sdf_primitive."""
@@ -177,7 +184,7 @@ STRUCT_SIZES = {
     "sdf_light": 32, "sdf_material": 40, "sdf_params": 80, "sdf_tiling": 24,
     "sdf_driver_config": 36, "sdf_reflect": 16, "sdf_environment": 96, "sdf_hits": 32,
     "sdf_rays": 32, "sdf_grid": 48, "sdf_mesh_out": 48, "sdf_grad_out": 24,
-    "sdf_points": 48, "sdf_point_shade": 40,
+    "sdf_points": 48, "sdf_point_shade": 40, "sdf_mesh_sharp": 16,
 }
 MAX_QUERY = 1 << 30   # rays or points of one sdf_trace / sdf_sample call
 
@@ -250,6 +257,11 @@ SIGNATURES = {
                                  C.c_int64, C.c_void_p, C.c_void_p]),
     "sdf_mesh_emit": (C.c_int, [_P(sdf_scene), _P(sdf_params), _P(sdf_grid), C.c_void_p,
                                 C.c_int64, _P(sdf_mesh_out), C.c_void_p]),
+    "sdf_validate_mesh_sharp": (C.c_int, [_P(sdf_scene), _P(sdf_params), _P(sdf_grid),
+                                          _P(sdf_mesh_sharp)]),
+    "sdf_mesh_emit_sharp": (C.c_int, [_P(sdf_scene), _P(sdf_params), _P(sdf_grid),
+                                      _P(sdf_mesh_sharp), C.c_void_p, C.c_int64, _P(sdf_mesh_out),
+                                      C.c_void_p]),
     "sdf_validate_grad": (C.c_int, [_P(sdf_scene), _P(sdf_params)]),
     "sdf_grad_workspace_bytes": (C.c_int64, [C.c_int64]),
     "sdf_sample_grad": (C.c_int, [_P(sdf_scene), _P(sdf_params), C.c_void_p, C.c_int64,

@@ -1,7 +1,8 @@
 // grad_kernel.inc -- analytic gradients of the scene function (sdf_abi.h
 // "Gradients": sdf_sample_grad).  Included by render_kernel.inc inside namespace
-// SDF_NS, after the meshes, in the primitive translation units only (no
-// Mandelbulb, no run-time specialisation).
+// SDF_NS, before the meshes (whose sharp kernel takes a point's gradient from
+// grad_fold / grad_sweep), in the primitive translation units and the run-time
+// specialised ones (no Mandelbulb); the kernels themselves are built in only.
 //
 // Lane = point.  The forward fold is GenericScene::eval's own loop (prim_sdf,
 // combine, every primitive, unculled), so `dist` is sdf_sample's value; it
@@ -213,6 +214,57 @@ __device__ __forceinline__ float wave_sum8(const float (&t)[8], int lane) {
   return xor_add(x, x, 32, lane);
 }
 
+// One point of the gradient, in two halves that sample_grad and the sharp mesh
+// kernel (mesh_kernel.inc) share.  fv / fd are the lane's own columns, rows
+// STRIDE floats apart.
+//
+// The forward fold at p: GenericScene::eval's loop; with `park` it leaves v_j in
+// fv[j STRIDE] and d_(j-1) in fd[j STRIDE].
+template <int STRIDE>
+__device__ __forceinline__ float grad_fold(KA& A, V3 p, bool park, float* fv, float* fd) {
+  const int count = A.prim_count;
+  float d = INFINITY;
+#pragma unroll 1
+  for (int j = 0; j < count; j++) {
+    const KARG sdf_primitive& pr = A.prims[j];
+    KF q = pr.p;
+    const float v = prim_sdf(pr.kind, p, q);
+    if (park) {
+      fv[j * STRIDE] = v;
+      fd[j * STRIDE] = d;
+    }
+    d = combine(pr.op, d, v, SMIN_K(pr), SMIN_IK(pr), SMIN_SC(pr), SMIN_KSC(pr));
+  }
+  return d;
+}
+// The backward sweep over what grad_fold parked, from the adjoint g of the
+// scene's value: df/dp times g.  terms(j, av, ak, t) sees primitive j's adjoints
+// and prim_partials' parameter terms (the parameter sums of sample_grad).  The
+// skip of a primitive no lane needs is a ballot: every lane of the wave is here.
+template <int STRIDE, class Terms>
+__device__ __forceinline__ V3 grad_sweep(KA& A, V3 p, float g, const float* fv, const float* fd,
+                                         Terms&& terms) {
+  V3 gp = mk(0.0f, 0.0f, 0.0f);
+#pragma unroll 1
+  for (int j = A.prim_count - 1; j >= 0; j--) {
+    const KARG sdf_primitive& pr = A.prims[j];
+    KF q = pr.p;
+    float gd, gv, gk;
+    fold_partials(pr.op, fd[j * STRIDE], fv[j * STRIDE], SMIN_K(pr), SMIN_IK(pr), gd, gv, gk);
+    const float av = g * gv;   // the adjoint of v_j
+    const float ak = g * gk;   // this lane's term of the sum for k
+    g = g * gd;
+    if (__builtin_amdgcn_ballot_w64(av != 0.0f || ak != 0.0f) == 0) continue;
+    V3 vp;
+    float t[7];
+    prim_partials(pr.kind, p, q, vp, t);
+    gp = add(gp, muls(vp, av));
+    terms(j, av, ak, t);
+  }
+  return gp;
+}
+
+#ifndef __HIPCC_RTC__   // the run-time specialiser takes the functions above alone
 template <bool PRIMS>
 __global__ __launch_bounds__(kGradBlock) void sample_grad(GradArgs args) {
   (void)args;
@@ -226,7 +278,6 @@ __global__ __launch_bounds__(kGradBlock) void sample_grad(GradArgs args) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
-  const int count = A.prim_count;
   if constexpr (PRIMS) {
 #pragma unroll
     for (int j = 0; j < kGradSlots / 64; j++) acc[wave * kGradSlots + j * 64 + lane] = 0.0;
@@ -243,49 +294,26 @@ __global__ __launch_bounds__(kGradBlock) void sample_grad(GradArgs args) {
     const long long ii = live ? i : G.n - 1;
     const float* const o = G.points + 3 * ii;
     const V3 p = mk(o[0], o[1], o[2]);
-    float d = INFINITY;
-#pragma unroll 1
-    for (int j = 0; j < count; j++) {
-      const KARG sdf_primitive& pr = A.prims[j];
-      KF q = pr.p;
-      const float v = prim_sdf(pr.kind, p, q);
-      if (backward) {
-        fv[j * kGradBlock + tid] = v;
-        fd[j * kGradBlock + tid] = d;
-      }
-      d = combine(pr.op, d, v, SMIN_K(pr), SMIN_IK(pr), SMIN_SC(pr), SMIN_KSC(pr));
-    }
+    const float d = grad_fold<kGradBlock>(A, p, backward, fv + tid, fd + tid);
     if (G.dist && live) G.dist[i] = d;
     if (!backward) continue;
     float g = 0.0f;
     if (live) g = G.upstream ? G.upstream[i] : 1.0f;
-    V3 gp = mk(0.0f, 0.0f, 0.0f);
-#pragma unroll 1
-    for (int j = count - 1; j >= 0; j--) {
-      const KARG sdf_primitive& pr = A.prims[j];
-      KF q = pr.p;
-      float gd, gv, gk;
-      fold_partials(pr.op, fd[j * kGradBlock + tid], fv[j * kGradBlock + tid], SMIN_K(pr),
-                    SMIN_IK(pr), gd, gv, gk);
-      const float av = g * gv;   // the adjoint of v_j
-      const float ak = g * gk;   // this lane's term of the sum for k
-      g = g * gd;
-      if (__builtin_amdgcn_ballot_w64(av != 0.0f || ak != 0.0f) == 0) continue;
-      V3 vp;
-      float t[7];
-      prim_partials(pr.kind, p, q, vp, t);
-      gp = add(gp, muls(vp, av));
-      if constexpr (PRIMS) {
-        // term 0 is k's (slot 2), term 1 + c is p[c]'s (slot 4 + c); lane l < 8 ends
-        // up with the wave's sum of term l
-        float t8[8];
-        t8[0] = ak;
+    const V3 gp = grad_sweep<kGradBlock>(
+        A, p, g, fv + tid, fd + tid, [&](int j, float av, float ak, const float (&t)[7]) {
+          if constexpr (PRIMS) {
+            // term 0 is k's (slot 2), term 1 + c is p[c]'s (slot 4 + c); lane l < 8 ends
+            // up with the wave's sum of term l
+            float t8[8];
+            t8[0] = ak;
 #pragma unroll
-        for (int c = 0; c < 7; c++) t8[c + 1] = av * t[c];
-        const float mine = wave_sum8(t8, lane);
-        if (lane < 8) acc[wave * kGradSlots + j * 16 + (lane == 0 ? 2 : 3 + lane)] += (double)mine;
-      }
-    }
+            for (int c = 0; c < 7; c++) t8[c + 1] = av * t[c];
+            const float mine = wave_sum8(t8, lane);
+            if (lane < 8) acc[wave * kGradSlots + j * 16 + (lane == 0 ? 2 : 3 + lane)] += (double)mine;
+          } else {
+            (void)j, (void)av, (void)ak, (void)t;
+          }
+        });
     if (G.grad_points && live) {
       float* const w = G.grad_points + 3 * i;
       w[0] = gp.x;
@@ -327,3 +355,4 @@ __global__ __launch_bounds__(4 * kGradSlots) void grad_reduce(const float* rows,
     out[slot] = (float)(((part[slot] + part[kGradSlots + slot]) + part[2 * kGradSlots + slot]) +
                         part[3 * kGradSlots + slot]);
 }
+#endif  // !__HIPCC_RTC__

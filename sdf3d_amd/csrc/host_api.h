@@ -94,7 +94,7 @@ struct RenderUnit {
   int (*frames)(const FramesArgs& a, int variant, void* stream, int nblocks);
   int (*query)(const QueryArgs& q, int variant, void* stream);   // by QueryArgs::kind
   int (*rays)(const RaysArgs& q, int variant, void* stream);     // sdf_render_rays
-  int (*mesh)(const MeshArgs& m, int variant, void* stream, int emit);   // mesh_count / mesh_emit
+  int (*mesh)(const MeshArgs& m, int variant, void* stream, int kind);   // a MeshKind
   int (*points)(const PointsArgs& q, int variant, void* stream);   // sdf_shade_points
   // one kernel each, in the units of the primitive scenes alone (null in the
   // Mandelbulb's): the ray generator of sdf_camera_rays, and the gradient
@@ -117,7 +117,7 @@ inline const RenderUnit& render_unit(bool exact, int variant) {
 int launch_render_jit(const RenderArgs& a, const RenderPlan& plan, void* stream);
 int launch_query_jit(const QueryArgs& q, const RenderPlan& plan, void* stream);
 int launch_rays_jit(const RaysArgs& q, const RenderPlan& plan, void* stream);
-int launch_mesh_jit(const MeshArgs& m, const RenderPlan& plan, void* stream, int emit);
+int launch_mesh_jit(const MeshArgs& m, const RenderPlan& plan, void* stream, int kind);
 int launch_points_jit(const PointsArgs& q, const RenderPlan& plan, void* stream);
 int jit_compiled_count();
 
@@ -279,6 +279,13 @@ inline dim3 query_grid(const QueryArgs& q) {
 // count that fits a grid, and the workspace the kernels write through.
 inline bool mesh_args_fit(const MeshArgs& m) {
   return m.nbricks > 0 && m.nbricks <= 0x7fffffffll && m.ws;
+}
+// the sharp kernel besides: the counts its loops run to, and a primitive list
+// for the gradient's fold (no Mandelbulb)
+inline bool mesh_sharp_args_fit(const MeshArgs& m) {
+  return m.refine >= 0 && m.refine <= 8 && m.iterations >= 0 && m.iterations <= 64 &&
+         m.a.scene_kind == SDF_SCENE_PRIMITIVES && m.a.prim_count > 0 &&
+         m.a.prim_count <= SDF_MAX_PRIMS;
 }
 inline dim3 mesh_grid(const MeshArgs& m) { return dim3((unsigned)m.nbricks); }
 

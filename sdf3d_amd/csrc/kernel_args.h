@@ -248,7 +248,7 @@ struct MeshLayout {
   }
 };
 // The argument block of the mesh kernels (mesh_kernel.inc mesh_count /
-// mesh_emit), their own: RenderArgs is full.  `a` carries the scene and the
+// mesh_emit / mesh_emit_sharp), their own: RenderArgs is full.  `a` carries the scene and the
 // normal's parameters; its camera, light and outputs are unused.
 struct MeshArgs {
   KernelArgs a;   // first: the scene evaluators read it at the start of the segment
@@ -264,7 +264,11 @@ struct MeshArgs {
   float* normal;       // emit, optional: 3 per vertex
   int32_t* prim;       // emit, optional: 1 per vertex
   long long max_verts, max_tris;
+  int32_t refine;      // mesh_emit_sharp: regula-falsi steps per crossing edge, 0 .. 8
+  int32_t iterations;  // mesh_emit_sharp: descent steps of the vertex fit, 0 .. 64
 };
+// the kernel of a mesh launch (RenderUnit::mesh, launch_mesh_jit: `kind`)
+enum MeshKind { kMeshCount = 0, kMeshEmit = 1, kMeshEmitSharp = 2 };
 // ---- gradients (sdf_sample_grad) ------------------------------------------------
 // The argument block of the gradient kernel (grad_kernel.inc sample_grad), its
 // own: `a` carries the prepared scene, nothing else of it is read.  A grid-stride

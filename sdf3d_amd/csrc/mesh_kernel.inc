@@ -1,6 +1,7 @@
 // mesh_kernel.inc -- isosurface extraction (sdf_abi.h "Meshes": sdf_mesh_count,
-// sdf_mesh_emit).  Included by render_kernel.inc inside namespace SDF_NS, after
-// the queries: the lattice value is Scene::eval, the normal trace_shape from a
+// sdf_mesh_emit; "Sharp meshes": sdf_mesh_emit_sharp, further down).  Included by
+// render_kernel.inc inside namespace SDF_NS, after the queries and the
+// gradients: the lattice value is Scene::eval, the normal trace_shape from a
 // fresh culling state and the owner Scene::owner_fold, exactly as sdf_sample
 // and the queries call them; only the extraction is new.
 //
@@ -230,12 +231,227 @@ __device__ __forceinline__ void mesh_quad(const KARG MeshArgs& M, const MeshLayo
   }
 }
 
+#if !SDF_TU_BULB
+// ---- sharp-feature vertices (sdf_abi.h "Sharp meshes": sdf_mesh_emit_sharp) ----
+// mesh_emit with another vertex: the cell's crossings are refined along their
+// edges (regula falsi on Scene::eval, the lattice's own evaluator), each gets the
+// scene's analytic gradient (grad_kernel.inc grad_fold / grad_sweep: the generic
+// fold of sdf_sample_grad), and the vertex is fitted to those tangent planes.
+//
+// A slice has about three active cells of 64, and a lattice edge is shared by
+// four cells, so edges are refined per brick and not per cell.  The brick is
+// taken in two slabs of kSharpSlab = 4 cell slices (5 lattice planes, the
+// middle plane's edges twice, to the same bits):
+//   1. the slab's 1044 lattice edges, 64 at a time, lane = edge: the crossing
+//      ones inside the grid are queued in LDS in slot order (ballot, popcount);
+//   2. the queue, 64 at a time, lane = crossing: `refine` evaluations, one
+//      gradient, (tau, n) to the edge's slot in LDS;
+//   3. the slab's four slices as in mesh_emit, lane = cell, the vertex fitted
+//      from the slots of the cell's crossing edges.
+// Every loop count is a constant, an argument or a popcount of sign ballots, as
+// mesh_emit's are; no address depends on a refined value.
+//
+// LDS per one-wave workgroup: lattice 2,916 B + vertices 6,144 B + slots
+// 16,704 B + queue 2,088 B + the gradient's two columns 8,192 B = 36,044 B, so
+// 4 workgroups per CU of 160 KiB: one wave per SIMD, and the registers of one
+// (a whole brick in one slab would be 50 KB and 3 per CU; slabs of two slices
+// 5 per CU at half the lanes in step 2).
+constexpr int kSharpSlab = 4;
+constexpr int kSharpEdgesXY = (kSharpSlab + 1) * 72;               // along 0 (and along 1) in the slab
+constexpr int kSharpEdges = 2 * kSharpEdgesXY + kSharpSlab * 81;   // 1044
+
+// the slot of the lattice edge from the slab's point (l0, l1, lp) along a
+__device__ __forceinline__ int sharp_slot(int a, int l0, int l1, int lp) {
+  return a == 0   ? (lp * 9 + l1) * 8 + l0
+         : a == 1 ? kSharpEdgesXY + (lp * 8 + l1) * 9 + l0
+                  : 2 * kSharpEdgesXY + (lp * 9 + l1) * 9 + l0;
+}
+struct SharpEdge {
+  int a, l0, l1, lp;
+};
+__device__ __forceinline__ SharpEdge sharp_edge(int slot) {
+  SharpEdge e;
+  e.a = slot < kSharpEdgesXY ? 0 : slot < 2 * kSharpEdgesXY ? 1 : 2;
+  const int s = slot - e.a * kSharpEdgesXY;
+  const int plane = e.a == 2 ? 81 : 72, row = e.a == 0 ? 8 : 9;
+  e.lp = s / plane;
+  const int r = s - plane * e.lp;
+  e.l1 = r / row;
+  e.l0 = r - row * e.l1;
+  return e;
+}
+// the edge's ends in the brick's lattice
+__device__ __forceinline__ int sharp_lattice_a(const SharpEdge& e, int s0) {
+  return ((s0 + e.lp) * 9 + e.l1) * 9 + e.l0;
+}
+__device__ __forceinline__ int sharp_lattice_step(int a) { return a == 0 ? 1 : a == 1 ? 9 : 81; }
+
+// the edge point at tau: RN(A_a + RN(tau cell_a)) along a, A's coordinates beside it
+__device__ __forceinline__ V3 sharp_point(V3 pa, int a, float step) {
+  return mk(a == 0 ? pa.x + step : pa.x, a == 1 ? pa.y + step : pa.y, a == 2 ? pa.z + step : pa.z);
+}
+
+// Steps 1 and 2 for the slab whose first slice is s0: es[slot] = (tau, n) of
+// every crossing edge of the slab that lies inside the grid.
 template <class Scene>
+__device__ __forceinline__ void sharp_edges(const KARG MeshArgs& M, const Scene& scene,
+                                            const MeshBrickAt& b, const float* w, int s0,
+                                            float4* es, unsigned short* queue, float* fv,
+                                            float* fd) {
+  KA& A = M.a;
+  const int lane = threadIdx.x;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  __syncthreads();   // the slab before this one has been fitted
+  int count = 0;
+#pragma unroll 1
+  for (int base = 0; base < kSharpEdges; base += 64) {
+    const int slot = base + lane;
+    bool cross = false;
+    if (slot < kSharpEdges) {
+      const SharpEdge e = sharp_edge(slot);
+      const int ia = sharp_lattice_a(e, s0);
+      const float wa = w[ia], wb = w[ia + sharp_lattice_step(e.a)];
+      // B inside the grid (A then is): beyond it the lattice holds zeros
+      const bool in_grid = b.c0 + e.l0 + (e.a == 0) <= M.n[0] && b.c1 + e.l1 + (e.a == 1) <= M.n[1] &&
+                           b.c2 + s0 + e.lp + (e.a == 2) <= M.n[2];
+      cross = in_grid && ((wa < 0.0f) != (wb < 0.0f));
+    }
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(cross);
+    if (cross) queue[count + __builtin_popcountll(m & below)] = (unsigned short)slot;
+    count += __builtin_popcountll(m);
+  }
+  __syncthreads();
+  // a wave's lanes beyond the queue carry its last edge and store nothing, so
+  // the gradient's ballots see the whole wave
+#pragma unroll 1
+  for (int r0 = 0; r0 < count; r0 += 64) {
+    const bool live = r0 + lane < count;
+    const int slot = queue[live ? r0 + lane : count - 1];
+    const SharpEdge e = sharp_edge(slot);
+    const int ia = sharp_lattice_a(e, s0);
+    float wa = w[ia], wb = w[ia + sharp_lattice_step(e.a)];
+    const V3 pa = mesh_point(M, b.c0 + e.l0, b.c1 + e.l1, b.c2 + s0 + e.lp);
+    const float cell = e.a == 0 ? M.cell[0] : e.a == 1 ? M.cell[1] : M.cell[2];
+    float ta = 0.0f, tb = 1.0f;
+    float tau = fdiv(wa, wa - wb);
+#pragma unroll 1
+    for (int k = 0; k < M.refine; k++) {
+      const float wm = scene.eval(sharp_point(pa, e.a, tau * cell)) - M.iso;
+      const bool same = (wm < 0.0f) == (wa < 0.0f);
+      ta = same ? tau : ta;
+      wa = same ? wm : wa;
+      tb = same ? tb : tau;
+      wb = same ? wb : wm;
+      tau = ta + (tb - ta) * fdiv(wa, wa - wb);
+    }
+    const V3 p = sharp_point(pa, e.a, tau * cell);
+    (void)grad_fold<64>(A, p, true, fv + lane, fd + lane);
+    const V3 n = grad_sweep<64>(A, p, 1.0f, fv + lane, fd + lane,
+                                [](int, float, float, const float (&)[7]) {});
+    if (live) es[slot] = make_float4(tau, n.x, n.y, n.z);
+  }
+  __syncthreads();
+}
+
+// The sharp vertex of an active cell (sdf_abi.h "Sharp meshes"): mesh_vertex's
+// mass point g from the refined tau, then `iterations` descent steps on the
+// tangent planes of the cell's crossing edges, clamped to the cell.  (l0, l1,
+// lp) is the cell in its slab.
+__device__ __forceinline__ V3 mesh_vertex_sharp(const KARG MeshArgs& M, const MeshCell& c, int i0,
+                                                int i1, int i2, const float4* es, int l0, int l1,
+                                                int lp) {
+  float S[3] = {0.0f, 0.0f, 0.0f};
+  float4 E[12];
+  int m = 0;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const int u = (a + 1) % 3, v = (a + 2) % 3;
+#pragma unroll
+    for (int st = 0; st < 4; st++) {
+      const int s = st & 1, t = st >> 1;
+      const int ka = (s << u) | (t << v), kb = ka | (1 << a);
+      const bool cross = (((c.in >> ka) ^ (c.in >> kb)) & 1u) != 0;
+      int l[3] = {l0, l1, lp};
+      l[u] += s;
+      l[v] += t;
+      E[4 * a + st] = es[sharp_slot(a, l[0], l[1], l[2])];
+      S[a] = cross ? S[a] + E[4 * a + st].x : S[a];
+      S[u] = cross ? S[u] + (float)s : S[u];
+      S[v] = cross ? S[v] + (float)t : S[v];
+      m += cross ? 1 : 0;
+    }
+  }
+  const float fm = (float)m;
+  const float g[3] = {fdiv(S[0], fm), fdiv(S[1], fm), fdiv(S[2], fm)};
+  float a00 = 0.0f, a01 = 0.0f, a02 = 0.0f, a11 = 0.0f, a12 = 0.0f, a22 = 0.0f;
+  float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const int u = (a + 1) % 3, v = (a + 2) % 3;
+#pragma unroll
+    for (int st = 0; st < 4; st++) {
+      const int s = st & 1, t = st >> 1;
+      const int ka = (s << u) | (t << v), kb = ka | (1 << a);
+      const bool cross = (((c.in >> ka) ^ (c.in >> kb)) & 1u) != 0;
+      const float4 e = E[4 * a + st];
+      float q[3];
+      q[a] = e.x;
+      q[u] = (float)s;
+      q[v] = (float)t;
+      const float r0 = (q[0] - g[0]) * M.cell[0], r1 = (q[1] - g[1]) * M.cell[1],
+                  r2 = (q[2] - g[2]) * M.cell[2];
+      const float be = (e.y * r0 + e.z * r1) + e.w * r2;
+      a00 = cross ? a00 + e.y * e.y : a00;
+      a01 = cross ? a01 + e.y * e.z : a01;
+      a02 = cross ? a02 + e.y * e.w : a02;
+      a11 = cross ? a11 + e.z * e.z : a11;
+      a12 = cross ? a12 + e.z * e.w : a12;
+      a22 = cross ? a22 + e.w * e.w : a22;
+      b0 = cross ? b0 + e.y * be : b0;
+      b1 = cross ? b1 + e.z * be : b1;
+      b2 = cross ? b2 + e.w * be : b2;
+    }
+  }
+  const float tr = (a00 + a11) + a22;
+  const float alpha = fdiv(1.0f, tr);
+  float x0 = 0.0f, x1 = 0.0f, x2 = 0.0f;
+#pragma unroll 1
+  for (int k = 0; k < M.iterations; k++) {
+    const float d0 = b0 - ((a00 * x0 + a01 * x1) + a02 * x2);
+    const float d1 = b1 - ((a01 * x0 + a11 * x1) + a12 * x2);
+    const float d2 = b2 - ((a02 * x0 + a12 * x1) + a22 * x2);
+    x0 = x0 + alpha * d0;
+    x1 = x1 + alpha * d1;
+    x2 = x2 + alpha * d2;
+  }
+  const bool ok = tr > 0.0f && tr < INFINITY && fabsf(x0) < INFINITY && fabsf(x1) < INFINITY &&
+                  fabsf(x2) < INFINITY;
+  x0 = ok ? x0 : 0.0f;
+  x1 = ok ? x1 : 0.0f;
+  x2 = ok ? x2 : 0.0f;
+  const float f0 = gclamp(g[0] + fdiv(x0, M.cell[0]), 0.0f, 1.0f);
+  const float f1 = gclamp(g[1] + fdiv(x1, M.cell[1]), 0.0f, 1.0f);
+  const float f2 = gclamp(g[2] + fdiv(x2, M.cell[2]), 0.0f, 1.0f);
+  const V3 p = mesh_point(M, i0, i1, i2);
+  return mk(p.x + f0 * M.cell[0], p.y + f1 * M.cell[1], p.z + f2 * M.cell[2]);
+}
+#endif  // !SDF_TU_BULB
+
+template <class Scene, bool SHARP>
 __device__ __forceinline__ void mesh_emit_body() {
   const KARG MeshArgs& M = *(const KARG MeshArgs*)__builtin_amdgcn_kernarg_segment_ptr();
   KA& A = M.a;
   __shared__ float w[kMeshLattice];
   __shared__ float vp[3 * 512];   // the brick's vertices in their order, for the second pass
+#if !SDF_TU_BULB
+  // the sharp kernel's own (see above); unused, and gone, in mesh_emit
+  __shared__ float4 es[SHARP ? kSharpEdges : 1];
+  __shared__ unsigned short queue[SHARP ? kSharpEdges : 1];
+  __shared__ float fv[SHARP ? SDF_MAX_PRIMS * 64 : 1];
+  __shared__ float fd[SHARP ? SDF_MAX_PRIMS * 64 : 1];
+#else
+  static_assert(!SHARP, "a Mandelbulb has no analytic gradient");
+#endif
   const int lane = threadIdx.x;
   const MeshBrickAt b = mesh_brick_at(M);
   const MeshLayout L(M.nbricks);
@@ -255,8 +471,19 @@ __device__ __forceinline__ void mesh_emit_body() {
     const bool active = ((m >> lane) & 1ull) != 0;
     const MeshCell c = mesh_cell(w, l0, l1, l2);
     const long long self = vbase + __builtin_popcountll(m & below);
+#if !SDF_TU_BULB
+    if constexpr (SHARP) {
+      if ((l2 & (kSharpSlab - 1)) == 0) sharp_edges(M, scene, b, w, l2, es, queue, fv, fd);
+    }
+#endif
     if (active) {
-      const V3 P = mesh_vertex(M, c, i[0], i[1], i[2]);
+      V3 P;
+#if !SDF_TU_BULB
+      if constexpr (SHARP)
+        P = mesh_vertex_sharp(M, c, i[0], i[1], i[2], es, l0, l1, l2 & (kSharpSlab - 1));
+      else
+#endif
+        P = mesh_vertex(M, c, i[0], i[1], i[2]);
       float* const l = vp + 3 * (int)(self - off.v);   // at most 511: a sum of mask popcounts
       l[0] = P.x;
       l[1] = P.y;
@@ -318,16 +545,22 @@ __device__ __forceinline__ void mesh_emit_body() {
 
 // The mesh kernels' occupancy: mesh_count is an evaluation and a few ballots, at
 // the render kernel's waves per SIMD; mesh_emit's 9 KB of LDS per one-wave
-// workgroup (the lattice and the brick's vertices) admit 5.
+// workgroup (the lattice and the brick's vertices) admit 5; mesh_emit_sharp's
+// 36 KB one (see there).
 #ifndef SDF_MESH_WAVES_PER_EU
 #define SDF_MESH_WAVES_PER_EU SDF_WAVES_PER_EU
 #endif
 #ifndef SDF_MESH_EMIT_WAVES_PER_EU
 #define SDF_MESH_EMIT_WAVES_PER_EU 5
 #endif
-template <class Scene, int EMIT>
+#ifndef SDF_MESH_SHARP_WAVES_PER_EU
+#define SDF_MESH_SHARP_WAVES_PER_EU 1
+#endif
+// KIND: 0 mesh_count, 1 mesh_emit, 2 mesh_emit_sharp
+template <class Scene, int KIND>
 __device__ __forceinline__ void mesh_body() {
-  if constexpr (EMIT) mesh_emit_body<Scene>();
+  if constexpr (KIND == 2) mesh_emit_body<Scene, true>();
+  else if constexpr (KIND == 1) mesh_emit_body<Scene, false>();
   else mesh_count_body<Scene>();
 }
 template <class Scene>
@@ -340,5 +573,13 @@ template <class Scene>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SDF_MESH_EMIT_WAVES_PER_EU, SDF_MESH_EMIT_WAVES_PER_EU)))
 void mesh_emit(MeshArgs args) {
   (void)args;
-  mesh_emit_body<Scene>();
+  mesh_emit_body<Scene, false>();
 }
+#if !SDF_TU_BULB
+template <class Scene>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SDF_MESH_SHARP_WAVES_PER_EU, SDF_MESH_SHARP_WAVES_PER_EU)))
+void mesh_emit_sharp(MeshArgs args) {
+  (void)args;
+  mesh_emit_body<Scene, true>();
+}
+#endif

@@ -2918,13 +2918,14 @@ void query(QueryArgs args) {
   query_body<Scene, KIND>();
 }
 
-// ---- isosurface meshes (sdf_abi.h "Meshes": sdf_mesh_count, sdf_mesh_emit) -----
-#include "mesh_kernel.inc"
-
 // ---- gradients (sdf_abi.h "Gradients": sdf_sample_grad) -------------------------
-#if !SDF_TU_BULB && !defined(__HIPCC_RTC__)
+#if !SDF_TU_BULB
 #include "grad_kernel.inc"
 #endif
+
+// ---- isosurface meshes (sdf_abi.h "Meshes": sdf_mesh_count, sdf_mesh_emit;
+// "Sharp meshes": sdf_mesh_emit_sharp, over the gradient's functions) -------------
+#include "mesh_kernel.inc"
 
 // ---- caller-supplied rays (sdf_abi.h "Rays": sdf_render_rays, sdf_camera_rays) --
 // The path of shade_pixel_reflect (ENV: shade_pixel_env) whose layer 0 is read

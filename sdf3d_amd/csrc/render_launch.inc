@@ -149,21 +149,34 @@ static int launch_query(const QueryArgs& q, int variant, void* stream) {
 }
 
 // one launch of scene kernel S for a mesh extraction: one wave per brick,
-// mesh_count or mesh_emit, under the family's contract (host_api.h
-// mesh_args_fit)
+// mesh_count, mesh_emit or mesh_emit_sharp (a MeshKind), under the family's
+// contract (host_api.h mesh_args_fit, mesh_sharp_args_fit).  The Mandelbulb's
+// unit has no sharp kernel: its scene has no analytic gradient.
 template <class S>
-static int launch_mesh_scene(const MeshArgs& m, int emit, hipStream_t s) {
+static int launch_mesh_scene(const MeshArgs& m, int kind, hipStream_t s) {
   if (!mesh_args_fit(m)) return (int)hipErrorInvalidValue;
   const dim3 block(64), grid = mesh_grid(m);
   (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
-  if (emit) hipLaunchKernelGGL((SDF_NS::mesh_emit<S>), grid, block, 0, s, m);
-  else hipLaunchKernelGGL((SDF_NS::mesh_count<S>), grid, block, 0, s, m);
+  if (kind == kMeshEmitSharp) {
+#if SDF_TU_BULB
+    return (int)hipErrorInvalidValue;
+#else
+    if (!mesh_sharp_args_fit(m)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((SDF_NS::mesh_emit_sharp<S>), grid, block, 0, s, m);
+#endif
+  } else if (kind == kMeshEmit) {
+    hipLaunchKernelGGL((SDF_NS::mesh_emit<S>), grid, block, 0, s, m);
+  } else if (kind == kMeshCount) {
+    hipLaunchKernelGGL((SDF_NS::mesh_count<S>), grid, block, 0, s, m);
+  } else {
+    return (int)hipErrorInvalidValue;
+  }
   return (int)hipGetLastError();
 }
 
-static int launch_mesh(const MeshArgs& m, int variant, void* stream, int emit) {
+static int launch_mesh(const MeshArgs& m, int variant, void* stream, int kind) {
   return with_scene(variant, [&](auto scene) {
-    return launch_mesh_scene<typename decltype(scene)::type>(m, emit, (hipStream_t)stream);
+    return launch_mesh_scene<typename decltype(scene)::type>(m, kind, (hipStream_t)stream);
   });
 }
 

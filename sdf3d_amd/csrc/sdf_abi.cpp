@@ -1346,6 +1346,7 @@ int sdf_sample(const sdf_scene* scene, const sdf_params* params, const float* po
 // ---- isosurface meshes (sdf_abi.h "Meshes") -----------------------------------
 static_assert(sizeof(sdf_grid) == 48, "sdf_grid layout");
 static_assert(sizeof(sdf_mesh_out) == 48, "sdf_mesh_out layout");
+static_assert(sizeof(sdf_mesh_sharp) == 16, "sdf_mesh_sharp layout");
 namespace {
 constexpr int64_t kMaxLattice = int64_t(1) << 30;
 
@@ -1407,9 +1408,10 @@ float mesh_skip_bound(const sdf_scene& s, const sdf_grid& g) {
 // One validated mesh call: the scene's plan with the grid and the mesh
 // buffers; the count is followed by the scan that turns the bricks' counts
 // into offsets and totals.
-int mesh_launch(bool emit, const sdf_scene* scene, const sdf_params* params, const sdf_grid* g,
+int mesh_launch(int kind, const sdf_scene* scene, const sdf_params* params, const sdf_grid* g,
                 int64_t nbricks, void* workspace, int64_t* counts, const sdf_mesh_out* out,
-                void* stream) {
+                const sdf_mesh_sharp* sharp, void* stream) {
+  const bool emit = kind != sdf::kMeshCount;
   std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
   const int rc = scene_plan(scene, nullptr, query_params(*params, false), plan.get());
   if (rc != SDF_OK) return rc;
@@ -1433,8 +1435,12 @@ int mesh_launch(bool emit, const sdf_scene* scene, const sdf_params* params, con
     m->max_verts = out->max_verts;
     m->max_tris = out->max_tris;
   }
+  if (kind == sdf::kMeshEmitSharp) {
+    m->refine = sharp->refine;
+    m->iterations = sharp->iterations;
+  }
   const int lrc = sdf::launch_planned(*plan, sdf::launch_mesh_jit, &sdf::RenderUnit::mesh, *m,
-                                      stream, emit ? 1 : 0);
+                                      stream, kind);
   if (lrc != SDF_OK || emit) return lrc;
   const int err = sdf::launch_mesh_scan(m->ws, nbricks, (long long*)counts, stream);
   return err == hipSuccess ? SDF_OK : SDF_E_HIP;
@@ -1464,21 +1470,45 @@ int sdf_mesh_count(const sdf_scene* scene, const sdf_params* params, const sdf_g
   const int rc = validate_mesh(scene, params, grid, &nbricks);
   if (rc != SDF_OK) return rc;
   if (!counts || !mesh_workspace_fits(workspace, workspace_bytes, nbricks)) return SDF_E_INVALID_ARG;
-  return mesh_launch(false, scene, params, grid, nbricks, workspace, counts, nullptr, stream);
+  return mesh_launch(sdf::kMeshCount, scene, params, grid, nbricks, workspace, counts, nullptr,
+                     nullptr, stream);
 }
 
-int sdf_mesh_emit(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
-                  void* workspace, int64_t workspace_bytes, const sdf_mesh_out* out,
-                  void* stream) {
+int sdf_validate_mesh_sharp(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
+                            const sdf_mesh_sharp* sharp) {
+  const int rc = validate_mesh(scene, params, grid, nullptr);
+  if (rc != SDF_OK || !sharp) return rc;
+  if (sharp->refine < 0 || sharp->refine > 8 || sharp->iterations < 0 || sharp->iterations > 64 ||
+      sharp->flags != 0 || sharp->reserved != 0)
+    return SDF_E_INVALID_ARG;
+  // the placement needs the scene's analytic gradient (sdf_validate_grad)
+  const bool plain = sharp->refine == 0 && sharp->iterations == 0;
+  return plain || scene->kind == SDF_SCENE_PRIMITIVES ? SDF_OK : SDF_E_UNSUPPORTED;
+}
+
+int sdf_mesh_emit_sharp(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
+                        const sdf_mesh_sharp* sharp, void* workspace, int64_t workspace_bytes,
+                        const sdf_mesh_out* out, void* stream) {
   int64_t nbricks = 0;
-  const int rc = validate_mesh(scene, params, grid, &nbricks);
+  int rc = validate_mesh(scene, params, grid, &nbricks);
   if (rc != SDF_OK) return rc;
   if (!out || !mesh_workspace_fits(workspace, workspace_bytes, nbricks)) return SDF_E_INVALID_ARG;
   if (out->max_verts < 0 || out->max_tris < 0) return SDF_E_INVALID_ARG;
   if ((out->max_verts > 0 && !out->verts) || (out->max_tris > 0 && !out->tris))
     return SDF_E_INVALID_ARG;
+  rc = sdf_validate_mesh_sharp(scene, params, grid, sharp);
+  if (rc != SDF_OK) return rc;
   if (out->max_verts == 0 && out->max_tris == 0) return SDF_OK;   // nothing may be written
-  return mesh_launch(true, scene, params, grid, nbricks, workspace, nullptr, out, stream);
+  // NULL and (0, 0) are sdf_mesh_emit itself: its kernel
+  const bool plain = !sharp || (sharp->refine == 0 && sharp->iterations == 0);
+  return mesh_launch(plain ? sdf::kMeshEmit : sdf::kMeshEmitSharp, scene, params, grid, nbricks,
+                     workspace, nullptr, out, sharp, stream);
+}
+
+int sdf_mesh_emit(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
+                  void* workspace, int64_t workspace_bytes, const sdf_mesh_out* out,
+                  void* stream) {
+  return sdf_mesh_emit_sharp(scene, params, grid, nullptr, workspace, workspace_bytes, out, stream);
 }
 
 // ---- gradients (sdf_abi.h "Gradients") -----------------------------------------

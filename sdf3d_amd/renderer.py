@@ -148,6 +148,15 @@ def grid(origin, cell, n, iso: float = 0.0, dense: bool = False) -> abi.sdf_grid
     return g
 
 
+def mesh_sharp(sharp):
+    """The sdf_mesh_sharp of ``Renderer.mesh``'s `sharp`: None or False none (a
+    NULL pointer), True (4, 16), or ``(refine, iterations)``."""
+    if sharp is None or sharp is False:
+        return None
+    refine, iterations = (4, 16) if sharp is True else sharp
+    return abi.sdf_mesh_sharp(int(refine), int(iterations), 0, 0)
+
+
 class Renderer:
     """Renders frames on one HIP device through ``sdf_render``."""
 
@@ -489,21 +498,26 @@ class Renderer:
 
     # ---- isosurface meshes (sdf_abi.h "Meshes") -----------------------------
     def mesh(self, frame: Frame, origin, cell, n, iso: float = 0.0, normal: bool = False,
-             prim: bool = False, dense: bool = False, stream=None) -> "Mesh":
+             prim: bool = False, dense: bool = False, stream=None, sharp=None) -> "Mesh":
         """The level set ``f(p) = iso`` of ``frame.scene`` inside the grid of
         `n` cells of size `cell` from `origin`, as an indexed triangle mesh
         (sdf_mesh_count, then sdf_mesh_emit into buffers sized from its counts;
         the host waits for the counts in between).  Returns ``Mesh(verts (nv, 3)
         float32, tris (nt, 3) int32, normal (nv, 3) or None, prim (nv,) int32 or
         None, counts)``.  `dense` evaluates every brick (SDF_MESH_DENSE); the
-        mesh is the same either way."""
+        mesh is the same either way.  `sharp` places the vertices on the
+        scene's edges and corners instead of chamfering them
+        (sdf_mesh_emit_sharp, "Sharp meshes"): True for 4 refinement steps per
+        crossing and 16 steps of the fit, or ``(refine, iterations)``; the
+        triangles are the same.  Not for a Mandelbulb."""
         torch = self.torch
         g = grid(origin, cell, n, iso, dense)
+        sp = mesh_sharp(sharp)
         nbytes = int(self.lib.sdf_mesh_workspace_bytes(C.byref(g)))
         if nbytes < 0:
             abi.check(nbytes, "sdf_mesh_workspace_bytes")
-        abi.check(self.lib.sdf_validate_mesh(C.byref(frame.scene), C.byref(frame.params),
-                                             C.byref(g)), "sdf_validate_mesh")
+        abi.check(self.lib.sdf_validate_mesh_sharp(C.byref(frame.scene), C.byref(frame.params),
+                                                   C.byref(g), sp), "sdf_validate_mesh_sharp")
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
         counts = torch.empty((4,), dtype=torch.int64, device=self.device)
         with self._on_device():
@@ -523,10 +537,10 @@ class Renderer:
             def ptr(x):
                 return C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None
             out = abi.sdf_mesh_out(ptr(verts), nv, ptr(tris), nt, ptr(nrm), ptr(own))
-            rc = self.lib.sdf_mesh_emit(C.byref(frame.scene), C.byref(frame.params), C.byref(g),
-                                        C.c_void_p(ws.data_ptr()), nbytes, C.byref(out),
-                                        self._stream(stream))
-            abi.check(rc, "sdf_mesh_emit")
+            rc = self.lib.sdf_mesh_emit_sharp(C.byref(frame.scene), C.byref(frame.params),
+                                              C.byref(g), sp, C.c_void_p(ws.data_ptr()), nbytes,
+                                              C.byref(out), self._stream(stream))
+            abi.check(rc, "sdf_mesh_emit_sharp")
             if stream is not None:
                 stream.synchronize()   # the workspace is released on return
         return Mesh(verts, tris, nrm, own, (nv, nt, evaluated, bricks))
@@ -654,7 +668,10 @@ class Renderer:
         with the mesh's normals when it has them.  The default `lift` is the
         length of the cell diagonal: a surface-nets vertex lies within half a
         diagonal of the surface, so one diagonal puts it outside for a field
-        whose Lipschitz constant is 1.  Returns a float32 (V, 4) tensor."""
+        whose Lipschitz constant is 1.  A mesh extracted with `sharp` has its
+        vertices on the surface and needs less, but a ``Mesh`` does not say how
+        it was made, so the default is the same: pass a smaller `lift` for one.
+        Returns a float32 (V, 4) tensor."""
         cell = (cell,) * 3 if isinstance(cell, (int, float)) else tuple(cell)
         if lift is None:
             lift = math.sqrt(sum(float(c) * float(c) for c in cell))
