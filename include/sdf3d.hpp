@@ -150,6 +150,12 @@ struct Frame {
     params.samples = samples;
     return *this;
   }
+  // The material table of a shading call: `v`, or where it is empty the
+  // frame's material on every primitive (once for a Mandelbulb).
+  std::vector<sdf_material> table(const std::vector<sdf_material>& v) const {
+    const size_t n = scene.kind == SDF_SCENE_PRIMITIVES ? static_cast<size_t>(scene.count) : 1;
+    return v.empty() ? std::vector<sdf_material>(n, material) : v;
+  }
 };
 
 // Arcball navigation producing V_mat: the reference
@@ -351,9 +357,7 @@ class Renderer {
               sdf_schedule* schedule = nullptr) {
     if (f.params.width != w_ || f.params.height != h_)
       throw Error(SDF_E_INVALID_ARG, "Renderer: frame size differs from framebuffer");
-    const std::vector<sdf_material> same(
-        f.scene.kind == SDF_SCENE_PRIMITIVES ? static_cast<size_t>(f.scene.count) : 1, f.material);
-    const std::vector<sdf_material>& m = materials.empty() ? same : materials;
+    const std::vector<sdf_material> m = f.table(materials);
     check(sdf_render_reflect(&f.scene, &f.camera, lights.data(),
                              static_cast<int32_t>(lights.size()), light_flags, m.data(),
                              static_cast<int32_t>(m.size()), &reflect, &f.params, tiling, rgba_,
@@ -369,9 +373,7 @@ class Renderer {
               int32_t* steps = nullptr, sdf_schedule* schedule = nullptr) {
     if (f.params.width != w_ || f.params.height != h_)
       throw Error(SDF_E_INVALID_ARG, "Renderer: frame size differs from framebuffer");
-    const std::vector<sdf_material> same(
-        f.scene.kind == SDF_SCENE_PRIMITIVES ? static_cast<size_t>(f.scene.count) : 1, f.material);
-    const std::vector<sdf_material>& m = materials.empty() ? same : materials;
+    const std::vector<sdf_material> m = f.table(materials);
     check(sdf_render_env(&f.scene, &f.camera, lights.data(), static_cast<int32_t>(lights.size()),
                          light_flags, m.data(), static_cast<int32_t>(m.size()), &reflect, &env,
                          &f.params, tiling, rgba_, steps, schedule, stream_),
@@ -480,9 +482,7 @@ inline void render_rays(const Frame& f, const std::vector<sdf_light>& lights, in
                         const sdf_environment* env, const float* origins, const float* dirs,
                         int64_t n, bool unit, void* rgba, int32_t* steps = nullptr,
                         hipStream_t stream = nullptr) {
-  const std::vector<sdf_material> same(
-      f.scene.kind == SDF_SCENE_PRIMITIVES ? static_cast<size_t>(f.scene.count) : 1, f.material);
-  const std::vector<sdf_material>& m = materials.empty() ? same : materials;
+  const std::vector<sdf_material> m = f.table(materials);
   const sdf_rays rays = {origins, dirs, n, unit ? SDF_RAYS_UNIT : 0, 0};
   check(sdf_render_rays(&f.scene, lights.data(), static_cast<int32_t>(lights.size()), light_flags,
                         m.data(), static_cast<int32_t>(m.size()), reflect, env, &f.params, &rays,
@@ -651,9 +651,7 @@ inline void shade_points(const Frame& f, const std::vector<sdf_light>& lights, i
                          const std::vector<sdf_material>& materials, const float* points,
                          const float* normals, int64_t n, const float* eye, float lift,
                          const sdf_point_shade& out, hipStream_t stream = nullptr) {
-  const std::vector<sdf_material> same(
-      f.scene.kind == SDF_SCENE_PRIMITIVES ? static_cast<size_t>(f.scene.count) : 1, f.material);
-  const std::vector<sdf_material>& m = materials.empty() ? same : materials;
+  const std::vector<sdf_material> m = f.table(materials);
   const std::vector<sdf_light> one(1, f.light);
   const std::vector<sdf_light>& l = lights.empty() ? one : lights;
   sdf_points p{};

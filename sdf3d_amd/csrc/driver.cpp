@@ -731,7 +731,8 @@ int sdf_driver_create(const sdf_scene* scene, const sdf_camera* camera, const sd
 
 int sdf_driver_set_camera(sdf_driver* d, const sdf_camera* camera) {
   if (!d) return SDF_E_INVALID_ARG;
-  const int rc = sdf_validate(&d->scene, camera, &d->light, &d->material, &d->params, nullptr);
+  // the driver's scene, light, material and params were validated when it was made
+  const int rc = sdf::validate_camera(camera);
   if (rc != SDF_OK) return rc;
   d->camera = *camera;
   for (auto* v : {&d->plan_send, &d->plan_frame})

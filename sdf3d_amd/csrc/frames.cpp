@@ -102,11 +102,10 @@ extern "C" int sdf_render_frames(const sdf_scene* scene, const sdf_camera* camer
   if (params->output_format == SDF_FORMAT_TILES) return SDF_E_UNSUPPORTED;
   // supersampling is sdf_render's alone: the persistent kernel has no resolve
   if (params->samples > 1) return SDF_E_UNSUPPORTED;
-  for (int i = 0; i < n; ++i) {
-    const int rc = sdf_validate(scene, &cameras[i], light, material, params, nullptr);
-    if (rc != SDF_OK) return rc;
-    if (!rgba[i]) return SDF_E_INVALID_ARG;
-  }
+  // the camera's part of every frame but the first, whose plan checks the
+  // whole request through camera 0
+  for (int i = 0; i < n; ++i)
+    if ((i && sdf::validate_camera(&cameras[i]) != SDF_OK) || !rgba[i]) return SDF_E_INVALID_ARG;
   sdf::RenderPlan plan;
   int rc = sdf::make_render_plan(scene, &cameras[0], light, material, params, nullptr, rgba[0],
                                  steps ? steps[0] : nullptr, &plan);

@@ -62,6 +62,30 @@ int tiling_run(const sdf_tiling& t);
 int tiling_step(const sdf_tiling& t);
 int tiling_gap_rows(const sdf_tiling& t);  // (step - 1) * block_rows
 
+// What every shading call is made of.  A call without a part leaves it null
+// (`camera`: rays and points; `reflect`, `env`: none asked) or at one entry
+// (`lights`, `materials`: the one light and material of sdf_render).
+struct Request {
+  const sdf_scene* scene;
+  const sdf_camera* camera;
+  const sdf_light* lights;
+  int32_t nlights, light_flags;
+  const sdf_material* materials;
+  int32_t nmaterials;
+  const sdf_reflect* reflect;
+  const sdf_environment* env;
+  const sdf_params* params;
+  const sdf_tiling* tiling;
+};
+// How much of a request an entry point takes, and the kernel family that
+// serves one (route): each includes the ones before it.
+enum Depth { kPlain, kLights, kMaterials, kReflect, kEnv };
+// The one validator: every part's rules up to `depth`, once, in the order of
+// sdf_abi.h.  `framed`: the call renders a frame through r.camera.
+int validate_request(const Request& r, Depth depth, bool framed = true);
+// The camera's part alone, for a caller that holds a validated request.
+int validate_camera(const sdf_camera* camera);
+
 // Validate and prepare (tiling NULL = the whole frame).  SDF_OK or an SDF_E_*.
 int make_render_plan(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* light,
                      const sdf_material* material, const sdf_params* params,

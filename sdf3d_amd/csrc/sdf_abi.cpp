@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 #include <algorithm>
 #include <cstring>
 #include <initializer_list>
@@ -114,7 +115,6 @@ bool finite3(const float* v) {
   return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
 }
 
-int run_of(const sdf_tiling& t) { return sdf::tiling_run(t); }
 using sdf::count_rows;
 
 const sdf_tiling kWholeFrame = {8, 0, 1, 0, 1, 1};
@@ -382,7 +382,245 @@ int select_variant(const sdf_scene& scene) {
 
 }  // namespace sdf
 
+// ---- a request's rules (sdf_abi.h), part by part ------------------------------
+namespace {
+
+// Working range of the kernels: every coordinate, size and distance at most
+// 1e15 in magnitude (and capsules of positive length), so that no square,
+// dot product or distance the scene evaluation forms overflows -- every
+// primitive value is then finite and the accumulated scene distance is never
+// NaN, which the exact kernel's hardware minimum relies on (render_kernel.inc
+// smin<HW>; ADVICE r04).
+constexpr float kMaxCoord = 1e15f;
+constexpr float kMinCapsule2 = 0x1p-30f;
+constexpr float kMaxCapsule2 = 0x1p30f;
+
+// params and tiling
+int validate_params(const sdf_params& p, const sdf_tiling* tiling) {
+  if (p.width <= 0 || p.height <= 0 || p.width > 65536 || p.height > 65536)
+    return SDF_E_INVALID_ARG;
+  // sub-samples per axis: 0 and 1 are one sample per pixel.  The sub-sample
+  // frame S W x S H is what the kernels index (cr_math.h div_refined: a quad
+  // numerator below 2^17 over at most 2^16), and its tiling's block_rows are
+  // S times the request's
+  if (p.samples != 0 && p.samples != 1 && p.samples != 2 && p.samples != 4)
+    return SDF_E_INVALID_ARG;
+  if (p.samples > 1) {
+    if (p.samples * (long long)p.width > 65536 || p.samples * (long long)p.height > 65536)
+      return SDF_E_INVALID_ARG;
+    if (tiling && tiling->block_rows > INT32_MAX / p.samples) return SDF_E_INVALID_ARG;
+  }
+  if (p.max_steps < 0 || p.max_steps > (1 << 24)) return SDF_E_INVALID_ARG;
+  // every length the marches add to a coordinate stays in the working range
+  // (kMaxCoord): normal_eps^2 and the AO tap lengths must not overflow,
+  // which the exact kernels' one-compare cr_sqrt guard relies on (ADVICE r05)
+  for (float v : {p.max_dist, p.eps, p.shadow_k, p.normal_eps, p.shadow_offset})
+    if (!(std::fabs(v) <= kMaxCoord)) return SDF_E_INVALID_ARG;
+  if (p.flags & SDF_FLAG_AO)
+    for (float v : {p.ao_step, p.ao_base, p.ao_falloff, p.ao_strength})
+      if (!(std::fabs(v) <= kMaxCoord)) return SDF_E_INVALID_ARG;
+  if (p.flags & ~(SDF_FLAG_SHADOW | SDF_FLAG_AO)) return SDF_E_INVALID_ARG;
+  if (p.normal_mode != SDF_NORMAL_CENTRAL && p.normal_mode != SDF_NORMAL_TETRA)
+    return SDF_E_INVALID_ARG;
+  if (p.precision != SDF_PRECISION_EXACT && p.precision != SDF_PRECISION_FAST)
+    return SDF_E_INVALID_ARG;
+  if (p.dispatch < SDF_DISPATCH_AUTO || p.dispatch > SDF_DISPATCH_UNCULLED)
+    return SDF_E_INVALID_ARG;
+  if (p.output_format != SDF_FORMAT_TILES && sdf_format_bytes(p.output_format) < 0)
+    return SDF_E_INVALID_ARG;
+  if ((p.flags & SDF_FLAG_AO) && (p.ao_taps < 0 || p.ao_taps > sdf::kMaxAoTaps))
+    return SDF_E_INVALID_ARG;
+  if (count_rows(p.height, tiling ? *tiling : kWholeFrame) < 0) return SDF_E_INVALID_ARG;
+  if (tiling && (tiling->flags & SDF_TILING_FRAME_ROWS) && p.output_format == SDF_FORMAT_TILES)
+    return SDF_E_INVALID_ARG;   // a stream is made of packed tiles
+  return SDF_OK;
+}
+
+int validate_scene(const sdf_scene& scene) {
+  if (scene.kind == SDF_SCENE_PRIMITIVES) {
+    if (scene.count < 0 || scene.count > SDF_MAX_PRIMS) return SDF_E_INVALID_ARG;
+    for (int i = 0; i < scene.count; ++i) {
+      const sdf_primitive& pr = scene.prims[i];
+      if (pr.kind < 0 || pr.kind >= SDF_PRIM_KIND_COUNT) return SDF_E_INVALID_ARG;
+      if (pr.op < 0 || pr.op >= SDF_OP_COUNT) return SDF_E_INVALID_ARG;
+      // a smooth blend radius in [2^-64, 1e15]: the exact smooth-min's
+      // h h (k/4) relies on the lower end (render_kernel.inc smin)
+      if (smooth_op(pr.op) && !(pr.k >= 0x1p-64f && pr.k <= kMaxCoord)) return SDF_E_INVALID_ARG;
+      for (float v : pr.p)
+        if (!std::isfinite(v) || std::fabs(v) > kMaxCoord) return SDF_E_INVALID_ARG;
+      if (pr.kind == SDF_PRIM_CAPSULE) {
+        // a segment of length in [2^-15, 2^15): dot(ba, ba), computed as the
+        // kernels do, in [2^-30, 2^30) -- the exact kernel's Markstein
+        // division of h = dot(pa, ba) / dot(ba, ba) (render_kernel.inc
+        // sd_capsule) needs its divisor there
+        const float bax = pr.p[3] - pr.p[0], bay = pr.p[4] - pr.p[1], baz = pr.p[5] - pr.p[2];
+        const float baba = bax * bax + bay * bay + baz * baz;
+        if (!(baba >= kMinCapsule2 && baba < kMaxCapsule2)) return SDF_E_INVALID_ARG;
+      }
+    }
+    return SDF_OK;
+  }
+  if (scene.kind != SDF_SCENE_MANDELBULB) return SDF_E_INVALID_ARG;
+  // local coordinates (p - c) * RN(1/scale) stay finite: |p - c| <= ~3e15
+  // and 1/scale <= 1e15, so the exact kernel's Markstein steps (unbounded
+  // above, BulbScene::local) never see an overflowing product
+  if (!(scene.bulb_scale >= 1.0f / kMaxCoord && scene.bulb_scale <= kMaxCoord))
+    return SDF_E_INVALID_ARG;
+  for (float v : scene.bulb_center)
+    if (!(std::fabs(v) <= kMaxCoord)) return SDF_E_INVALID_ARG;
+  if (scene.bulb_iterations < 1 || scene.bulb_iterations > 64) return SDF_E_INVALID_ARG;
+  // bailout in (0, 2^32]: its square stays finite, so every iteration's
+  // x^2 + z^2 <= m <= bailout^2 is finite (the exact kernel's 1 / sqrt of it,
+  // render_kernel.inc frsqrt, relies on that)
+  if (!(scene.bulb_bailout > 0.0f && scene.bulb_bailout <= 4294967296.0f))
+    return SDF_E_INVALID_ARG;
+  return SDF_OK;
+}
+
+// the lights' own rules: the count, the flags, every position in the working
+// range; a colour is an arbitrary finite factor (negative ones included)
+int validate_lights(const sdf_light* lights, int32_t n, int32_t flags) {
+  if (!lights || n < 1 || n > SDF_MAX_LIGHTS) return SDF_E_INVALID_ARG;
+  if (flags & ~SDF_LIGHTS_COLOR) return SDF_E_INVALID_ARG;
+  for (int i = 0; i < n; ++i) {
+    for (float v : lights[i].pos)
+      if (!(std::fabs(v) <= kMaxCoord)) return SDF_E_INVALID_ARG;
+    if ((flags & SDF_LIGHTS_COLOR) && !finite3(lights[i].color)) return SDF_E_INVALID_ARG;
+  }
+  return SDF_OK;
+}
+
+int validate_reflect(const sdf_reflect* r) {
+  if (!r) return SDF_E_INVALID_ARG;
+  if (r->bounces < 0 || r->bounces > SDF_MAX_BOUNCES) return SDF_E_INVALID_ARG;
+  if (r->layer < -1 || r->layer > r->bounces) return SDF_E_INVALID_ARG;
+  if (r->flags & ~SDF_REFLECT_WEIGHT) return SDF_E_INVALID_ARG;
+  if ((r->flags & SDF_REFLECT_WEIGHT) && r->layer < 0) return SDF_E_INVALID_ARG;
+  if (!std::isfinite(r->strength)) return SDF_E_INVALID_ARG;
+  return SDF_OK;
+}
+
+// sdf_environment's own rules (sdf_abi.h "Environment"); fields of a feature
+// whose flag is off are not looked at
+int validate_environment(const sdf_environment& e) {
+  if (e.flags & ~(SDF_ENV_SKY | SDF_ENV_SUN | SDF_ENV_FOG)) return SDF_E_INVALID_ARG;
+  if ((e.flags & SDF_ENV_SUN) && !(e.flags & SDF_ENV_SKY)) return SDF_E_INVALID_ARG;
+  if (e.flags & SDF_ENV_SKY)
+    if (!finite3(e.horizon) || !finite3(e.zenith) || !finite3(e.ground)) return SDF_E_INVALID_ARG;
+  if (e.flags & SDF_ENV_SUN)
+    if (!finite3(e.sun_dir) || !finite3(e.sun_color) || !std::isfinite(e.sun_exponent) ||
+        !(e.sun_exponent >= 1.0f))
+      return SDF_E_INVALID_ARG;
+  if (e.flags & SDF_ENV_FOG) {
+    if (!finite3(e.fog_color) || !std::isfinite(e.fog_start) || !std::isfinite(e.fog_end))
+      return SDF_E_INVALID_ARG;
+    // the kernels divide by den (exact) or multiply by RN(1 / den) (fast):
+    // both must be numbers above 0
+    const float den = e.fog_end - e.fog_start;   // RN: this unit never contracts
+    if (!(den > 0.0f) || !std::isfinite(den) || !std::isfinite(1.0f / den))
+      return SDF_E_INVALID_ARG;
+  }
+  return SDF_OK;
+}
+
+// every entry's amb, dif and ref are materials[0]'s byte for byte (the three
+// lead the struct; the shininess apart): the frame has one material
+bool one_material(const sdf_material* materials, int32_t n) {
+  for (int i = 1; i < n; ++i)
+    if (std::memcmp(&materials[i], &materials[0], offsetof(sdf_material, shininess)) != 0)
+      return false;
+  return true;
+}
+// the call is sdf_render_materials itself: no bounce, and the composite or
+// layer 0's colour asked for
+bool reflect_is_materials(const sdf_reflect& r) {
+  return r.bounces == 0 && !(r.flags & SDF_REFLECT_WEIGHT);
+}
+
+bool no_device() {
+  int ndev = 0;
+  return hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0;
+}
+
+}  // namespace
+
 namespace sdf {
+
+int validate_camera(const sdf_camera* camera) {
+  if (!camera) return SDF_E_INVALID_ARG;
+  for (float v : camera->view)
+    if (!std::isfinite(v)) return SDF_E_INVALID_ARG;
+  if (!std::isfinite(camera->fov_deg) || !std::isfinite(camera->pi)) return SDF_E_INVALID_ARG;
+  for (float v : camera->eye)
+    if (!(std::fabs(v) <= kMaxCoord)) return SDF_E_INVALID_ARG;
+  float inv[16];
+  if (!invert_view(camera->view, inv)) return SDF_E_INVALID_ARG;
+  for (float v : inv)
+    if (!(std::fabs(v) <= kMaxCoord)) return SDF_E_INVALID_ARG;
+  // the hoisted camera position inverse(V_mat) * (eye, 1) (voxel_fragment.frag:180)
+  for (int i = 0; i < 3; ++i) {
+    const double c = (double)inv[i] * camera->eye[0] + (double)inv[4 + i] * camera->eye[1] +
+                     (double)inv[8 + i] * camera->eye[2] + inv[12 + i];
+    if (!(std::fabs(c) <= kMaxCoord)) return SDF_E_INVALID_ARG;
+  }
+  return SDF_OK;
+}
+
+// The order matters where SDF_E_UNSUPPORTED competes with SDF_E_INVALID_ARG.
+int validate_request(const Request& r, Depth depth, bool framed) {
+  const bool env = depth >= kEnv && r.env && r.env->flags != 0;
+  int rc = env ? validate_environment(*r.env) : SDF_OK;
+  if (rc == SDF_OK && depth >= kReflect) rc = validate_reflect(r.reflect);
+  if (rc != SDF_OK) return rc;
+  if (depth >= kMaterials) {
+    if (!r.materials || !r.scene) return SDF_E_INVALID_ARG;
+    // one material per primitive; a Mandelbulb has one
+    const int32_t want = r.scene->kind == SDF_SCENE_PRIMITIVES ? r.scene->count : 1;
+    if (r.nmaterials < 1 || r.nmaterials > SDF_MAX_PRIMS || r.nmaterials != want)
+      return SDF_E_INVALID_ARG;
+  }
+  rc = validate_lights(r.lights, r.nlights, r.light_flags);
+  if (rc != SDF_OK) return rc;
+  // a material's checks are its presence alone
+  if (!r.scene || !r.materials || !r.params) return SDF_E_INVALID_ARG;
+  rc = validate_params(*r.params, r.tiling);
+  if (rc == SDF_OK) rc = validate_scene(*r.scene);
+  if (rc == SDF_OK && framed) rc = validate_camera(r.camera);
+  if (rc != SDF_OK) return rc;
+  // valid requests no kernel serves: shading terms do not average to the
+  // colour, so no stream is resolved from sub-samples, and a stream carries
+  // one light's and one material's terms of one layer, and no sky or fog
+  const bool stream = is_stream(r.params->output_format);
+  if (r.params->samples > 1 && stream) return SDF_E_UNSUPPORTED;
+  if ((r.nlights > 1 || r.light_flags != 0) && stream) return SDF_E_UNSUPPORTED;
+  if (depth >= kMaterials) {
+    // the exponent is frame-wide: the bits of materials[0].shininess everywhere
+    for (int i = 1; i < r.nmaterials; ++i)
+      if (std::memcmp(&r.materials[i].shininess, &r.materials[0].shininess, sizeof(float)) != 0)
+        return SDF_E_UNSUPPORTED;
+    if (!one_material(r.materials, r.nmaterials) && stream) return SDF_E_UNSUPPORTED;
+  }
+  if (depth >= kReflect) {
+    // a reflected layer's colour feeds the next weight and the composite: the
+    // components must be numbers
+    if (r.reflect->bounces >= 1)
+      for (int i = 0; i < r.nmaterials; ++i)
+        if (!finite3(r.materials[i].amb) || !finite3(r.materials[i].dif) ||
+            !finite3(r.materials[i].ref))
+          return SDF_E_INVALID_ARG;
+    if (!reflect_is_materials(*r.reflect) && stream) return SDF_E_UNSUPPORTED;
+  }
+  return env && stream ? SDF_E_UNSUPPORTED : SDF_OK;
+}
+
+// The kernel family a validated request needs: the collapse rules.  A request
+// that collapses takes the lower family's path, kernels and bits.
+static Depth route(const Request& r) {
+  if (r.env && r.env->flags != 0) return kEnv;
+  if (r.reflect && !reflect_is_materials(*r.reflect)) return kReflect;
+  if (!one_material(r.materials, r.nmaterials)) return kMaterials;   // a Mandelbulb: never
+  return r.nlights == 1 && r.light_flags == 0 ? kPlain : kLights;
+}
 
 void plan_set_camera(RenderPlan* plan, const sdf_camera* camera) {
   KernelArgs& a = plan->a;
@@ -398,63 +636,92 @@ void plan_set_camera(RenderPlan* plan, const sdf_camera* camera) {
   a.aspect = camera->aspect > 0.0f ? camera->aspect : (float)a.width / (float)a.height;
 }
 
-int make_render_plan(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* light,
-                     const sdf_material* material, const sdf_params* params,
-                     const sdf_tiling* tiling, void* rgba, int32_t* steps, RenderPlan* plan) {
-  int rc = sdf_validate(scene, camera, light, material, params, tiling);
-  if (rc != SDF_OK) return rc;
-  if (!plan) return SDF_E_INVALID_ARG;
-  // Supersampling (params->samples = S > 1): the kernel is handed the S W x
+// The pixel grid of a width x height frame and the camera behind it.
+static void plan_view(RenderPlan* plan, const sdf_camera& camera, int width, int height) {
+  KernelArgs& a = plan->a;
+  a.width = width;
+  a.height = height;
+  a.inv_width = 1.0f / (float)width;
+  a.inv_height = 1.0f / (float)height;
+  plan_set_camera(plan, &camera);
+}
+
+// The frame step of a validated request's plan, on a zeroed plan: the rows,
+// the camera, the tiling's geometry, the outputs and the size of a TILES stream.
+// With plan->rows = 0 nothing is to be rendered (SDF_OK).
+static int plan_frame(const sdf_camera& camera, const sdf_params& params, const sdf_tiling* tiling,
+                      void* rgba, int32_t* steps, RenderPlan* plan) {
+  // Supersampling (params.samples = S > 1): the kernel is handed the S W x
   // S H sub-sample frame, whose pixel grid is exactly the request's S x S
   // sub-sample grid ((2x+1)/W - 1 at S W), under the request's tiling with
   // block_rows S times as long: S times the rows, every block and the frame's
   // last row a multiple of S.  The plan's rows (what a schedule matches and
   // the grid covers) are sub-sample rows.
-  const int S = params->samples > 1 ? params->samples : 1;
+  const int S = params.samples > 1 ? params.samples : 1;
   sdf_tiling t = tiling ? *tiling : kWholeFrame;
   t.block_rows *= S;
-  const int rows = count_rows(params->height * S, t);
-  std::memset(plan, 0, sizeof(*plan));
+  const int rows = count_rows(params.height * S, t);
   plan->rows = rows;
   if (rows == 0) return SDF_OK;  // a rank that owns no block: nothing to write
   if (!rgba) return SDF_E_INVALID_ARG;
-
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return SDF_E_NO_DEVICE;
+  if (no_device()) return SDF_E_NO_DEVICE;
 
   KernelArgs& a = plan->a;
-  a.width = params->width * S;
-  a.height = params->height * S;
-  a.out_width = params->width;
+  plan_view(plan, camera, params.width * S, params.height * S);
+  a.out_width = params.width;
   a.ss_log2 = S == 4 ? 2 : S == 2 ? 1 : 0;
-  plan_set_camera(plan, camera);
+  a.block_rows = t.block_rows;
+  a.chunk_rows = t.block_rows * sdf::tiling_run(t);
+  a.run_gap_rows = sdf::tiling_gap_rows(t);
+  a.first_block = t.first_block;
+  a.block_stride = t.block_stride;
+  a.rows = rows;
+  a.frame_rows = (t.flags & SDF_TILING_FRAME_ROWS) ? 1 : 0;
+  a.rgba = rgba;
+  a.steps = steps;
+  plan->tiles_ntiles = params.output_format == SDF_FORMAT_TILES
+                           ? ((params.width + 7) / 8) * ((rows + 7) / 8)
+                           : 0;
+  // TILES offsets and the `used` header word are uint32 (tiles.hip): a
+  // stream whose worst case would not fit them is refused, not wrapped
+  if (plan->tiles_ntiles > 0 && TilesLayout(plan->tiles_ntiles).stream_end > 0xffffffffull)
+    return SDF_E_UNSUPPORTED;
+  return SDF_OK;
+}
+
+// The scene step: the primitive blocks and the culling bounds, the march and
+// shading parameters under one light and one material, and the kernel that
+// serves the scene (variant, precision, JIT flag and signature).
+static void plan_scene(const sdf_scene& scene, const sdf_light& light,
+                       const sdf_material& material, const sdf_params& params, RenderPlan* plan) {
+  KernelArgs& a = plan->a;
   for (int i = 0; i < 3; ++i) {
-    a.light_pos[i] = light->pos[i];
-    a.mat_amb[i] = material->amb[i];
-    a.mat_dif[i] = material->dif[i];
-    a.mat_ref[i] = material->ref[i];
+    a.light_pos[i] = light.pos[i];
+    a.mat_amb[i] = material.amb[i];
+    a.mat_dif[i] = material.dif[i];
+    a.mat_ref[i] = material.ref[i];
   }
-  a.light_amb = light->ambient;
-  a.shininess = material->shininess;
-  a.max_steps = params->max_steps;
-  a.max_dist = params->max_dist;
-  a.eps = params->eps;
-  a.shadow_k = params->shadow_k;
-  a.normal_eps = params->normal_eps;
-  a.shadow_offset = params->shadow_offset;
-  a.flags = params->flags;
-  a.normal_mode = params->normal_mode;
-  a.format = params->output_format;
-  a.ao_taps = (params->flags & SDF_FLAG_AO) ? params->ao_taps : 0;
-  a.ao_step = params->ao_step;
-  a.ao_base = params->ao_base;
-  a.ao_falloff = params->ao_falloff;
-  a.ao_strength = params->ao_strength;
+  a.light_amb = light.ambient;
+  a.shininess = material.shininess;
+  a.max_steps = params.max_steps;
+  a.max_dist = params.max_dist;
+  a.eps = params.eps;
+  a.shadow_k = params.shadow_k;
+  a.normal_eps = params.normal_eps;
+  a.shadow_offset = params.shadow_offset;
+  a.flags = params.flags;
+  a.normal_mode = params.normal_mode;
+  a.format = params.output_format;
+  a.ao_taps = (params.flags & SDF_FLAG_AO) ? params.ao_taps : 0;
+  a.ao_step = params.ao_step;
+  a.ao_base = params.ao_base;
+  a.ao_falloff = params.ao_falloff;
+  a.ao_strength = params.ao_strength;
   // AO tap heights, in the oracle's fp32 operation order (oracle_core.h
   // ambient_occlusion): t = i / (taps - 1); h = base + step * t
   for (int i = 0; i < a.ao_taps && i < kMaxAoTaps; ++i) {
     const float tt = a.ao_taps > 1 ? (float)i / (float)(a.ao_taps - 1) : 0.0f;
-    a.ao_h[i] = params->ao_base + params->ao_step * tt;
+    a.ao_h[i] = params.ao_base + params.ao_step * tt;
   }
   // the AO taps' path lengths from P, visited in order (render_kernel.inc):
   // |h_0| + sum |h_k - h_(k-1)|, rounded up to fp32 so it never undercounts
@@ -467,47 +734,46 @@ int make_render_plan(const sdf_scene* scene, const sdf_camera* camera, const sdf
       a.ao_path[i] = f;
     }
   }
-  a.inv_width = 1.0f / (float)a.width;
-  a.inv_height = 1.0f / (float)a.height;
-  a.block_rows = t.block_rows;
-  a.chunk_rows = t.block_rows * run_of(t);
-  a.run_gap_rows = sdf::tiling_gap_rows(t);
-  a.first_block = t.first_block;
-  a.block_stride = t.block_stride;
-  a.rows = rows;
-  a.frame_rows = (t.flags & SDF_TILING_FRAME_ROWS) ? 1 : 0;
-  a.scene_kind = scene->kind;
-  a.prim_count = scene->kind == SDF_SCENE_PRIMITIVES ? scene->count : 0;
-  for (int i = 0; i < 3; ++i) a.bulb_center[i] = scene->bulb_center[i];
-  a.bulb_scale = scene->bulb_scale;
-  a.bulb_bail2 = scene->bulb_bailout * scene->bulb_bailout;
-  a.bulb_iterations = scene->bulb_iterations;
-  prepare_prims(*scene, a.prims);
+  a.scene_kind = scene.kind;
+  a.prim_count = scene.kind == SDF_SCENE_PRIMITIVES ? scene.count : 0;
+  for (int i = 0; i < 3; ++i) a.bulb_center[i] = scene.bulb_center[i];
+  a.bulb_scale = scene.bulb_scale;
+  a.bulb_bail2 = scene.bulb_bailout * scene.bulb_bailout;
+  a.bulb_iterations = scene.bulb_iterations;
+  a.bulb_inv_scale = 1.0f / scene.bulb_scale;
+  prepare_prims(scene, a.prims);
   // the generic kernel on request, and beyond the culling's proven range
   // (there unculled); only the specialised kernels carry gaps along a path
-  const bool prims = scene->kind == SDF_SCENE_PRIMITIVES;
-  const bool exact = params->precision == SDF_PRECISION_EXACT;
-  const bool cached = params->dispatch == SDF_DISPATCH_AUTO;
-  const bool cull_proven = !prims || prepare_bounds(*scene, a, exact, cached, params->max_dist);
-  a.bulb_inv_scale = 1.0f / scene->bulb_scale;
-  a.rgba = rgba;
-  a.steps = steps;
-
+  const bool prims = scene.kind == SDF_SCENE_PRIMITIVES;
+  const bool exact = params.precision == SDF_PRECISION_EXACT;
+  const bool cached = params.dispatch == SDF_DISPATCH_AUTO;
+  const bool cull_proven = !prims || prepare_bounds(scene, a, exact, cached, params.max_dist);
   const bool generic = (!cached || !cull_proven) && prims;
-  if (params->dispatch == SDF_DISPATCH_UNCULLED || !cull_proven) a.cluster_first = a.prim_count;
-  plan->variant = generic ? kVariantGeneric : select_variant(*scene);
-  plan->exact = params->precision == SDF_PRECISION_EXACT;
+  if (params.dispatch == SDF_DISPATCH_UNCULLED || !cull_proven) a.cluster_first = a.prim_count;
+  plan->variant = generic ? kVariantGeneric : select_variant(scene);
+  plan->exact = exact;
   // no built-in specialisation: a run-time compiled one (jit.cpp)
   plan->jit = plan->variant == kVariantGeneric && !generic && a.prim_count > 0;
-  if (plan->jit) plan->nsig = scene_signature(*scene, plan->sig);
-  plan->tiles_ntiles = params->output_format == SDF_FORMAT_TILES
-                           ? ((params->width + 7) / 8) * ((rows + 7) / 8)
-                           : 0;
-  // TILES offsets and the `used` header word are uint32 (tiles.hip): a
-  // stream whose worst case would not fit them is refused, not wrapped
-  if (plan->tiles_ntiles > 0 && TilesLayout(plan->tiles_ntiles).stream_end > 0xffffffffull)
-    return SDF_E_UNSUPPORTED;
-  return SDF_OK;
+  if (plan->jit) plan->nsig = scene_signature(scene, plan->sig);
+}
+
+// Both steps for a validated request under its first light and material.
+static int plan_request(const Request& r, void* rgba, int32_t* steps, RenderPlan* plan) {
+  std::memset(plan, 0, sizeof(*plan));
+  const int rc = plan_frame(*r.camera, *r.params, r.tiling, rgba, steps, plan);
+  if (rc == SDF_OK && plan->rows > 0)
+    plan_scene(*r.scene, r.lights[0], r.materials[0], *r.params, plan);
+  return rc;
+}
+
+int make_render_plan(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* light,
+                     const sdf_material* material, const sdf_params* params,
+                     const sdf_tiling* tiling, void* rgba, int32_t* steps, RenderPlan* plan) {
+  const Request r = {scene, camera, light, 1, 0, material, 1, nullptr, nullptr, params, tiling};
+  const int rc = validate_request(r, kPlain);
+  if (rc != SDF_OK) return rc;
+  if (!plan) return SDF_E_INVALID_ARG;
+  return plan_request(r, rgba, steps, plan);
 }
 
 int launch_render_plan(const RenderPlan& plan, void* stream) {
@@ -687,15 +953,60 @@ static void fill_materials(sdf::RenderPlan& plan, const sdf_material* materials,
     }
 }
 
-// A validated sdf_reflect's uniforms (the reflect, env and rays kernels).
-static sdf::ReflectArgs fill_reflect(const sdf_reflect& reflect) {
-  sdf::ReflectArgs r{};
-  r.on = 1;
-  r.bounces = reflect.bounces;
-  r.strength = reflect.strength;
-  r.layer = reflect.layer;
-  r.weight = (reflect.flags & SDF_REFLECT_WEIGHT) ? 1 : 0;
-  return r;
+// A validated environment's uniforms (flags != 0): the fields of the features
+// that are on; the rest stays zero
+static sdf::EnvArgs fill_env(const sdf_environment& env) {
+  sdf::EnvArgs e{};
+  e.on = 1;
+  e.flags = env.flags;
+  if (env.flags & SDF_ENV_SKY)
+    for (int c = 0; c < 3; ++c) {
+      e.horizon[c] = env.horizon[c];
+      e.zenith[c] = env.zenith[c];
+      e.ground[c] = env.ground[c];
+    }
+  if (env.flags & SDF_ENV_SUN) {
+    for (int c = 0; c < 3; ++c) {
+      e.sun_dir[c] = env.sun_dir[c];
+      e.sun_color[c] = env.sun_color[c];
+    }
+    e.sun_exponent = env.sun_exponent;
+  }
+  if (env.flags & SDF_ENV_FOG) {
+    for (int c = 0; c < 3; ++c) e.fog_color[c] = env.fog_color[c];
+    e.fog_end = env.fog_end;
+    e.fog_den = env.fog_end - env.fog_start;   // RN, > 0 (validate_environment)
+    e.fog_inv = 1.0f / e.fog_den;
+  }
+  return e;
+}
+
+// What the kernels of `family` read beside the plan's one light and material,
+// from a validated request.  Every family above kPlain is a lights kernel (for
+// every L >= 1, one plain light included); the reflect and env kernels fold
+// the table of every primitive scene (a Mandelbulb's one material is the
+// plan's own).
+static void fill_plan(sdf::RenderPlan& plan, const sdf::Request& r, sdf::Depth family) {
+  if (family >= sdf::kLights) fill_lights(plan, r.lights, r.nlights, r.light_flags);
+  if (family >= sdf::kMaterials && r.scene->kind == SDF_SCENE_PRIMITIVES)
+    fill_materials(plan, r.materials, r.nmaterials);
+  if (family >= sdf::kReflect)   // on, bounces, strength, layer, weight
+    plan.reflect = {1, r.reflect->bounces, r.reflect->strength, r.reflect->layer,
+                    (r.reflect->flags & SDF_REFLECT_WEIGHT) ? 1 : 0, {0, 0, 0}};
+  if (family >= sdf::kEnv) plan.env = fill_env(*r.env);
+}
+
+// Every frame render: the request validated once at the entry point's depth,
+// routed to its kernel family, planned and launched.
+static int render_request(const sdf::Request& r, sdf::Depth depth, void* rgba, int32_t* steps,
+                          sdf_schedule* schedule, void* stream) {
+  int rc = sdf::validate_request(r, depth);
+  if (rc != SDF_OK) return rc;
+  sdf::RenderPlan plan;
+  rc = sdf::plan_request(r, rgba, steps, &plan);
+  if (rc != SDF_OK) return rc;
+  fill_plan(plan, r, sdf::route(r));
+  return run_plan(plan, schedule, stream);
 }
 
 extern "C" {
@@ -729,11 +1040,8 @@ int sdf_render_scheduled(const sdf_scene* scene, const sdf_camera* camera, const
                          const sdf_material* material, const sdf_params* params,
                          const sdf_tiling* tiling, void* rgba, int32_t* steps,
                          sdf_schedule* schedule, void* stream) {
-  sdf::RenderPlan plan;
-  int rc = sdf::make_render_plan(scene, camera, light, material, params, tiling, rgba, steps,
-                                 &plan);
-  if (rc != SDF_OK) return rc;
-  return run_plan(plan, schedule, stream);
+  return render_request({scene, camera, light, 1, 0, material, 1, nullptr, nullptr, params, tiling},
+                        sdf::kPlain, rgba, steps, schedule, stream);
 }
 
 int sdf_defaults(sdf_scene* scene, sdf_camera* camera, sdf_light* light,
@@ -823,119 +1131,11 @@ int sdf_owned_rows(int32_t height, const sdf_tiling* tiling) {
   return count_rows(height, tiling ? *tiling : kWholeFrame);
 }
 
-// Working range of the kernels: every coordinate, size and distance at most
-// 1e15 in magnitude (and capsules of positive length), so that no square,
-// dot product or distance the scene evaluation forms overflows -- every
-// primitive value is then finite and the accumulated scene distance is never
-// NaN, which the exact kernel's hardware minimum relies on (render_kernel.inc
-// smin<HW>; ADVICE r04).
-constexpr float kMaxCoord = 1e15f;
-constexpr float kMinCapsule2 = 0x1p-30f;
-constexpr float kMaxCapsule2 = 0x1p30f;
-
 int sdf_validate(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* light,
                  const sdf_material* material, const sdf_params* params,
                  const sdf_tiling* tiling) {
-  if (!scene || !camera || !light || !material || !params) return SDF_E_INVALID_ARG;
-  const sdf_params& p = *params;
-  if (p.width <= 0 || p.height <= 0 || p.width > 65536 || p.height > 65536)
-    return SDF_E_INVALID_ARG;
-  // sub-samples per axis: 0 and 1 are one sample per pixel.  The sub-sample
-  // frame S W x S H is what the kernels index (cr_math.h div_refined: a quad
-  // numerator below 2^17 over at most 2^16), and its tiling's block_rows are
-  // S times the request's
-  if (p.samples != 0 && p.samples != 1 && p.samples != 2 && p.samples != 4)
-    return SDF_E_INVALID_ARG;
-  if (p.samples > 1) {
-    if (p.samples * (long long)p.width > 65536 || p.samples * (long long)p.height > 65536)
-      return SDF_E_INVALID_ARG;
-    if (tiling && tiling->block_rows > INT32_MAX / p.samples) return SDF_E_INVALID_ARG;
-  }
-  if (p.max_steps < 0 || p.max_steps > (1 << 24)) return SDF_E_INVALID_ARG;
-  // every length the marches add to a coordinate stays in the working range
-  // (kMaxCoord below): normal_eps^2 and the AO tap lengths must not overflow,
-  // which the exact kernels' one-compare cr_sqrt guard relies on (ADVICE r05)
-  for (float v : {p.max_dist, p.eps, p.shadow_k, p.normal_eps, p.shadow_offset})
-    if (!(std::fabs(v) <= kMaxCoord)) return SDF_E_INVALID_ARG;
-  if (p.flags & SDF_FLAG_AO)
-    for (float v : {p.ao_step, p.ao_base, p.ao_falloff, p.ao_strength})
-      if (!(std::fabs(v) <= kMaxCoord)) return SDF_E_INVALID_ARG;
-  if (p.flags & ~(SDF_FLAG_SHADOW | SDF_FLAG_AO)) return SDF_E_INVALID_ARG;
-  if (p.normal_mode != SDF_NORMAL_CENTRAL && p.normal_mode != SDF_NORMAL_TETRA)
-    return SDF_E_INVALID_ARG;
-  if (p.precision != SDF_PRECISION_EXACT && p.precision != SDF_PRECISION_FAST)
-    return SDF_E_INVALID_ARG;
-  if (p.dispatch < SDF_DISPATCH_AUTO || p.dispatch > SDF_DISPATCH_UNCULLED)
-    return SDF_E_INVALID_ARG;
-  if (p.output_format != SDF_FORMAT_TILES && sdf_format_bytes(p.output_format) < 0)
-    return SDF_E_INVALID_ARG;
-  if ((p.flags & SDF_FLAG_AO) && (p.ao_taps < 0 || p.ao_taps > sdf::kMaxAoTaps))
-    return SDF_E_INVALID_ARG;
-  if (count_rows(p.height, tiling ? *tiling : kWholeFrame) < 0) return SDF_E_INVALID_ARG;
-  if (tiling && (tiling->flags & SDF_TILING_FRAME_ROWS) && p.output_format == SDF_FORMAT_TILES)
-    return SDF_E_INVALID_ARG;   // a stream is made of packed tiles
-  if (scene->kind == SDF_SCENE_PRIMITIVES) {
-    if (scene->count < 0 || scene->count > SDF_MAX_PRIMS) return SDF_E_INVALID_ARG;
-    for (int i = 0; i < scene->count; ++i) {
-      const sdf_primitive& pr = scene->prims[i];
-      if (pr.kind < 0 || pr.kind >= SDF_PRIM_KIND_COUNT) return SDF_E_INVALID_ARG;
-      if (pr.op < 0 || pr.op >= SDF_OP_COUNT) return SDF_E_INVALID_ARG;
-      // a smooth blend radius in [2^-64, 1e15]: the exact smooth-min's
-      // h h (k/4) relies on the lower end (render_kernel.inc smin)
-      if (smooth_op(pr.op) && !(pr.k >= 0x1p-64f && pr.k <= kMaxCoord)) return SDF_E_INVALID_ARG;
-      for (float v : pr.p)
-        if (!std::isfinite(v) || std::fabs(v) > kMaxCoord) return SDF_E_INVALID_ARG;
-      if (pr.kind == SDF_PRIM_CAPSULE) {
-        // a segment of length in [2^-15, 2^15): dot(ba, ba), computed as the
-        // kernels do, in [2^-30, 2^30) -- the exact kernel's Markstein
-        // division of h = dot(pa, ba) / dot(ba, ba) (render_kernel.inc
-        // sd_capsule) needs its divisor there
-        const float bax = pr.p[3] - pr.p[0], bay = pr.p[4] - pr.p[1], baz = pr.p[5] - pr.p[2];
-        const float baba = bax * bax + bay * bay + baz * baz;
-        if (!(baba >= kMinCapsule2 && baba < kMaxCapsule2)) return SDF_E_INVALID_ARG;
-      }
-    }
-  } else if (scene->kind == SDF_SCENE_MANDELBULB) {
-    // local coordinates (p - c) * RN(1/scale) stay finite: |p - c| <= ~3e15
-    // and 1/scale <= 1e15, so the exact kernel's Markstein steps (unbounded
-    // above, BulbScene::local) never see an overflowing product
-    if (!(scene->bulb_scale >= 1.0f / kMaxCoord && scene->bulb_scale <= kMaxCoord))
-      return SDF_E_INVALID_ARG;
-    for (float v : scene->bulb_center)
-      if (!(std::fabs(v) <= kMaxCoord)) return SDF_E_INVALID_ARG;
-    if (scene->bulb_iterations < 1 || scene->bulb_iterations > 64) return SDF_E_INVALID_ARG;
-    // bailout in (0, 2^32]: its square stays finite, so every iteration's
-    // x^2 + z^2 <= m <= bailout^2 is finite (the exact kernel's 1 / sqrt of it,
-    // render_kernel.inc frsqrt, relies on that)
-    if (!(scene->bulb_bailout > 0.0f && scene->bulb_bailout <= 4294967296.0f))
-      return SDF_E_INVALID_ARG;
-  } else {
-    return SDF_E_INVALID_ARG;
-  }
-  for (float v : camera->view)
-    if (!std::isfinite(v)) return SDF_E_INVALID_ARG;
-  if (!finite3(camera->eye) || !std::isfinite(camera->fov_deg) || !std::isfinite(camera->pi))
-    return SDF_E_INVALID_ARG;
-  if (!finite3(light->pos)) return SDF_E_INVALID_ARG;
-  float inv[16];
-  if (!invert_view(camera->view, inv)) return SDF_E_INVALID_ARG;
-  for (float v : inv)
-    if (!(std::fabs(v) <= kMaxCoord)) return SDF_E_INVALID_ARG;
-  // the hoisted camera position inverse(V_mat) * (eye, 1) (voxel_fragment.frag:180)
-  for (int i = 0; i < 3; ++i) {
-    const double c = (double)inv[i] * camera->eye[0] + (double)inv[4 + i] * camera->eye[1] +
-                     (double)inv[8 + i] * camera->eye[2] + inv[12 + i];
-    if (!(std::fabs(c) <= kMaxCoord)) return SDF_E_INVALID_ARG;
-  }
-  for (int i = 0; i < 3; ++i)
-    if (std::fabs(camera->eye[i]) > kMaxCoord || std::fabs(light->pos[i]) > kMaxCoord)
-      return SDF_E_INVALID_ARG;
-  if (std::fabs(p.max_dist) > kMaxCoord) return SDF_E_INVALID_ARG;
-  (void)material;
-  // a valid request no kernel serves: shading terms do not average to the
-  // colour, so a resolve of TILES or SHADE32F sub-samples would be wrong
-  if (p.samples > 1 && sdf::is_stream(p.output_format)) return SDF_E_UNSUPPORTED;
-  return SDF_OK;
+  return sdf::validate_request(
+      {scene, camera, light, 1, 0, material, 1, nullptr, nullptr, params, tiling}, sdf::kPlain);
 }
 
 int sdf_format_bytes(int32_t format) {
@@ -962,88 +1162,32 @@ int64_t sdf_tiles_bytes(int32_t width, int32_t rows) {
 int sdf_render(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* light,
                const sdf_material* material, const sdf_params* params,
                const sdf_tiling* tiling, void* rgba, int32_t* steps, void* stream) {
-  sdf::RenderPlan plan;
-  const int rc = sdf::make_render_plan(scene, camera, light, material, params, tiling, rgba,
-                                       steps, &plan);
-  if (rc != SDF_OK) return rc;
-  return run_plan(plan, nullptr, stream);
+  return render_request({scene, camera, light, 1, 0, material, 1, nullptr, nullptr, params, tiling},
+                        sdf::kPlain, rgba, steps, nullptr, stream);
 }
 
 int sdf_validate_lights(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
                         int32_t nlights, int32_t light_flags, const sdf_material* material,
                         const sdf_params* params, const sdf_tiling* tiling) {
-  if (!lights || nlights < 1 || nlights > SDF_MAX_LIGHTS) return SDF_E_INVALID_ARG;
-  if (light_flags & ~SDF_LIGHTS_COLOR) return SDF_E_INVALID_ARG;
-  // every light as sdf_validate checks its one light
-  for (int i = 0; i < nlights; ++i) {
-    if (!finite3(lights[i].pos)) return SDF_E_INVALID_ARG;
-    for (float v : lights[i].pos)
-      if (std::fabs(v) > kMaxCoord) return SDF_E_INVALID_ARG;
-    // a colour is an arbitrary finite factor (negative ones included)
-    if ((light_flags & SDF_LIGHTS_COLOR) && !finite3(lights[i].color)) return SDF_E_INVALID_ARG;
-  }
-  const int rc = sdf_validate(scene, camera, &lights[0], material, params, tiling);
-  if (rc != SDF_OK) return rc;
-  // a TILES or SHADE32F stream carries one light's terms
-  if ((nlights > 1 || light_flags != 0) && sdf::is_stream(params->output_format))
-    return SDF_E_UNSUPPORTED;
-  return SDF_OK;
+  return sdf::validate_request({scene, camera, lights, nlights, light_flags, material, 1, nullptr,
+                                nullptr, params, tiling}, sdf::kLights);
 }
 
 int sdf_render_lights(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
                       int32_t nlights, int32_t light_flags, const sdf_material* material,
                       const sdf_params* params, const sdf_tiling* tiling, void* rgba,
                       int32_t* steps, sdf_schedule* schedule, void* stream) {
-  int rc = sdf_validate_lights(scene, camera, lights, nlights, light_flags, material, params,
-                               tiling);
-  if (rc != SDF_OK) return rc;
-  // one plain light: sdf_render's own path, kernels and bits
-  if (nlights == 1 && light_flags == 0)
-    return sdf_render_scheduled(scene, camera, &lights[0], material, params, tiling, rgba, steps,
-                                schedule, stream);
-  sdf::RenderPlan plan;
-  rc = sdf::make_render_plan(scene, camera, &lights[0], material, params, tiling, rgba, steps,
-                             &plan);
-  if (rc != SDF_OK) return rc;
-  fill_lights(plan, lights, nlights, light_flags);
-  return run_plan(plan, schedule, stream);
-}
-
-// amb, dif and ref of two materials byte for byte (the shininess apart)
-static bool same_colours(const sdf_material& a, const sdf_material& b) {
-  return std::memcmp(a.amb, b.amb, sizeof(a.amb)) == 0 &&
-         std::memcmp(a.dif, b.dif, sizeof(a.dif)) == 0 &&
-         std::memcmp(a.ref, b.ref, sizeof(a.ref)) == 0;
-}
-// every entry's amb, dif and ref are materials[0]'s: the frame has one material
-static bool one_material(const sdf_material* materials, int32_t n) {
-  for (int i = 1; i < n; ++i)
-    if (!same_colours(materials[i], materials[0])) return false;
-  return true;
+  return render_request({scene, camera, lights, nlights, light_flags, material, 1, nullptr,
+                         nullptr, params, tiling},
+                        sdf::kLights, rgba, steps, schedule, stream);
 }
 
 int sdf_validate_materials(const sdf_scene* scene, const sdf_camera* camera,
                            const sdf_light* lights, int32_t nlights, int32_t light_flags,
                            const sdf_material* materials, int32_t nmaterials,
                            const sdf_params* params, const sdf_tiling* tiling) {
-  if (!materials || !scene) return SDF_E_INVALID_ARG;
-  // one material per primitive; a Mandelbulb has one
-  const int32_t want = scene->kind == SDF_SCENE_PRIMITIVES ? scene->count : 1;
-  if (nmaterials < 1 || nmaterials > SDF_MAX_PRIMS || nmaterials != want)
-    return SDF_E_INVALID_ARG;
-  // everything else as sdf_validate_lights checks it; sdf_validate's checks of
-  // a material are its presence alone, which holds for every entry here
-  const int rc = sdf_validate_lights(scene, camera, lights, nlights, light_flags, &materials[0],
-                                     params, tiling);
-  if (rc != SDF_OK) return rc;
-  // the exponent is frame-wide: the bits of materials[0].shininess everywhere
-  for (int i = 1; i < nmaterials; ++i)
-    if (std::memcmp(&materials[i].shininess, &materials[0].shininess, sizeof(float)) != 0)
-      return SDF_E_UNSUPPORTED;
-  // a TILES or SHADE32F stream carries one material's constants
-  if (!one_material(materials, nmaterials) && sdf::is_stream(params->output_format))
-    return SDF_E_UNSUPPORTED;
-  return SDF_OK;
+  return sdf::validate_request({scene, camera, lights, nlights, light_flags, materials, nmaterials,
+                                nullptr, nullptr, params, tiling}, sdf::kMaterials);
 }
 
 int sdf_render_materials(const sdf_scene* scene, const sdf_camera* camera,
@@ -1051,29 +1195,9 @@ int sdf_render_materials(const sdf_scene* scene, const sdf_camera* camera,
                          const sdf_material* materials, int32_t nmaterials,
                          const sdf_params* params, const sdf_tiling* tiling, void* rgba,
                          int32_t* steps, sdf_schedule* schedule, void* stream) {
-  int rc = sdf_validate_materials(scene, camera, lights, nlights, light_flags, materials,
-                                  nmaterials, params, tiling);
-  if (rc != SDF_OK) return rc;
-  // one material for the whole frame (a Mandelbulb always): sdf_render_lights's
-  // own path, kernels and bits
-  if (one_material(materials, nmaterials))
-    return sdf_render_lights(scene, camera, lights, nlights, light_flags, &materials[0], params,
-                             tiling, rgba, steps, schedule, stream);
-  sdf::RenderPlan plan;
-  rc = sdf::make_render_plan(scene, camera, &lights[0], &materials[0], params, tiling, rgba,
-                             steps, &plan);
-  if (rc != SDF_OK) return rc;
-  // the materials kernels are lights kernels for every L >= 1, one plain
-  // light included
-  fill_lights(plan, lights, nlights, light_flags);
-  fill_materials(plan, materials, nmaterials);
-  return run_plan(plan, schedule, stream);
-}
-
-// the call is sdf_render_materials itself: no bounce, and the composite or
-// layer 0's colour asked for
-static bool reflect_is_materials(const sdf_reflect& r) {
-  return r.bounces == 0 && !(r.flags & SDF_REFLECT_WEIGHT);
+  return render_request({scene, camera, lights, nlights, light_flags, materials, nmaterials,
+                         nullptr, nullptr, params, tiling},
+                        sdf::kMaterials, rgba, steps, schedule, stream);
 }
 
 int sdf_validate_reflect(const sdf_scene* scene, const sdf_camera* camera,
@@ -1081,46 +1205,8 @@ int sdf_validate_reflect(const sdf_scene* scene, const sdf_camera* camera,
                          const sdf_material* materials, int32_t nmaterials,
                          const sdf_reflect* reflect, const sdf_params* params,
                          const sdf_tiling* tiling) {
-  if (!reflect) return SDF_E_INVALID_ARG;
-  if (reflect->bounces < 0 || reflect->bounces > SDF_MAX_BOUNCES) return SDF_E_INVALID_ARG;
-  if (reflect->layer < -1 || reflect->layer > reflect->bounces) return SDF_E_INVALID_ARG;
-  if (reflect->flags & ~SDF_REFLECT_WEIGHT) return SDF_E_INVALID_ARG;
-  if ((reflect->flags & SDF_REFLECT_WEIGHT) && reflect->layer < 0) return SDF_E_INVALID_ARG;
-  if (!std::isfinite(reflect->strength)) return SDF_E_INVALID_ARG;
-  const int rc = sdf_validate_materials(scene, camera, lights, nlights, light_flags, materials,
-                                        nmaterials, params, tiling);
-  if (rc != SDF_OK) return rc;
-  // a reflected layer's colour feeds the next weight and the composite: the
-  // components must be numbers
-  if (reflect->bounces >= 1)
-    for (int i = 0; i < nmaterials; ++i)
-      if (!finite3(materials[i].amb) || !finite3(materials[i].dif) || !finite3(materials[i].ref))
-        return SDF_E_INVALID_ARG;
-  // a stream carries one layer's terms
-  if (!reflect_is_materials(*reflect) && sdf::is_stream(params->output_format))
-    return SDF_E_UNSUPPORTED;
-  return SDF_OK;
-}
-
-// The launch of a validated reflect render through the reflect kernels, or,
-// with `env` (sdf_render_env with a flag set), through the env kernels.
-static int launch_reflect(const sdf_scene* scene, const sdf_camera* camera,
-                          const sdf_light* lights, int32_t nlights, int32_t light_flags,
-                          const sdf_material* materials, int32_t nmaterials,
-                          const sdf_reflect* reflect, const sdf::EnvArgs* env,
-                          const sdf_params* params, const sdf_tiling* tiling, void* rgba,
-                          int32_t* steps, sdf_schedule* schedule, void* stream) {
-  sdf::RenderPlan plan;
-  int rc = sdf::make_render_plan(scene, camera, &lights[0], &materials[0], params, tiling, rgba,
-                             steps, &plan);
-  if (rc != SDF_OK) return rc;
-  // the reflect kernels are lights kernels and fold the table of every
-  // primitive scene (a Mandelbulb's one material is the plan's own)
-  fill_lights(plan, lights, nlights, light_flags);
-  if (scene->kind == SDF_SCENE_PRIMITIVES) fill_materials(plan, materials, nmaterials);
-  plan.reflect = fill_reflect(*reflect);
-  if (env) plan.env = *env;
-  return run_plan(plan, schedule, stream);
+  return sdf::validate_request({scene, camera, lights, nlights, light_flags, materials, nmaterials,
+                                reflect, nullptr, params, tiling}, sdf::kReflect);
 }
 
 int sdf_render_reflect(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
@@ -1128,82 +1214,17 @@ int sdf_render_reflect(const sdf_scene* scene, const sdf_camera* camera, const s
                        int32_t nmaterials, const sdf_reflect* reflect, const sdf_params* params,
                        const sdf_tiling* tiling, void* rgba, int32_t* steps,
                        sdf_schedule* schedule, void* stream) {
-  int rc = sdf_validate_reflect(scene, camera, lights, nlights, light_flags, materials, nmaterials,
-                                reflect, params, tiling);
-  if (rc != SDF_OK) return rc;
-  // no bounce: sdf_render_materials's own path, kernels and bits
-  if (reflect_is_materials(*reflect))
-    return sdf_render_materials(scene, camera, lights, nlights, light_flags, materials, nmaterials,
-                                params, tiling, rgba, steps, schedule, stream);
-  return launch_reflect(scene, camera, lights, nlights, light_flags, materials, nmaterials, reflect,
-                        nullptr, params, tiling, rgba, steps, schedule, stream);
-}
-
-// sdf_environment's own rules (sdf_abi.h "Environment"); fields of a feature
-// whose flag is off are not looked at
-static int validate_environment(const sdf_environment& e) {
-  if (e.flags & ~(SDF_ENV_SKY | SDF_ENV_SUN | SDF_ENV_FOG)) return SDF_E_INVALID_ARG;
-  if ((e.flags & SDF_ENV_SUN) && !(e.flags & SDF_ENV_SKY)) return SDF_E_INVALID_ARG;
-  if (e.flags & SDF_ENV_SKY)
-    if (!finite3(e.horizon) || !finite3(e.zenith) || !finite3(e.ground)) return SDF_E_INVALID_ARG;
-  if (e.flags & SDF_ENV_SUN)
-    if (!finite3(e.sun_dir) || !finite3(e.sun_color) || !std::isfinite(e.sun_exponent) ||
-        !(e.sun_exponent >= 1.0f))
-      return SDF_E_INVALID_ARG;
-  if (e.flags & SDF_ENV_FOG) {
-    if (!finite3(e.fog_color) || !std::isfinite(e.fog_start) || !std::isfinite(e.fog_end))
-      return SDF_E_INVALID_ARG;
-    // the kernels divide by den (exact) or multiply by RN(1 / den) (fast):
-    // both must be numbers above 0
-    const float den = e.fog_end - e.fog_start;   // RN: this unit never contracts
-    if (!(den > 0.0f) || !std::isfinite(den) || !std::isfinite(1.0f / den))
-      return SDF_E_INVALID_ARG;
-  }
-  return SDF_OK;
+  return render_request({scene, camera, lights, nlights, light_flags, materials, nmaterials,
+                         reflect, nullptr, params, tiling},
+                        sdf::kReflect, rgba, steps, schedule, stream);
 }
 
 int sdf_validate_env(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
                      int32_t nlights, int32_t light_flags, const sdf_material* materials,
                      int32_t nmaterials, const sdf_reflect* reflect, const sdf_environment* env,
                      const sdf_params* params, const sdf_tiling* tiling) {
-  if (env && env->flags != 0) {
-    const int rc = validate_environment(*env);
-    if (rc != SDF_OK) return rc;
-  }
-  const int rc = sdf_validate_reflect(scene, camera, lights, nlights, light_flags, materials,
-                                      nmaterials, reflect, params, tiling);
-  if (rc != SDF_OK) return rc;
-  // a stream carries one layer's terms, and no sky or fog
-  if (env && env->flags != 0 && sdf::is_stream(params->output_format)) return SDF_E_UNSUPPORTED;
-  return SDF_OK;
-}
-
-// A validated environment's uniforms (flags != 0): the fields of the features
-// that are on; the rest stays zero
-static sdf::EnvArgs fill_env(const sdf_environment* env) {
-  sdf::EnvArgs e{};
-  e.on = 1;
-  e.flags = env->flags;
-  if (env->flags & SDF_ENV_SKY)
-    for (int c = 0; c < 3; ++c) {
-      e.horizon[c] = env->horizon[c];
-      e.zenith[c] = env->zenith[c];
-      e.ground[c] = env->ground[c];
-    }
-  if (env->flags & SDF_ENV_SUN) {
-    for (int c = 0; c < 3; ++c) {
-      e.sun_dir[c] = env->sun_dir[c];
-      e.sun_color[c] = env->sun_color[c];
-    }
-    e.sun_exponent = env->sun_exponent;
-  }
-  if (env->flags & SDF_ENV_FOG) {
-    for (int c = 0; c < 3; ++c) e.fog_color[c] = env->fog_color[c];
-    e.fog_end = env->fog_end;
-    e.fog_den = env->fog_end - env->fog_start;   // RN, > 0 (validate_environment)
-    e.fog_inv = 1.0f / e.fog_den;
-  }
-  return e;
+  return sdf::validate_request({scene, camera, lights, nlights, light_flags, materials, nmaterials,
+                                reflect, env, params, tiling}, sdf::kEnv);
 }
 
 int sdf_render_env(const sdf_scene* scene, const sdf_camera* camera, const sdf_light* lights,
@@ -1211,16 +1232,9 @@ int sdf_render_env(const sdf_scene* scene, const sdf_camera* camera, const sdf_l
                    int32_t nmaterials, const sdf_reflect* reflect, const sdf_environment* env,
                    const sdf_params* params, const sdf_tiling* tiling, void* rgba, int32_t* steps,
                    sdf_schedule* schedule, void* stream) {
-  // nothing switched on: sdf_render_reflect's own path, kernels and bits
-  if (!env || env->flags == 0)
-    return sdf_render_reflect(scene, camera, lights, nlights, light_flags, materials, nmaterials,
-                              reflect, params, tiling, rgba, steps, schedule, stream);
-  const int rc = sdf_validate_env(scene, camera, lights, nlights, light_flags, materials,
-                                  nmaterials, reflect, env, params, tiling);
-  if (rc != SDF_OK) return rc;
-  const sdf::EnvArgs e = fill_env(env);
-  return launch_reflect(scene, camera, lights, nlights, light_flags, materials, nmaterials, reflect,
-                        &e, params, tiling, rgba, steps, schedule, stream);
+  return render_request({scene, camera, lights, nlights, light_flags, materials, nmaterials,
+                         reflect, env, params, tiling},
+                        sdf::kEnv, rgba, steps, schedule, stream);
 }
 
 // ---- queries (sdf_abi.h "Queries") ------------------------------------------
@@ -1247,34 +1261,30 @@ sdf_params query_params(const sdf_params& p, bool frame) {
   return q;
 }
 
+// a query's own checks: its params, its scene, and its camera where it has one
 int validate_query(const sdf_scene* scene, const sdf_camera* camera, const sdf_params& q) {
-  sdf_camera c;
-  sdf_light l;
-  sdf_material m;
-  sdf_defaults(nullptr, &c, &l, &m, nullptr, 0, 0);
-  return sdf_validate(scene, camera ? camera : &c, &l, &m, &q, nullptr);
+  int rc = validate_params(q, nullptr);
+  if (rc == SDF_OK && scene) rc = validate_scene(*scene);
+  if (rc == SDF_OK && camera) rc = sdf::validate_camera(camera);
+  return rc;
 }
 
-// The prepared scene of a call that renders no frame (a query, a mesh, a
-// gradient), under the query's params `q`: plan->a with the scene blocks, the
-// culling bounds and the march parameters (and `camera` hoisted where the call
-// has one), no outputs, and beside it the variant, the precision, the JIT flag
-// and the signature.  A render's plan, made with sdf_defaults' camera, light
-// and material standing in for what such a call does not have (`light`,
-// `material`: the call's own, where it shades -- sdf_shade_points).
+// The prepared scene of a validated call that renders no frame (a query, a
+// mesh, a gradient, rays, points), under the call's params `q`: the plan's
+// scene step alone, and the pixel grid of `camera` where the call has one.  No
+// outputs.  `light`, `material`: the call's own where it shades; sdf_defaults'
+// otherwise, which the kernel arguments then carry.
 int scene_plan(const sdf_scene* scene, const sdf_camera* camera, const sdf_params& q,
                sdf::RenderPlan* plan, const sdf_light* light = nullptr,
                const sdf_material* material = nullptr) {
-  sdf_camera c;
+  if (no_device()) return SDF_E_NO_DEVICE;
   sdf_light l;
   sdf_material m;
-  sdf_defaults(nullptr, &c, &l, &m, nullptr, 0, 0);
-  int unused = 0;   // a render's plan refuses a null framebuffer
-  const int rc = sdf::make_render_plan(scene, camera ? camera : &c, light ? light : &l,
-                                       material ? material : &m, &q, nullptr, &unused, nullptr,
-                                       plan);
-  if (rc == SDF_OK) plan->a.rgba = nullptr;
-  return rc;
+  if (!light || !material) sdf_defaults(nullptr, nullptr, &l, &m, nullptr, 0, 0);
+  std::memset(plan, 0, sizeof(*plan));
+  if (camera) sdf::plan_view(plan, *camera, q.width, q.height);
+  sdf::plan_scene(*scene, light ? *light : l, material ? *material : m, q, plan);
+  return SDF_OK;
 }
 
 // One validated query: the scene's plan with the query's buffers.
@@ -1571,44 +1581,34 @@ int sdf_sample_grad(const sdf_scene* scene, const sdf_params* params, const floa
 namespace {
 const sdf_reflect kNoBounce = {0, 1.0f, -1, 0};   // reflect NULL: bounces 0, the composite
 
-// The params a rays call is validated and run with: the caller's, with the
-// frame size at sdf_defaults' values (a list of rays has none).
-sdf_params rays_params(const sdf_params& p) {
+// The params a call over a list of rays or points is validated and run with:
+// the caller's, with the frame size (a list has none) at sdf_defaults' values;
+// `points` have no samples and no output format either.
+sdf_params list_params(const sdf_params& p, bool points) {
   sdf_params d;
   sdf_defaults(nullptr, nullptr, nullptr, nullptr, &d, 0, 0);
   sdf_params q = p;
   q.width = d.width;
   q.height = d.height;
+  if (points) q.samples = d.samples, q.output_format = d.output_format;
   return q;
 }
 
-// One validated sdf_render_rays: the render's own plan (scene blocks, culling
-// bounds, shading parameters, dispatch; its camera and frame size unused) with
-// the lights, the table, the reflect and env uniforms of a reflect launch and
-// the ray buffers in place of a frame's geometry.
-int rays_launch(const sdf_scene* scene, const sdf_light* lights, int32_t nlights,
-                int32_t light_flags, const sdf_material* materials, int32_t nmaterials,
-                const sdf_reflect& reflect, const sdf_environment* env, const sdf_params& q,
-                const sdf_rays& rays, void* rgba, int32_t* steps, void* stream) {
-  sdf_camera c;
-  sdf_defaults(nullptr, &c, nullptr, nullptr, nullptr, 0, 0);
-  std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
-  const int rc = sdf::make_render_plan(scene, &c, &lights[0], &materials[0], &q, nullptr, rgba,
-                                       steps, plan.get());
+// A rays call's own checks, and its request validated once: on return under
+// the params it runs with, *q, and with no bounce where none was asked.
+int validate_rays(sdf::Request& r, const sdf_rays* rays, sdf_params* q) {
+  if (!rays || !r.scene || !r.params) return SDF_E_INVALID_ARG;
+  if (rays->flags & ~SDF_RAYS_UNIT) return SDF_E_INVALID_ARG;
+  if (rays->n < 0 || rays->n > kMaxQuery) return SDF_E_INVALID_ARG;
+  if (rays->n > 0 && (!rays->origins || !rays->dirs)) return SDF_E_INVALID_ARG;
+  *q = list_params(*r.params, false);
+  r.params = q;
+  if (!r.reflect) r.reflect = &kNoBounce;
+  const int rc = sdf::validate_request(r, sdf::kEnv, false);
   if (rc != SDF_OK) return rc;
-  fill_lights(*plan, lights, nlights, light_flags);
-  if (scene->kind == SDF_SCENE_PRIMITIVES) fill_materials(*plan, materials, nmaterials);
-  std::unique_ptr<sdf::RaysArgs> a(new sdf::RaysArgs());
-  a->a = plan->a;
-  a->l = plan->lights;
-  a->m = plan->materials;
-  a->r = fill_reflect(reflect);
-  if (env && env->flags != 0) a->e = fill_env(env);
-  a->in0 = rays.origins;
-  a->in1 = rays.dirs;
-  a->n = rays.n;
-  a->flags = rays.flags;
-  return sdf::launch_planned(*plan, sdf::launch_rays_jit, &sdf::RenderUnit::rays, *a, stream);
+  // the caller supplies more rays and averages; a stream has no list of rays
+  if (q->samples > 1 || sdf::is_stream(q->output_format)) return SDF_E_UNSUPPORTED;
+  return SDF_OK;
 }
 }  // namespace
 
@@ -1616,19 +1616,10 @@ int sdf_validate_rays(const sdf_scene* scene, const sdf_light* lights, int32_t n
                       int32_t light_flags, const sdf_material* materials, int32_t nmaterials,
                       const sdf_reflect* reflect, const sdf_environment* env,
                       const sdf_params* params, const sdf_rays* rays) {
-  if (!rays || !scene || !params) return SDF_E_INVALID_ARG;
-  if (rays->flags & ~SDF_RAYS_UNIT) return SDF_E_INVALID_ARG;
-  if (rays->n < 0 || rays->n > kMaxQuery) return SDF_E_INVALID_ARG;
-  if (rays->n > 0 && (!rays->origins || !rays->dirs)) return SDF_E_INVALID_ARG;
-  sdf_camera c;
-  sdf_defaults(nullptr, &c, nullptr, nullptr, nullptr, 0, 0);
-  const sdf_params q = rays_params(*params);
-  const int rc = sdf_validate_env(scene, &c, lights, nlights, light_flags, materials, nmaterials,
-                                  reflect ? reflect : &kNoBounce, env, &q, nullptr);
-  if (rc != SDF_OK) return rc;
-  // the caller supplies more rays and averages; a stream has no list of rays
-  if (q.samples > 1 || sdf::is_stream(q.output_format)) return SDF_E_UNSUPPORTED;
-  return SDF_OK;
+  sdf_params q;
+  sdf::Request r = {scene,   nullptr, lights, nlights, light_flags, materials, nmaterials,
+                    reflect, env,     params, nullptr};
+  return validate_rays(r, rays, &q);
 }
 
 int sdf_render_rays(const sdf_scene* scene, const sdf_light* lights, int32_t nlights,
@@ -1636,38 +1627,50 @@ int sdf_render_rays(const sdf_scene* scene, const sdf_light* lights, int32_t nli
                     const sdf_reflect* reflect, const sdf_environment* env,
                     const sdf_params* params, const sdf_rays* rays, void* rgba, int32_t* steps,
                     void* stream) {
-  const int rc = sdf_validate_rays(scene, lights, nlights, light_flags, materials, nmaterials,
-                                   reflect, env, params, rays);
+  sdf_params q;
+  sdf::Request r = {scene,   nullptr, lights, nlights, light_flags, materials, nmaterials,
+                    reflect, env,     params, nullptr};
+  int rc = validate_rays(r, rays, &q);
   if (rc != SDF_OK) return rc;
   if (rays->n == 0) return SDF_OK;   // nothing to launch, no device needed
   if (!rgba) return SDF_E_INVALID_ARG;
-  return rays_launch(scene, lights, nlights, light_flags, materials, nmaterials,
-                     reflect ? *reflect : kNoBounce, env, rays_params(*params), *rays, rgba, steps,
-                     stream);
+  // the scene's plan under light 0 and material 0, with the uniforms of a
+  // reflect launch (an env launch where one is asked) and the ray buffers in
+  // place of a frame's geometry
+  std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
+  rc = scene_plan(scene, nullptr, q, plan.get(), &lights[0], &materials[0]);
+  if (rc != SDF_OK) return rc;
+  fill_plan(*plan, r, std::max(sdf::route(r), sdf::kReflect));
+  std::unique_ptr<sdf::RaysArgs> a(new sdf::RaysArgs());
+  a->a = plan->a;
+  a->a.rgba = rgba;
+  a->a.steps = steps;
+  a->l = plan->lights;
+  a->m = plan->materials;
+  a->r = plan->reflect;
+  a->e = plan->env;
+  a->in0 = rays->origins;
+  a->in1 = rays->dirs;
+  a->n = rays->n;
+  a->flags = rays->flags;
+  return sdf::launch_planned(*plan, sdf::launch_rays_jit, &sdf::RenderUnit::rays, *a, stream);
 }
 
 int sdf_camera_rays(const sdf_camera* camera, const sdf_params* params, float* origins,
                     float* dirs, void* stream) {
   if (!camera || !params || (!origins && !dirs)) return SDF_E_INVALID_ARG;
-  sdf_scene s;
-  sdf_defaults(&s, nullptr, nullptr, nullptr, nullptr, 0, 0);
   const sdf_params q = query_params(*params, true);
-  const int rc = validate_query(&s, camera, q);
+  const int rc = validate_query(nullptr, camera, q);
   if (rc != SDF_OK) return rc;
   if (params->samples > 1) return SDF_E_UNSUPPORTED;   // one ray per pixel
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return SDF_E_NO_DEVICE;
+  if (no_device()) return SDF_E_NO_DEVICE;
   // the hoisted camera and the quad mapping of a render of this frame size;
   // no scene: the precision alone picks the kernel (variant 0, never JIT)
   std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
   std::unique_ptr<sdf::RaysArgs> a(new sdf::RaysArgs());
   plan->exact = q.precision == SDF_PRECISION_EXACT;
-  plan->a.width = q.width;
-  plan->a.height = q.height;
-  sdf::plan_set_camera(plan.get(), camera);
+  sdf::plan_view(plan.get(), *camera, q.width, q.height);
   a->a = plan->a;
-  a->a.inv_width = 1.0f / (float)q.width;
-  a->a.inv_height = 1.0f / (float)q.height;
   a->out0 = origins;
   a->out1 = dirs;
   return sdf::launch_built_in(*plan, &sdf::RenderUnit::camera_rays, *a, stream);
@@ -1678,35 +1681,29 @@ static_assert(sizeof(sdf_points) == 48, "sdf_points layout");
 static_assert(sizeof(sdf_point_shade) == 40, "sdf_point_shade layout");
 
 namespace {
-// The params a points call is validated and run with: the caller's, with the
-// frame's fields (a list of points has none) at sdf_defaults' values.
-sdf_params points_params(const sdf_params& p) {
-  sdf_params d;
-  sdf_defaults(nullptr, nullptr, nullptr, nullptr, &d, 0, 0);
-  sdf_params q = p;
-  q.width = d.width;
-  q.height = d.height;
-  q.samples = d.samples;
-  q.output_format = d.output_format;
-  return q;
-}
-}  // namespace
-
-int sdf_validate_points(const sdf_scene* scene, const sdf_light* lights, int32_t nlights,
-                        int32_t light_flags, const sdf_material* materials, int32_t nmaterials,
-                        const sdf_params* params, const sdf_points* pts) {
-  if (!pts || !scene || !params) return SDF_E_INVALID_ARG;
+// A points call's own checks, and its request validated once: on return under
+// the params it runs with, *q.
+int validate_points(sdf::Request& r, const sdf_points* pts, sdf_params* q) {
+  if (!pts || !r.scene || !r.params) return SDF_E_INVALID_ARG;
   if ((pts->flags & ~SDF_POINTS_EYE) || pts->reserved != 0) return SDF_E_INVALID_ARG;
   if (pts->n < 0 || pts->n > kMaxQuery || (pts->n > 0 && !pts->points)) return SDF_E_INVALID_ARG;
   if (!(pts->lift >= 0.0f && pts->lift <= 1e15f)) return SDF_E_INVALID_ARG;
   if (pts->flags & SDF_POINTS_EYE)
     for (int c = 0; c < 3; ++c)
       if (!(std::fabs(pts->eye[c]) <= 1e15f)) return SDF_E_INVALID_ARG;
-  sdf_camera c;
-  sdf_defaults(nullptr, &c, nullptr, nullptr, nullptr, 0, 0);
-  const sdf_params q = points_params(*params);
-  return sdf_validate_materials(scene, &c, lights, nlights, light_flags, materials, nmaterials, &q,
-                                nullptr);
+  *q = list_params(*r.params, true);
+  r.params = q;
+  return sdf::validate_request(r, sdf::kMaterials, false);
+}
+}  // namespace
+
+int sdf_validate_points(const sdf_scene* scene, const sdf_light* lights, int32_t nlights,
+                        int32_t light_flags, const sdf_material* materials, int32_t nmaterials,
+                        const sdf_params* params, const sdf_points* pts) {
+  sdf_params q;
+  sdf::Request r = {scene,   nullptr, lights, nlights, light_flags, materials, nmaterials,
+                    nullptr, nullptr, params, nullptr};
+  return validate_points(r, pts, &q);
 }
 
 int sdf_shade_points(const sdf_scene* scene, const sdf_light* lights, int32_t nlights,
@@ -1718,18 +1715,19 @@ int sdf_shade_points(const sdf_scene* scene, const sdf_light* lights, int32_t nl
     return SDF_E_INVALID_ARG;
   // the kernels store a point's colour as one 16-byte word
   if (reinterpret_cast<uintptr_t>(out->rgba) % 16 != 0) return SDF_E_INVALID_ARG;
-  int rc = sdf_validate_points(scene, lights, nlights, light_flags, materials, nmaterials, params,
-                               pts);
+  sdf_params q;
+  sdf::Request r = {scene,   nullptr, lights, nlights, light_flags, materials, nmaterials,
+                    nullptr, nullptr, params, nullptr};
+  int rc = validate_points(r, pts, &q);
   if (rc != SDF_OK) return rc;
   if (pts->n == 0) return SDF_OK;   // nothing to launch, no device needed
   // the scene's plan (scene blocks, culling bounds, march and shading parameters,
   // dispatch; no camera, no frame, no outputs) under light 0 and material 0,
   // with the lights and the table of a materials launch and the point buffers
   std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
-  rc = scene_plan(scene, nullptr, points_params(*params), plan.get(), &lights[0], &materials[0]);
+  rc = scene_plan(scene, nullptr, q, plan.get(), &lights[0], &materials[0]);
   if (rc != SDF_OK) return rc;
-  fill_lights(*plan, lights, nlights, light_flags);
-  if (scene->kind == SDF_SCENE_PRIMITIVES) fill_materials(*plan, materials, nmaterials);
+  fill_plan(*plan, r, sdf::kMaterials);
   std::unique_ptr<sdf::PointsArgs> a(new sdf::PointsArgs());
   a->a = plan->a;
   // the occlusion taps run only for an output that needs them
@@ -1765,12 +1763,7 @@ const char* sdf_kernel_id(int32_t precision) {
 int sdf_scene_bounds(const sdf_scene* scene, float* bounds, float* cluster,
                      int32_t* cluster_first) {
   if (!scene || !bounds || !cluster || !cluster_first) return SDF_E_INVALID_ARG;
-  sdf_camera c;
-  sdf_light l;
-  sdf_material m;
-  sdf_params p;
-  sdf_defaults(nullptr, &c, &l, &m, &p, 0, 0);
-  const int rc = sdf_validate(scene, &c, &l, &m, &p, nullptr);   // the scene's own checks
+  const int rc = validate_scene(*scene);
   if (rc != SDF_OK) return rc;
   if (scene->kind != SDF_SCENE_PRIMITIVES) return SDF_E_UNSUPPORTED;
   std::unique_ptr<sdf::KernelArgs> a(new sdf::KernelArgs());
@@ -1807,7 +1800,7 @@ int decode_parts(const void* parts, int32_t nparts, int64_t part_stride, const s
     d.first_block[r] = t.first_block;
     d.block_stride[r] = t.block_stride;
     d.block_rows[r] = t.block_rows;
-    d.chunk_rows[r] = t.block_rows * run_of(t);
+    d.chunk_rows[r] = t.block_rows * sdf::tiling_run(t);
     d.run_gap_rows[r] = sdf::tiling_gap_rows(t);
   }
   const int err = sdf::launch_tiles_decode(d, frame, parts, stream);

@@ -157,6 +157,25 @@ def mesh_sharp(sharp):
     return abi.sdf_mesh_sharp(int(refine), int(iterations), 0, 0)
 
 
+def _shading(frame: Frame, lights, materials, reflect=None):
+    """The ctypes form of a call's `lights`, `materials` and `reflect` with
+    ``Renderer.render``'s defaults -- the frame's light; the frame's material
+    on every primitive (once for a Mandelbulb); a ``(bounces, strength)`` pair
+    is the composite of that many bounces: (light array, its count, material
+    array, its count, the sdf_reflect or None)."""
+    if reflect is not None and not isinstance(reflect, abi.sdf_reflect):
+        bounces, strength = reflect
+        reflect = abi.sdf_reflect(int(bounces), float(strength), -1, 0)
+    if materials is None:
+        prims = frame.scene.kind == abi.SCENE_PRIMITIVES
+        materials = [frame.material] * (frame.scene.count if prims else 1)
+    materials = list(materials)
+    marr = (abi.sdf_material * max(len(materials), 1))(*materials)
+    lights = [frame.light] if lights is None else list(lights)
+    larr = (abi.sdf_light * max(len(lights), 1))(*lights)
+    return larr, len(lights), marr, len(materials), reflect
+
+
 class Renderer:
     """Renders frames on one HIP device through ``sdf_render``."""
 
@@ -255,60 +274,33 @@ class Renderer:
                                or not st.is_contiguous()):
             raise ValueError(f"steps must be a contiguous int32 {sshape} tensor")
         with self._on_device():
-            tail = (C.byref(frame.material), C.byref(frame.params),
-                    C.byref(t) if t is not None else None,
+            head = (C.byref(frame.scene), C.byref(frame.camera))
+            tail = (C.byref(frame.params), C.byref(t) if t is not None else None,
                     C.c_void_p(rgba.data_ptr()),
                     C.c_void_p(st.data_ptr()) if st is not None else None)
-            args = (C.byref(frame.scene), C.byref(frame.camera), C.byref(frame.light), *tail)
+            sched = schedule.handle if schedule is not None else None
             if env is not None and reflect is None:
                 reflect = abi.sdf_reflect(0, 1.0, -1, 0)
-            if reflect is not None:
-                if not isinstance(reflect, abi.sdf_reflect):
-                    bounces, strength = reflect
-                    reflect = abi.sdf_reflect(int(bounces), float(strength), -1, 0)
-                if materials is None:
-                    prims = frame.scene.kind == abi.SCENE_PRIMITIVES
-                    materials = [frame.material] * (frame.scene.count if prims else 1)
-                materials = list(materials)
-                marr = (abi.sdf_material * max(len(materials), 1))(*materials)
-                lights = [frame.light] if lights is None else list(lights)
-                arr = (abi.sdf_light * max(len(lights), 1))(*lights)
-                head = (C.byref(frame.scene), C.byref(frame.camera), arr, len(lights),
-                        int(light_flags), marr, len(materials), C.byref(reflect))
-                sched = schedule.handle if schedule is not None else None
+            name = "sdf_render"
+            if reflect is not None or materials is not None or lights is not None:
+                larr, nl, marr, nm, reflect = _shading(frame, lights, materials, reflect)
+                lit = (*head, larr, nl, int(light_flags))
                 if env is not None:
-                    rc = self.lib.sdf_render_env(*head, C.byref(env), *tail[1:], sched,
-                                                 self._stream(stream))
-                    abi.check(rc, "sdf_render_env")
-                    return rgba, st
-                rc = self.lib.sdf_render_reflect(*head, *tail[1:], sched, self._stream(stream))
-                abi.check(rc, "sdf_render_reflect")
-                return rgba, st
-            if materials is not None:
-                materials = list(materials)
-                marr = (abi.sdf_material * max(len(materials), 1))(*materials)
-                lights = [frame.light] if lights is None else list(lights)
-                arr = (abi.sdf_light * max(len(lights), 1))(*lights)
-                rc = self.lib.sdf_render_materials(
-                    C.byref(frame.scene), C.byref(frame.camera), arr, len(lights),
-                    int(light_flags), marr, len(materials), *tail[1:],
-                    schedule.handle if schedule is not None else None, self._stream(stream))
-                abi.check(rc, "sdf_render_materials")
-                return rgba, st
-            if lights is not None:
-                lights = list(lights)
-                arr = (abi.sdf_light * max(len(lights), 1))(*lights)
-                rc = self.lib.sdf_render_lights(
-                    C.byref(frame.scene), C.byref(frame.camera), arr, len(lights),
-                    int(light_flags), *tail,
-                    schedule.handle if schedule is not None else None, self._stream(stream))
-                abi.check(rc, "sdf_render_lights")
-                return rgba, st
-            if schedule is None:
-                rc = self.lib.sdf_render(*args, self._stream(stream))
+                    name, args = "sdf_render_env", (*lit, marr, nm, C.byref(reflect), C.byref(env))
+                elif reflect is not None:
+                    name, args = "sdf_render_reflect", (*lit, marr, nm, C.byref(reflect))
+                elif materials is not None:
+                    name, args = "sdf_render_materials", (*lit, marr, nm)
+                else:
+                    name, args = "sdf_render_lights", (*lit, C.byref(frame.material))
+                rc = getattr(self.lib, name)(*args, *tail, sched, self._stream(stream))
             else:
-                rc = self.lib.sdf_render_scheduled(*args, schedule.handle, self._stream(stream))
-        abi.check(rc, "sdf_render")
+                args = (*head, C.byref(frame.light), C.byref(frame.material), *tail)
+                if schedule is None:
+                    rc = self.lib.sdf_render(*args, self._stream(stream))
+                else:
+                    rc = self.lib.sdf_render_scheduled(*args, sched, self._stream(stream))
+        abi.check(rc, name)
         return rgba, st
 
     def render_multi(self, frame: Frame, devices, shares=(0, 0), out=None, stream=None):
@@ -581,21 +573,12 @@ class Renderer:
         if st is not None and (tuple(st.shape) != (n, 2) or st.dtype != torch.int32
                                or not st.is_contiguous() or st.device != self.device):
             raise ValueError(f"steps must be a contiguous int32 ({n}, 2) tensor on {self.device}")
-        if reflect is not None and not isinstance(reflect, abi.sdf_reflect):
-            bounces, strength = reflect
-            reflect = abi.sdf_reflect(int(bounces), float(strength), -1, 0)
-        if materials is None:
-            prims = frame.scene.kind == abi.SCENE_PRIMITIVES
-            materials = [frame.material] * (frame.scene.count if prims else 1)
-        materials = list(materials)
-        marr = (abi.sdf_material * max(len(materials), 1))(*materials)
-        lights = [frame.light] if lights is None else list(lights)
-        arr = (abi.sdf_light * max(len(lights), 1))(*lights)
+        arr, nl, marr, nm, reflect = _shading(frame, lights, materials, reflect)
         rays = abi.sdf_rays(o.data_ptr() if n else None, d.data_ptr() if n else None, n,
                             abi.RAYS_UNIT if unit else 0, 0)
         with self._on_device():
             rc = self.lib.sdf_render_rays(
-                C.byref(frame.scene), arr, len(lights), int(light_flags), marr, len(materials),
+                C.byref(frame.scene), arr, nl, int(light_flags), marr, nm,
                 C.byref(reflect) if reflect is not None else None,
                 C.byref(env) if env is not None else None, C.byref(frame.params),
                 C.byref(rays), C.c_void_p(rgba.data_ptr()) if n else None,
@@ -628,14 +611,7 @@ class Renderer:
             raise ValueError("points and normals must have the same shape")
         if not (rgba or ao or shadow or material or steps):
             raise ValueError("shade_points needs at least one output")
-        if materials is None:
-            prims = frame.scene.kind == abi.SCENE_PRIMITIVES
-            materials = [frame.material] * (frame.scene.count if prims else 1)
-        materials = list(materials)
-        marr = (abi.sdf_material * max(len(materials), 1))(*materials)
-        lights = [frame.light] if lights is None else list(lights)
-        arr = (abi.sdf_light * max(len(lights), 1))(*lights)
-        nl = len(lights)
+        arr, nl, marr, nm, _ = _shading(frame, lights, materials)
 
         def new(want, tail, dtype=torch.float32):
             return torch.empty((n, *tail), dtype=dtype, device=self.device) if want else None
@@ -656,7 +632,7 @@ class Renderer:
                                    for x in out])
         with self._on_device():
             rc = self.lib.sdf_shade_points(C.byref(frame.scene), arr, nl, int(light_flags), marr,
-                                           len(materials), C.byref(frame.params), C.byref(p),
+                                           nm, C.byref(frame.params), C.byref(p),
                                            C.byref(ps), self._stream(stream))
         abi.check(rc, "sdf_shade_points")
         return out

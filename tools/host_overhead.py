@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Host (CPU) time of the per-frame calls the frame driver makes: one
 Renderer.render enqueue, one tiles_decode enqueue, a torch event record and
-an empty-ish torch op, measured without waiting for the GPU (small frames,
-so the queue never backs up).
+an empty-ish torch op, and of the shading entry points above sdf_render -- an
+sdf_render_env call that collapses to sdf_render and one with a sky and a
+bounce, sdf_render_rays and sdf_shade_points on 4,096 rays and points --
+measured without waiting for the GPU (small frames, so the queue never backs
+up).
 
     python tools/host_overhead.py
 """
@@ -40,6 +43,11 @@ def main():
     frame = torch.empty((64, 64, 4), dtype=torch.float32, device=rd.device)
     ev = torch.cuda.Event()
     x = torch.zeros(1, device=rd.device)
+    # nothing switched on: no flag, no bounce, one material, one plain light
+    nothing, sky = abi.sdf_environment(), scenes.sky()
+    o, d = (r.view(-1, 3) for r in rd.camera_rays(f))
+    rays_out, _ = rd.render_rays(f, o, d, unit=True)
+    pts = o + d
     out = {
         "render_us": per_call(lambda: rd.render(f, out=buf, stream=s)),
         "render_tiles_us": per_call(lambda: rd.render(ft, out=tb, stream=s)),
@@ -47,6 +55,12 @@ def main():
                                                             out=frame, stream=s)),
         "event_record_us": per_call(lambda: ev.record(s)),
         "torch_add_us": per_call(lambda: x.add_(1)),
+        "render_env_collapsing_us": per_call(lambda: rd.render(f, out=buf, stream=s, env=nothing)),
+        "render_env_sky_bounce_us": per_call(lambda: rd.render(f, out=buf, stream=s, env=sky,
+                                                               reflect=(1, 0.5))),
+        "render_rays_us": per_call(lambda: rd.render_rays(f, o, d, unit=True, out=rays_out,
+                                                          stream=s)),
+        "shade_points_us": per_call(lambda: rd.shade_points(f, pts, stream=s)),
     }
     print(json.dumps(out, indent=1))
 
