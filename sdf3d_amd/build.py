@@ -82,38 +82,36 @@ UNITS = [
     ("multi.cpp", ["-x", "hip"]),
     ("frames.cpp", ["-ffp-contract=off", "-x", "hip"]),
 ]
-# sources the run-time specialiser (jit.cpp) compiles with hipRTC, embedded
-# into the library as string literals (build/rtc_sources.inc)
-RTC_SOURCES = [("kRtcRenderKernel", CSRC / "render_kernel.inc"),
-               ("kRtcMeshKernel", CSRC / "mesh_kernel.inc"),
-               ("kRtcGradKernel", CSRC / "grad_kernel.inc"),
-               ("kRtcKernelArgs", CSRC / "kernel_args.h"),
-               ("kRtcWaveBits", CSRC / "wave_bits.h"),
-               ("kRtcCrMath", CSRC / "cr_math.h"),
-               ("kRtcShade", CSRC / "shade.h"),
-               ("kRtcAbiHeader", ROOT / "include" / "sdf_abi.h")]
+# The device sources, in the order render_kernel.inc takes them: what the
+# built-in render kernels of one precision are made of (kernel_id: kernel
+# sources alone, no host launcher), what hipRTC is given for a run-time
+# specialisation (rtc_sources.inc) and, with the host-only headers, what makes
+# an object stale.  An entry is (include name, path); the name is the path
+# from csrc/, as the files include one another.  The one list of them.
+KERNEL_SOURCES = [(n, Path(os.path.normpath(CSRC / n))) for n in (
+    "render_kernel.inc", "kernel_args.h", "../../include/sdf_abi.h", "wave_bits.h", "shade.h",
+    "cr_math.h", "kmath.inc", "prims.inc", "store.inc", "scenes.inc", "trace.inc",
+    "pixel_paths.inc", "render_entry.inc", "query_kernel.inc", "grad_kernel.inc",
+    "mesh_kernel.inc", "rays_kernel.inc", "points_kernel.inc", "jit_entry.inc")]
+HEADERS = [p for _, p in KERNEL_SOURCES] + [CSRC / "host_api.h", CSRC / "render_launch.inc",
+                                            CSRC / "turbo_lut.inc"]
 
 
 def write_rtc_sources() -> Path:
+    """The device sources as the two columns hiprtcCreateProgram takes (include
+    names, texts) and their count, embedded into the library (jit.cpp)."""
     out = OBJ / "rtc_sources.inc"
-    srcs = [p for _, p in RTC_SOURCES]
-    if _stale(out, [*srcs, Path(__file__)]):
-        parts = ["// generated by sdf3d_amd/build.py -- kernel sources for hipRTC (jit.cpp)\n"]
-        for name, path in RTC_SOURCES:
-            text = path.read_text()
-            assert ")SDF3D\"" not in text
-            parts.append(f'static const char {name}[] = R"SDF3D({text})SDF3D";\n')
-        out.write_text("".join(parts))
+    if _stale(out, [*(p for _, p in KERNEL_SOURCES), Path(__file__)]):
+        texts = [p.read_text() for _, p in KERNEL_SOURCES]
+        assert not any(')SDF3D"' in t for t in texts)
+        out.write_text(
+            "// generated by sdf3d_amd/build.py (KERNEL_SOURCES) -- kernel sources for hipRTC\n"
+            f"static const int kRtcCount = {len(texts)};\n"
+            "static const char* kRtcNames[] = {\n"
+            + "".join(f'    "{n}",\n' for n, _ in KERNEL_SOURCES) + "};\n"
+            "static const char* kRtcTexts[] = {\n"
+            + "".join(f'    R"SDF3D({t})SDF3D",\n' for t in texts) + "};\n")
     return out
-HEADERS = [CSRC / "kernel_args.h", CSRC / "render_kernel.inc", CSRC / "mesh_kernel.inc",
-           CSRC / "grad_kernel.inc", CSRC / "host_api.h", CSRC / "render_launch.inc",
-           CSRC / "wave_bits.h", CSRC / "cr_math.h", CSRC / "shade.h", CSRC / "turbo_lut.inc",
-           ROOT / "include" / "sdf_abi.h"]
-# what the built-in render kernels of one precision are made of (kernel_id):
-# kernel sources alone, no host launcher (render_launch.inc, host_api.h)
-KERNEL_SOURCES = [CSRC / "render_kernel.inc", CSRC / "mesh_kernel.inc",
-                  CSRC / "grad_kernel.inc", CSRC / "kernel_args.h", CSRC / "wave_bits.h",
-                  CSRC / "cr_math.h", CSRC / "shade.h", ROOT / "include" / "sdf_abi.h"]
 
 
 def _compiler_version() -> str:
@@ -140,8 +138,8 @@ def kernel_id(unit: str, compiler: str | None = None) -> str:
     units = PRECISION_UNITS.get(unit, (unit,))
     for u in units:
         h.update(u.encode() + b"\0" + (CSRC / u).read_bytes() + b"\0")
-    for p in KERNEL_SOURCES:
-        h.update(p.name.encode() + b"\0" + p.read_bytes() + b"\0")
+    for name, p in KERNEL_SOURCES:
+        h.update(name.encode() + b"\0" + p.read_bytes() + b"\0")
     for u in units:
         h.update(" ".join([*COMMON, *dict(UNITS)[u]]).encode() + b"\0")
     h.update((compiler if compiler is not None else _compiler_version()).encode())
@@ -287,71 +285,47 @@ def build_oracle(verbose: bool = True) -> Path:
     return ROOT / "oracle" / "build" / "liboracle.so"
 
 
-MATERIALS_REF_SRC = ROOT / "tests" / "materials_ref.c"
-MATERIALS_REF_LIB = ROOT / "tests" / "build" / "libmaterials_ref.so"
+# TEST INFRASTRUCTURE: references over the CPU oracle (tests/*_ref.c, each
+# includes oracle/sdf_oracle.c), built with the oracle's floating-point flags
+# (oracle/Makefile: no contraction, no fast-math).  Never linked into
+# libsdf3d.so.
+REF_FLAGS = ["-O3", "-fPIC", "-std=c11", "-ffp-contract=off", "-fno-fast-math", "-fno-math-errno",
+             "-fopenmp", "-Wall", "-Wextra", "-Wno-unused-function", "-shared"]
+
+
+def _build_ref(name: str, force: bool, verbose: bool, over_materials: bool = True) -> Path:
+    """tests/build/lib<name>_ref.so from tests/<name>_ref.c; over_materials:
+    linked against the material fold's reference beside it (found through
+    $ORIGIN)."""
+    src = ROOT / "tests" / f"{name}_ref.c"
+    lib = ROOT / "tests" / "build" / f"lib{name}_ref.so"
+    deps = [src, ROOT / "oracle" / "sdf_oracle.c", ROOT / "oracle" / "oracle_core.h",
+            ROOT / "include" / "sdf_abi.h"]
+    link = []
+    if over_materials:
+        deps.append(build_materials_ref(force=force, verbose=verbose))
+        link = ["-L", lib.parent, "-lmaterials_ref", "-Wl,-rpath,$ORIGIN"]
+    if force or _stale(lib, deps):
+        lib.parent.mkdir(parents=True, exist_ok=True)
+        tmp = lib.with_suffix(".so.tmp")
+        _run([os.environ.get("CC", "gcc"), *REF_FLAGS, "-o", tmp, src, *link, "-lm"], verbose)
+        os.replace(tmp, lib)
+    return lib
 
 
 def build_materials_ref(force: bool = False, verbose: bool = True) -> Path:
-    """TEST INFRASTRUCTURE: the material fold's reference over the CPU oracle
-    (tests/materials_ref.c includes oracle/sdf_oracle.c), with the oracle's
-    floating-point flags (oracle/Makefile: no contraction, no fast-math).
-    Never linked into libsdf3d.so."""
-    deps = [MATERIALS_REF_SRC, ROOT / "oracle" / "sdf_oracle.c", ROOT / "oracle" / "oracle_core.h",
-            ROOT / "include" / "sdf_abi.h"]
-    if force or _stale(MATERIALS_REF_LIB, deps):
-        MATERIALS_REF_LIB.parent.mkdir(parents=True, exist_ok=True)
-        tmp = MATERIALS_REF_LIB.with_suffix(".so.tmp")
-        _run([os.environ.get("CC", "gcc"), "-O3", "-fPIC", "-std=c11", "-ffp-contract=off",
-              "-fno-fast-math", "-fno-math-errno", "-fopenmp", "-Wall", "-Wextra",
-              "-Wno-unused-function", "-shared", "-o", tmp, MATERIALS_REF_SRC, "-lm"], verbose)
-        os.replace(tmp, MATERIALS_REF_LIB)
-    return MATERIALS_REF_LIB
-
-
-REFLECT_REF_SRC = ROOT / "tests" / "reflect_ref.c"
-REFLECT_REF_LIB = ROOT / "tests" / "build" / "libreflect_ref.so"
+    """The material fold's reference."""
+    return _build_ref("materials", force, verbose, over_materials=False)
 
 
 def build_reflect_ref(force: bool = False, verbose: bool = True) -> Path:
-    """TEST INFRASTRUCTURE: the reference of mirror reflections over the CPU
-    oracle (tests/reflect_ref.c includes oracle/sdf_oracle.c), with the oracle's
-    floating-point flags, linked against the material fold's reference beside
-    it (libmaterials_ref.so, found through $ORIGIN).  Never linked into
-    libsdf3d.so."""
-    mat = build_materials_ref(force=force, verbose=verbose)
-    deps = [REFLECT_REF_SRC, ROOT / "oracle" / "sdf_oracle.c", ROOT / "oracle" / "oracle_core.h",
-            ROOT / "include" / "sdf_abi.h", mat]
-    if force or _stale(REFLECT_REF_LIB, deps):
-        tmp = REFLECT_REF_LIB.with_suffix(".so.tmp")
-        _run([os.environ.get("CC", "gcc"), "-O3", "-fPIC", "-std=c11", "-ffp-contract=off",
-              "-fno-fast-math", "-fno-math-errno", "-fopenmp", "-Wall", "-Wextra",
-              "-Wno-unused-function", "-shared", "-o", tmp, REFLECT_REF_SRC,
-              "-L", mat.parent, "-lmaterials_ref", "-Wl,-rpath,$ORIGIN", "-lm"], verbose)
-        os.replace(tmp, REFLECT_REF_LIB)
-    return REFLECT_REF_LIB
-
-
-POINTS_REF_SRC = ROOT / "tests" / "points_ref.c"
-POINTS_REF_LIB = ROOT / "tests" / "build" / "libpoints_ref.so"
+    """The reference of mirror reflections."""
+    return _build_ref("reflect", force, verbose)
 
 
 def build_points_ref(force: bool = False, verbose: bool = True) -> Path:
-    """TEST INFRASTRUCTURE: the reference of shading at caller-supplied points
-    over the CPU oracle (tests/points_ref.c includes oracle/sdf_oracle.c), with
-    the oracle's floating-point flags, linked against the material fold's
-    reference beside it (libmaterials_ref.so, found through $ORIGIN).  Never
-    linked into libsdf3d.so."""
-    mat = build_materials_ref(force=force, verbose=verbose)
-    deps = [POINTS_REF_SRC, ROOT / "oracle" / "sdf_oracle.c", ROOT / "oracle" / "oracle_core.h",
-            ROOT / "include" / "sdf_abi.h", mat]
-    if force or _stale(POINTS_REF_LIB, deps):
-        tmp = POINTS_REF_LIB.with_suffix(".so.tmp")
-        _run([os.environ.get("CC", "gcc"), "-O3", "-fPIC", "-std=c11", "-ffp-contract=off",
-              "-fno-fast-math", "-fno-math-errno", "-fopenmp", "-Wall", "-Wextra",
-              "-Wno-unused-function", "-shared", "-o", tmp, POINTS_REF_SRC,
-              "-L", mat.parent, "-lmaterials_ref", "-Wl,-rpath,$ORIGIN", "-lm"], verbose)
-        os.replace(tmp, POINTS_REF_LIB)
-    return POINTS_REF_LIB
+    """The reference of shading at caller-supplied points."""
+    return _build_ref("points", force, verbose)
 
 
 if __name__ == "__main__":

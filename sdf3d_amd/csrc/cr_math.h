@@ -15,7 +15,7 @@
 //                           fma(r, yb, q) = RN(a/b)) wherever a/b, q and r
 //                           neither overflow nor underflow (3 instructions
 //                           instead of 11).  div_scaled applies it to the
-//                           smooth-min's h = n / k (render_kernel.inc smin)
+//                           smooth-min's h = n / k (prims.inc smin)
 //                           after an exact power-of-two scaling that puts
 //                           every positive k in its domain.
 //   cr_log(x)            == (float)log((double)x) for every x.  Fast path:
@@ -145,8 +145,8 @@ __device__ __forceinline__ float div_prepared(float a, float b, float yb) {
 // The residual's sign convention keeps a signed zero numerator's sign (q0 =
 // +-0, r = +0, q1 = -0 + q0 = q0).  Domain: l in [2^-30, 2^30), every a zero
 // or |a| >= 2^-60 (quotients and residuals stay normal); other lanes of the
-// wave take the IEEE division.  The pixel's quad division (render_kernel.inc
-// shade_pixel) calls it without a guard: its numerator 2x + 1 is an integer
+// wave take the IEEE division.  The pixel's quad division (trace.inc
+// trace_surface) calls it without a guard: its numerator 2x + 1 is an integer
 // in [1, 2^17) and its divisor the width (height) the KERNEL indexes, an
 // integer in [1, 2^16] -- with supersampling the sub-sample width S W, which
 // sdf_validate holds to 65536 like a plain frame's.

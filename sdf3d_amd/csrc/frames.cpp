@@ -5,7 +5,7 @@
 //
 // Each launch takes up to kFramesPerLaunch frames.  Its grid is sized to the
 // device (8 waves per SIMD on every CU); the waves take 8x8 tiles of all its
-// frames, in order, from one work counter (render_kernel.inc render_frames),
+// frames, in order, from one work counter (render_entry.inc render_frames),
 // so no frame ends with an idle tail while its slowest tiles finish, and the
 // scene's registers are loaded once per wave instead of once per tile.  The
 // pixels are those of sdf_render bit for bit (same shade_pixel).

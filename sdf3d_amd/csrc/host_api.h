@@ -9,7 +9,7 @@
 //   Per kernel family its grid and its argument contract, which the built-in
 //     launchers (render_launch.inc) and the run-time specialised ones share.
 //
-// A new kernel family is a kernel body (render_kernel.inc), a
+// A new kernel family is a kernel body (its kernel file beside render_kernel.inc), a
 // launch_*_scene (render_launch.inc) with a RenderUnit slot, a *_args_fit and
 // *_grid here, and one launch_planned (or launch_built_in) line where its
 // entry point has the scene's plan (sdf_abi.cpp scene_plan).

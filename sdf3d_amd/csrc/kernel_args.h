@@ -59,7 +59,7 @@ struct KernelArgs {
   float bulb_center[3], bulb_scale, bulb_inv_scale, bulb_bail2;
   int32_t bulb_iterations;
   // prepared primitives (sdf_abi.cpp prepare_prims): kind, op, k,
-  // reserved = 1/k, p = per-kind parameter block (see render_kernel.inc)
+  // reserved = 1/k, p = per-kind parameter block (see prims.inc)
   sdf_primitive prims[SDF_MAX_PRIMS];
   // culling bounds (fixed-scene kernels): per primitive {centre.xyz, K} with
   // K = k + R + margin, R the radius of a sphere containing the primitive;
@@ -109,7 +109,7 @@ struct LightsArgs {
 };
 // ---- per-primitive materials (sdf_render_materials) ------------------------
 // m[i] = primitive i's material as 9 components (amb, dif, ref), read with
-// scalar loads by the material fold at P (render_kernel.inc material_fold).
+// scalar loads by the material fold at P (scenes.inc material_fold).
 // The shininess stays KernelArgs::shininess (frame-wide).  n = 0: one material
 // for the frame (KernelArgs::mat_*), nothing here is read.
 struct MaterialArgs {
@@ -118,7 +118,7 @@ struct MaterialArgs {
   int32_t reserved[3];
 };
 // ---- mirror reflections (sdf_render_reflect) --------------------------------
-// The uniforms of the loop over a pixel's layers (render_kernel.inc
+// The uniforms of the loop over a pixel's layers (pixel_paths.inc
 // shade_pixel_reflect): sdf_reflect's fields as the host validated them.
 // on = 0: no reflect kernel, nothing here is read.
 struct ReflectArgs {
@@ -130,7 +130,7 @@ struct ReflectArgs {
   int32_t reserved[3];
 };
 // ---- environment (sdf_render_env) -------------------------------------------
-// The uniforms of a missed layer's sky and of the distance fog (render_kernel.inc
+// The uniforms of a missed layer's sky and of the distance fog (pixel_paths.inc
 // shade_pixel_env, shade.h env_sky / env_fog): sdf_environment's fields as the
 // host validated them, with the fog's denominator RN(fog_end - fog_start)
 // (exact precision divides by it) and its reciprocal RN(1 / den) (fast
@@ -152,7 +152,7 @@ struct RenderArgs {
   EnvArgs e;      // behind the reflect block: an env render is a reflect render (bounces >= 0)
 };
 // ---- queries (sdf_trace, sdf_trace_camera, sdf_sample) ------------------------
-// The argument block of the query kernels (render_kernel.inc query_rays /
+// The argument block of the query kernels (query_kernel.inc query_rays /
 // query_camera / query_points), their own: RenderArgs is full (4096 bytes).
 // `a` carries the scene, the march parameters and, for camera rays, the
 // hoisted camera and the frame size; its outputs (rgba, steps) are unused.
@@ -173,7 +173,7 @@ struct QueryArgs {
   int32_t reserved;
 };
 // ---- caller-supplied rays (sdf_render_rays, sdf_camera_rays) -------------------
-// The argument block of the rays kernels (render_kernel.inc render_rays /
+// The argument block of the rays kernels (rays_kernel.inc render_rays /
 // render_rays_env / camera_rays), their own: RenderArgs is full, and its
 // RowOrder is of no use to a list of rays.  `a` carries the scene, the march
 // and shading parameters and the outputs (a.rgba: n pixels of a.format,
@@ -196,7 +196,7 @@ struct RaysArgs {
   int32_t reserved;
 };
 // ---- shading at caller-supplied points (sdf_shade_points) ----------------------
-// The argument block of the points kernels (render_kernel.inc shade_points),
+// The argument block of the points kernels (points_kernel.inc shade_points),
 // their own: `a` carries the scene, the march and shading parameters (its camera,
 // frame size and outputs are unused; a.ao_taps is 0 when no output needs the
 // occlusion term); l and m are a materials render's.  `points` holds n x 3
@@ -292,7 +292,7 @@ __host__ __device__ inline long long grad_blocks(long long n) {
   return b < kGradMaxBlocks ? b : kGradMaxBlocks;
 }
 
-// Waves (8x8 tiles side by side) per render workgroup (render_kernel.inc
+// Waves (8x8 tiles side by side) per render workgroup (render_entry.inc
 // render / render_tiles / render_ssaa; the built-in and the run-time
 // specialised launchers).
 // Round 4: one wave per workgroup -- each wave is placed on its own, so the

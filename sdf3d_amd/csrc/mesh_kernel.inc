@@ -563,23 +563,23 @@ __device__ __forceinline__ void mesh_body() {
   else if constexpr (KIND == 1) mesh_emit_body<Scene, false>();
   else mesh_count_body<Scene>();
 }
-template <class Scene>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SDF_MESH_WAVES_PER_EU, SDF_MESH_WAVES_PER_EU)))
-void mesh_count(MeshArgs args) {
-  (void)args;
-  mesh_count_body<Scene>();
+constexpr int mesh_waves(int kind) {
+  return kind == 2 ? SDF_MESH_SHARP_WAVES_PER_EU
+         : kind == 1 ? SDF_MESH_EMIT_WAVES_PER_EU
+                     : SDF_MESH_WAVES_PER_EU;
 }
+// a mesh entry, built-in or run-time (jit_entry.inc): one wave per workgroup
+#define SDF_MESH_KERNEL(name, Scene, KIND)                   \
+  SDF_KERNEL(64, mesh_waves(KIND))                           \
+  void name(MeshArgs args) {                                 \
+    (void)args;                                              \
+    mesh_body<Scene, KIND>();                                \
+  }
 template <class Scene>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SDF_MESH_EMIT_WAVES_PER_EU, SDF_MESH_EMIT_WAVES_PER_EU)))
-void mesh_emit(MeshArgs args) {
-  (void)args;
-  mesh_emit_body<Scene, false>();
-}
+SDF_MESH_KERNEL(mesh_count, Scene, 0)
+template <class Scene>
+SDF_MESH_KERNEL(mesh_emit, Scene, 1)
 #if !SDF_TU_BULB
 template <class Scene>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SDF_MESH_SHARP_WAVES_PER_EU, SDF_MESH_SHARP_WAVES_PER_EU)))
-void mesh_emit_sharp(MeshArgs args) {
-  (void)args;
-  mesh_emit_body<Scene, true>();
-}
+SDF_MESH_KERNEL(mesh_emit_sharp, Scene, 2)
 #endif

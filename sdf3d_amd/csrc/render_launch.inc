@@ -2,7 +2,7 @@
 //
 // Included behind render_kernel.inc by render_{exact,fast}.hip and
 // render_{exact,fast}_bulb.hip; host code only: no kernel source (build.py
-// KERNEL_SOURCES), nothing of it is handed to hipRTC (build.py RTC_SOURCES).
+// KERNEL_SOURCES), so nothing of it is hashed or handed to hipRTC.
 //
 // Per kernel family one launch_*_scene<Scene>: the family's grid, its argument
 // contract (host_api.h: the run-time specialised launchers of jit.cpp use the

@@ -120,7 +120,7 @@ using sdf::count_rows;
 const sdf_tiling kWholeFrame = {8, 0, 1, 0, 1, 1};
 
 // Per-frame preparation of the primitive parameter blocks the kernels read
-// (layouts in render_kernel.inc).  Every derived value is computed in fp32
+// (layouts in prims.inc).  Every derived value is computed in fp32
 // with the operation order the oracle uses per evaluation (oracle_core.h), so
 // the exact-precision kernel stays bit-identical; 1/x values are only used by
 // the fast-precision kernel.
@@ -131,7 +131,7 @@ void prepare_prims(const sdf_scene& s, sdf_primitive* out) {
     sdf_primitive& o = out[i];
     o.reserved = in.k > 0.0f ? 1.0f / in.k : 0.0f;
     o.p[11] = in.k * 0.25f;  // smooth-min k/4 (fast precision)
-    // exact precision's smooth-min division n / k (render_kernel.inc smin,
+    // exact precision's smooth-min division n / k (prims.inc smin,
     // cr_math.h smin_h / div_scaled): sc = 2^s with k sc in [0.5, 1) (s <=
     // 127, so a denormal k lands in [2^-22, 1)), and RN(1/(k sc)) by an IEEE
     // division.  k sc < 1: smin_h's clamp to [0, 1] is its max(., 0) alone
@@ -181,7 +181,7 @@ void prepare_prims(const sdf_scene& s, sdf_primitive* out) {
 // farthest sphere with diminishing length from the centroid, and the
 // two-sphere balls of every pair, keeping the best).  The tighter the
 // cluster sphere, the more often the culling and the shadow march's lit
-// tail (render_kernel.inc) skip it.  Cached per primitive list: sdf_render
+// tail (scenes.inc, trace.inc) skip it.  Cached per primitive list: sdf_render
 // prepares a plan per call.
 static double sphere_radius_at(const double (*c)[3], const double* r, int n, const double* C) {
   double R = 0;
@@ -245,7 +245,7 @@ static double cluster_sphere(const double (*c)[3], const double* r, int n, doubl
 }
 
 // Host-only constants of the culling margins (no kernel reads them).  The
-// cached gaps (render_kernel.inc FixedScene::march) compare computed path
+// cached gaps (scenes.inc FixedScene::march) compare computed path
 // points o + D t, each rounded by up to sqrt 3 2^-24 (|D t|_inf + |p|_inf);
 // at most four such points lie between a stored gap and its use, and
 // 4 sqrt 3 2^-24 < 2^-21: kCullPath holds twice that.
@@ -281,7 +281,7 @@ bool prepare_bounds(const sdf_scene& s, sdf::KernelArgs& a, bool exact = false,
       case SDF_PRIM_SPHERE: R = q[3]; break;
       case SDF_PRIM_BOX: R = std::sqrt(double(q[3]) * q[3] + double(q[4]) * q[4] + double(q[5]) * q[5]); break;
       case SDF_PRIM_ROUND_BOX: {
-        // the box (b - r) rounded by r (render_kernel.inc sd_round_box; a
+        // the box (b - r) rounded by r (prims.inc sd_round_box; a
         // negative b - r only shrinks the shape: box_core falls with e)
         double e2 = 0;
         for (int j = 3; j < 6; ++j) {
@@ -319,11 +319,11 @@ bool prepare_bounds(const sdf_scene& s, sdf::KernelArgs& a, bool exact = false,
         std::max({std::fabs(c[0]), std::fabs(c[1]), std::fabs(c[2])}) + R + k;
     if (cull[i]) span = std::max(span, reachi);
     const double margin = sdf::kCullAbs + (cached ? kCullPath * (reachi + reach) : 0.0);
-    // K' = (k + R + margin) / (1 - kCullRel), rounded up (render_kernel.inc wave_near)
+    // K' = (k + R + margin) / (1 - kCullRel), rounded up (scenes.inc wave_near)
     a.bound[i][3] = float((k + R + margin) / (1.0 - sdf::kCullRel) * (1.0 + 1e-6));
     // exact kernel (the prepared block's `reserved`, unused there): the
     // offset of the gap an evaluated primitive's own value leaves in the
-    // culling cache, k + margin + 1e-4 R (render_kernel.inc step_cached),
+    // culling cache, k + margin + 1e-4 R (scenes.inc step_cached),
     // rounded up
     if (exact && sdf::cullable(kind, pr.op))
       a.prims[i].reserved = float((k + margin + 1e-4 * R) * (1.0 + 1e-6));
@@ -389,7 +389,7 @@ namespace {
 // 1e15 in magnitude (and capsules of positive length), so that no square,
 // dot product or distance the scene evaluation forms overflows -- every
 // primitive value is then finite and the accumulated scene distance is never
-// NaN, which the exact kernel's hardware minimum relies on (render_kernel.inc
+// NaN, which the exact kernel's hardware minimum relies on (prims.inc
 // smin<HW>).
 constexpr float kMaxCoord = 1e15f;
 constexpr float kMinCapsule2 = 0x1p-30f;
@@ -444,14 +444,14 @@ int validate_scene(const sdf_scene& scene) {
       if (pr.kind < 0 || pr.kind >= SDF_PRIM_KIND_COUNT) return SDF_E_INVALID_ARG;
       if (pr.op < 0 || pr.op >= SDF_OP_COUNT) return SDF_E_INVALID_ARG;
       // a smooth blend radius in [2^-64, 1e15]: the exact smooth-min's
-      // h h (k/4) relies on the lower end (render_kernel.inc smin)
+      // h h (k/4) relies on the lower end (prims.inc smin)
       if (smooth_op(pr.op) && !(pr.k >= 0x1p-64f && pr.k <= kMaxCoord)) return SDF_E_INVALID_ARG;
       for (float v : pr.p)
         if (!std::isfinite(v) || std::fabs(v) > kMaxCoord) return SDF_E_INVALID_ARG;
       if (pr.kind == SDF_PRIM_CAPSULE) {
         // a segment of length in [2^-15, 2^15): dot(ba, ba), computed as the
         // kernels do, in [2^-30, 2^30) -- the exact kernel's Markstein
-        // division of h = dot(pa, ba) / dot(ba, ba) (render_kernel.inc
+        // division of h = dot(pa, ba) / dot(ba, ba) (prims.inc
         // sd_capsule) needs its divisor there
         const float bax = pr.p[3] - pr.p[0], bay = pr.p[4] - pr.p[1], baz = pr.p[5] - pr.p[2];
         const float baba = bax * bax + bay * bay + baz * baz;
@@ -471,7 +471,7 @@ int validate_scene(const sdf_scene& scene) {
   if (scene.bulb_iterations < 1 || scene.bulb_iterations > 64) return SDF_E_INVALID_ARG;
   // bailout in (0, 2^32]: its square stays finite, so every iteration's
   // x^2 + z^2 <= m <= bailout^2 is finite (the exact kernel's 1 / sqrt of it,
-  // render_kernel.inc frsqrt, relies on that)
+  // kmath.inc frsqrt, relies on that)
   if (!(scene.bulb_bailout > 0.0f && scene.bulb_bailout <= 4294967296.0f))
     return SDF_E_INVALID_ARG;
   return SDF_OK;
@@ -723,7 +723,7 @@ static void plan_scene(const sdf_scene& scene, const sdf_light& light,
     const float tt = a.ao_taps > 1 ? (float)i / (float)(a.ao_taps - 1) : 0.0f;
     a.ao_h[i] = params.ao_base + params.ao_step * tt;
   }
-  // the AO taps' path lengths from P, visited in order (render_kernel.inc):
+  // the AO taps' path lengths from P, visited in order (trace.inc trace_shape):
   // |h_0| + sum |h_k - h_(k-1)|, rounded up to fp32 so it never undercounts
   {
     double path = 0.0;

@@ -52,7 +52,7 @@ enum TilesShade : uint32_t {
 // per 4K frame, tiles.hip.)
 // The library fp64 pow, out of line (SDF_SHADE_POW_CALL 1): inlined, its
 // ~30 fp64 constants were hoisted out of the persistent frames kernel's tile
-// loop (render_kernel.inc render_frames) and spilled to scratch; as a call
+// loop (render_entry.inc render_frames) and spilled to scratch; as a call
 // they exist only on the rare lanes that need it.
 #if !defined(SDF_SHADE_POW_CALL) || SDF_SHADE_POW_CALL
 inline __device__ __attribute__((noinline)) float library_pow(float x, float y) {

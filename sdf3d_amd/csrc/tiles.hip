@@ -1,5 +1,5 @@
 // tiles.hip -- the TILES wire format (sdf_abi.h SDF_FORMAT_TILES) around the
-// render kernel's encoder (render_kernel.inc store_tiles):
+// render kernel's encoder (store.inc store_tiles):
 //
 //   compaction  the encoder leaves each tile's words in a fixed worst-case
 //               slot and its head (base widths, raw first pixel) in place;

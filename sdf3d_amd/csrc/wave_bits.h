@@ -1,5 +1,5 @@
 // wave_bits.h -- wave64 bit-matrix transpose shared by the TILES encoder
-// (render_kernel.inc store_tiles) and decoder (tiles.hip decode_tiles).
+// (store.inc store_tiles) and decoder (tiles.hip decode_tiles).
 //
 // Transpose of the 64 x 64 bit matrix whose row r is lane r's word (lo =
 // bits 0..31, hi = 32..63): on return lane c holds column c (bit r = bit c

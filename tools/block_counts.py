@@ -378,25 +378,33 @@ def cmd_run(a):
 
 # ---- report ---------------------------------------------------------------------
 
-# shade_pixel's stages: render_kernel.inc line ranges found from anchors in
-# its source (so the table follows edits of the file)
+# A pixel's stages: (file, first line, last line) ranges of the device sources
+# (build.py KERNEL_SOURCES), found from anchors in their text, so the table
+# follows edits and moves.  The anchors lie in this order; a stage runs from its
+# anchor to the end of the function it is in, or to the next anchor if that
+# comes first.
 ANCHORS = [("// quad = ((2x+1)/W - 1,", "setup: quad, ray"), ("// raymarch, :86-103", "primary march"),
            ("// normal, :134-155", "normal"), ("// ambient occlusion (extension)", "AO"),
            ("// Blinn-Phong, :200-204", "Blinn-Phong"), ("// soft shadow, :105-132", "shadow setup"),
            ("tlim = scene.shadow_limit(", "shadow lit-tail setup"), ("if (!lit)", "shadow march"),
-           ("const float dif = gclamp(ndl", "colour terms")]
+           ("dif_out = gclamp(ndl", "colour terms")]
 
 
 def _stages():
-    lines = (ROOT / "sdf3d_amd" / "csrc" / "render_kernel.inc").read_text().split("\n")
-    start = next(i for i, l in enumerate(lines) if "__device__ __forceinline__ float4 shade_pixel(" in l)
-    marks = []
+    from sdf3d_amd import build as B
+    files = [(p.name, p.read_text().split("\n")) for _, p in B.KERNEL_SOURCES]
+    marks, f, i = [], 0, 0
     for key, name in ANCHORS:
-        i = next(j for j in range(start, len(lines)) if key in lines[j])
-        marks.append((i + 1, name))
-    end = next(j for j in range(start, len(lines)) if lines[j].startswith("}")) + 1
-    return [(a, (marks[k + 1][0] - 1) if k + 1 < len(marks) else end, name)
-            for k, (a, name) in enumerate(marks)]
+        f, i = next((g, j) for g in range(f, len(files))
+                    for j in range(i if g == f else 0, len(files[g][1])) if key in files[g][1][j])
+        marks.append((f, i, name))
+    out = []
+    for k, (f, i, name) in enumerate(marks):
+        last = next(j for j in range(i, len(files[f][1])) if files[f][1][j].startswith("}")) + 1
+        if k + 1 < len(marks) and marks[k + 1][0] == f:
+            last = min(last, marks[k + 1][1])
+        out.append((files[f][0], i + 1, last, name))
+    return out
 
 
 STAGES = None
@@ -406,13 +414,14 @@ def stage(stack) -> str:
     global STAGES
     if STAGES is None:
         STAGES = _stages()
+    for _, loc in stack:   # leaf first: the innermost frame that lies in a stage
+        file, _, ln = loc.partition(":")
+        for f, a, b, name in STAGES:
+            if file == f and ln.isdigit() and a <= int(ln) <= b:
+                return name
     for fn, loc in stack:
-        if fn.startswith("shade_pixel") and loc.startswith("render_kernel.inc:"):
-            ln = int(loc.split(":")[1])
-            for a, b, name in STAGES:
-                if a <= ln <= b:
-                    return name
-            return f"shade_pixel:{ln}"
+        if fn.startswith("shade_pixel"):
+            return f"shade_pixel {loc}"
     for fn, _ in stack:
         if fn.startswith(("render_body", "store_pixel", "pixel_value", "shade_colour")):
             return "store / index"
