@@ -9,6 +9,7 @@
 //            [--pick X,Y] [--projection pinhole|equirect]
 //            [--mesh FILE.obj|FILE.ply --grid x0,y0,z0,x1,y1,z1,N [--mesh-colors]
 //             [--mesh-sharp [R,K]]]
+//            [--measure x0,y0,z0,x1,y1,z1,N [--density d0,d1,...]]
 //            [width height frames out.ppm scene [samples [lights]]]
 //     scene: ref | csg8 | bulb; samples: 1 (default), 2 or 4 sub-samples per
 //     axis, resolved in the render kernel (single-GPU path only: the frame
@@ -56,6 +57,13 @@
 //     R refinement steps per crossing and K steps of the fit, 4,16 when not
 //     given; not for a Mandelbulb).  --palette stays the switch it is above: it
 //     takes no count, the palette has one entry per primitive
+//     --measure x0,y0,z0,x1,y1,z1,N [--density d0,d1,...] (anywhere on the line):
+//     after the last frame, one JSON line with the volume, mass, centroid, inertia
+//     tensor about the centroid and bounds of the solid inside the box, N cells
+//     per axis (sdf::measure: sdf_measure; single-GPU path only), and the bricks
+//     evaluated, taken in closed form and in all.  --density gives a density per
+//     primitive (in list order; a ground plane gets 0 to be left out): mass,
+//     centroid and inertia are then the weighted ones; without it the density is 1
 //
 // Multi-GPU: launched once per GPU by any launcher that sets RANK,
 // WORLD_SIZE and LOCAL_RANK (e.g. `torchrun --nproc-per-node 8 --no-python
@@ -232,6 +240,9 @@ int main(int argc, char** argv) {
   bool mesh_colors = false;
   sdf_mesh_sharp mesh_sharp = {0, 0, 0, 0};   // --mesh-sharp [R,K]
   bool use_mesh_sharp = false;
+  double measure_box[6] = {0, 0, 0, 0, 0, 0};   // --measure x0,y0,z0,x1,y1,z1,N
+  int measure_n = 0;
+  std::vector<double> densities;                // --density d0,d1,...
   int pick_x = 0, pick_y = 0;
   sdf_reflect reflect = {0, 1.0f, -1, 0};
   sdf_environment environment = sdf::sky(0);
@@ -290,6 +301,29 @@ int main(int argc, char** argv) {
           std::fprintf(stderr, "sdf_main: --grid x0,y0,z0,x1,y1,z1,N\n");
           return 1;
         }
+      } else if (std::string(argv[i]) == "--measure") {
+        char tail = 0;
+        double* b = measure_box;
+        if (!(i + 1 < argc && std::sscanf(argv[++i], "%lf,%lf,%lf,%lf,%lf,%lf,%d%c", &b[0], &b[1], &b[2],
+                                          &b[3], &b[4], &b[5], &measure_n, &tail) == 7 &&
+              measure_n >= 1)) {
+          std::fprintf(stderr, "sdf_main: --measure x0,y0,z0,x1,y1,z1,N\n");
+          return 1;
+        }
+      } else if (std::string(argv[i]) == "--density") {
+        const char* p = i + 1 < argc ? argv[++i] : "";
+        char* end = nullptr;
+        for (;;) {
+          const double d = std::strtod(p, &end);
+          if (end == p) break;
+          densities.push_back(d);
+          if (*end != ',') break;
+          p = end + 1;
+        }
+        if (densities.empty() || *end != '\0' || densities.size() > SDF_MAX_PRIMS) {
+          std::fprintf(stderr, "sdf_main: --density d0,d1,... (at most %d)\n", SDF_MAX_PRIMS);
+          return 1;
+        }
       } else if (std::string(argv[i]) == "--projection") {
         projection = i + 1 < argc ? argv[++i] : "";
         if (projection != "pinhole" && projection != "equirect") {
@@ -333,6 +367,10 @@ int main(int argc, char** argv) {
     }
     if ((mesh_colors || use_mesh_sharp) && mesh_path.empty()) {
       std::fprintf(stderr, "sdf_main: --mesh-colors and --mesh-sharp need --mesh FILE --grid ...\n");
+      return 1;
+    }
+    if (!densities.empty() && measure_n == 0) {
+      std::fprintf(stderr, "sdf_main: --density needs --measure x0,y0,z0,x1,y1,z1,N\n");
       return 1;
     }
     if (no_sun) environment.flags &= ~SDF_ENV_SUN;
@@ -464,6 +502,35 @@ int main(int argc, char** argv) {
       std::printf("mesh: %lld vertices, %lld triangles, %lld of %lld bricks evaluated; wrote %s\n",
                   (long long)m.counts[0], (long long)m.counts[1], (long long)m.counts[2],
                   (long long)m.counts[3], mesh_path.c_str());
+    }
+    if (measure_n > 0) {
+      // one JSON line: the solid inside the box on N cells per axis (sdf::measure);
+      // with --density a density per primitive weighs mass, centroid and inertia
+      const double lo[3] = {measure_box[0], measure_box[1], measure_box[2]},
+                   hi[3] = {measure_box[3], measure_box[4], measure_box[5]};
+      const sdf::Measure m = sdf::measure(f, sdf::box_grid(lo, hi, measure_n), !densities.empty(), stream);
+      double c[3], I[3][3], blo[3], bhi[3];
+      const double mass = densities.empty() ? m.volume() : m.mass(densities);
+      std::printf("{\"measure\": {\"volume\": %.17g, \"mass\": %.17g, ", m.volume(), mass);
+      // nothing weighs anything (an empty solid, densities of 0): no centroid and no
+      // inertia, null as the bounds of an empty solid are (0 / 0 is no JSON number)
+      if (m.moments(densities).m0 != 0.0) {
+        m.centroid(c, densities);
+        m.inertia(I, 1.0, densities);
+        std::printf("\"centroid\": [%.17g, %.17g, %.17g], "
+                    "\"inertia\": [[%.17g, %.17g, %.17g], [%.17g, %.17g, %.17g], [%.17g, %.17g, %.17g]], ",
+                    c[0], c[1], c[2], I[0][0], I[0][1], I[0][2], I[1][0], I[1][1], I[1][2], I[2][0],
+                    I[2][1], I[2][2]);
+      } else {
+        std::printf("\"centroid\": null, \"inertia\": null, ");
+      }
+      if (m.bounds(blo, bhi))
+        std::printf("\"bounds\": [[%.17g, %.17g, %.17g], [%.17g, %.17g, %.17g]], ", blo[0], blo[1], blo[2],
+                    bhi[0], bhi[1], bhi[2]);
+      else
+        std::printf("\"bounds\": null, ");
+      std::printf("\"bricks\": {\"evaluated\": %lld, \"closed_form\": %lld, \"all\": %lld}}}\n",
+                  (long long)m.counts[0], (long long)m.counts[1], (long long)m.counts[2]);
     }
     (void)hipEventDestroy(t0);
     (void)hipEventDestroy(t1);

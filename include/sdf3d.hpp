@@ -608,6 +608,137 @@ inline sdf_grid box_grid(const double (&lo)[3], const double (&hi)[3], int n, fl
   g.iso = iso;
   return g;
 }
+// ---- measures (sdf_abi.h "Measures") ---------------------------------------------
+// The integer rows of sdf_measure on the host, with the header's fp64
+// conversions over the lattice coordinates origin + (i + 1/2) cell.  Row 0 is
+// the whole solid; with owners, row 1 + k the samples primitive k owns.
+struct Moments {
+  double m0, m1[3], m2[3][3];   // sums of w, w i_c, w i_c i_d
+};
+struct Measure {
+  std::vector<int64_t> rows;    // 16 per row: one row, or 17 with owners
+  int64_t counts[4];            // bricks evaluated, in closed form, in all, 0
+  double origin[3], cell[3];
+  int32_t n[3];
+
+  bool owners() const { return rows.size() == size_t(SDF_MEASURE_ROWS) * SDF_MEASURE_SLOTS; }
+  double cell_volume() const { return cell[0] * cell[1] * cell[2]; }
+  static void add_row(Moments& m, const int64_t* r, double w) {
+    static const int pair[6][2] = {{0, 0}, {1, 1}, {2, 2}, {0, 1}, {0, 2}, {1, 2}};
+    m.m0 += w * double(r[0]);
+    for (int c = 0; c < 3; ++c) m.m1[c] += w * double(r[1 + c]);
+    for (int s = 0; s < 6; ++s) {
+      m.m2[pair[s][0]][pair[s][1]] += w * double(r[4 + s]);
+      if (pair[s][0] != pair[s][1]) m.m2[pair[s][1]][pair[s][0]] += w * double(r[4 + s]);
+    }
+  }
+  // row 0's raw moments; with densities sum_k rho_k (N_k, S_k, Q_k) over the owner rows
+  Moments moments(const std::vector<double>& densities = {}) const {
+    Moments m{};
+    if (densities.empty()) {
+      add_row(m, rows.data(), 1.0);
+      return m;
+    }
+    if (!owners() || densities.size() > size_t(SDF_MAX_PRIMS))
+      throw Error(SDF_E_INVALID_ARG, "Measure: densities need the owner rows");
+    for (size_t k = 0; k < densities.size(); ++k)
+      add_row(m, rows.data() + (1 + k) * SDF_MEASURE_SLOTS, densities[k]);
+    return m;
+  }
+  double volume() const { return double(rows[0]) * cell_volume(); }
+  double mass(const std::vector<double>& densities) const {
+    return moments(densities).m0 * cell_volume();
+  }
+  void centroid(double (&out)[3], const std::vector<double>& densities = {}) const {
+    const Moments m = moments(densities);
+    for (int c = 0; c < 3; ++c) out[c] = origin[c] + (m.m1[c] / m.m0 + 0.5) * cell[c];
+  }
+  // (every helper evaluates in the order of sdf3d_amd/measure.py, operation for
+  // operation, so the two give the same fp64 bits)
+  void covariance(double (&out)[3][3], const std::vector<double>& densities = {}) const {
+    const Moments m = moments(densities);
+    for (int c = 0; c < 3; ++c)
+      for (int d = 0; d < 3; ++d)
+        out[c][d] = (m.m2[c][d] / m.m0 - (m.m1[c] / m.m0) * (m.m1[d] / m.m0)) * (cell[c] * cell[d]) +
+                    (c == d ? cell[c] * cell[c] / 12.0 : 0.0);
+  }
+  // about the centroid: mass (tr(C) Id - C), the mass density * volume or mass(densities)
+  void inertia(double (&out)[3][3], double density = 1.0,
+               const std::vector<double>& densities = {}) const {
+    double cv[3][3];
+    covariance(cv, densities);
+    const double ms = densities.empty() ? density * volume() : mass(densities);
+    const double tr = cv[0][0] + cv[1][1] + cv[2][2];
+    for (int c = 0; c < 3; ++c)
+      for (int d = 0; d < 3; ++d) out[c][d] = ms * ((c == d ? tr : 0.0) - cv[c][d]);
+  }
+  // the cells row 0 occupies; false for an empty set
+  bool bounds(double (&lo)[3], double (&hi)[3]) const {
+    if (rows[0] == 0) return false;
+    for (int c = 0; c < 3; ++c) {
+      lo[c] = origin[c] + double(rows[10 + c]) * cell[c];
+      hi[c] = origin[c] + double(rows[13 + c] + 1) * cell[c];
+    }
+    return true;
+  }
+  // the measure whose row 0 combines the owner rows of `prims`
+  Measure select(const std::vector<int>& prims) const {
+    if (!owners()) throw Error(SDF_E_INVALID_ARG, "Measure: select needs the owner rows");
+    Measure r = *this;
+    r.rows.assign(SDF_MEASURE_SLOTS, 0);
+    for (int c = 0; c < 3; ++c) {
+      r.rows[10 + c] = n[c];
+      r.rows[13 + c] = -1;
+    }
+    std::vector<bool> seen(SDF_MAX_PRIMS, false);
+    for (int k : prims) {
+      if (k < 0 || k >= SDF_MAX_PRIMS) throw Error(SDF_E_INVALID_ARG, "Measure: no such primitive");
+      if (seen[k]) continue;
+      seen[k] = true;
+      const int64_t* q = rows.data() + (1 + k) * SDF_MEASURE_SLOTS;
+      for (int j = 0; j < 10; ++j) r.rows[j] += q[j];
+      for (int j = 10; j < 13; ++j) r.rows[j] = std::min(r.rows[j], q[j]);
+      for (int j = 13; j < 16; ++j) r.rows[j] = std::max(r.rows[j], q[j]);
+    }
+    return r;
+  }
+};
+// sdf_measure of the frame's scene on `grid`, and the copies back.  Blocking.
+inline Measure measure(const Frame& f, const sdf_grid& grid, bool owners = false,
+                       hipStream_t stream = nullptr) {
+  check_abi();
+  const int32_t flags = owners ? SDF_MEASURE_OWNERS : 0;
+  check(sdf_validate_measure(&f.scene, &f.params, &grid, flags), "sdf_validate_measure");
+  const int64_t bytes = sdf_measure_workspace_bytes(&grid, flags);
+  if (bytes < 0) check(static_cast<int>(bytes), "sdf_measure_workspace_bytes");
+  Measure m{};
+  const size_t nrows = owners ? SDF_MEASURE_ROWS : 1, out_bytes = nrows * SDF_MEASURE_SLOTS * 8;
+  m.rows.resize(nrows * SDF_MEASURE_SLOTS);
+  for (int c = 0; c < 3; ++c) {
+    m.origin[c] = grid.origin[c];
+    m.cell[c] = grid.cell[c];
+    m.n[c] = grid.n[c];
+  }
+  char *ws = nullptr, *out = nullptr;   // out: moments | counts
+  int rc = SDF_OK;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&ws), size_t(bytes));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&out), out_bytes + 32);
+  if (e == hipSuccess) {
+    rc = sdf_measure(&f.scene, &f.params, &grid, flags, ws, bytes, reinterpret_cast<int64_t*>(out),
+                     reinterpret_cast<int64_t*>(out + out_bytes), stream);
+    if (rc == SDF_OK) e = hipStreamSynchronize(stream);
+    if (rc == SDF_OK && e == hipSuccess)
+      e = hipMemcpy(m.rows.data(), out, out_bytes, hipMemcpyDeviceToHost);
+    if (rc == SDF_OK && e == hipSuccess)
+      e = hipMemcpy(m.counts, out + out_bytes, 32, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(out);
+  (void)hipFree(ws);
+  check(rc, "sdf_measure");
+  check_hip(e, "measure");
+  return m;
+}
+
 // A Wavefront OBJ file of the mesh: 1-based indices, `vn` lines when the mesh
 // has normals (sdf3d_amd/meshio.py reads it back).  `colors` (4 floats per
 // vertex, as bake returns them; empty: none): every `v` line carries r g b

@@ -299,6 +299,11 @@ typedef struct {
   float* grad_prims;   /* device, SDF_MAX_PRIMS * 16 floats, optional (layout below)    */
 } sdf_grad_out;        /* 24 bytes; at least one pointer non-NULL */
 
+/* Measures (sdf_measure; "Measures" below) */
+#define SDF_MEASURE_OWNERS 0x1      /* rows 1 + k: the inside samples primitive k owns */
+#define SDF_MEASURE_SLOTS  16       /* int64 per row */
+#define SDF_MEASURE_ROWS   (1 + SDF_MAX_PRIMS)
+
 /* Render flags */
 #define SDF_FLAG_SHADOW    0x1  /* soft shadow march (voxel_fragment.frag:205) */
 #define SDF_FLAG_AO         0x2  /* ambient occlusion (extension)               */
@@ -996,6 +1001,81 @@ typedef struct {
  *     Mandelbulb, per-point (unreduced) parameter gradients and several devices
  *     are not offered. */
 
+/* Measures (sdf_measure: how much solid the scene holds inside a regular grid,
+ * where its centre of mass lies, what its inertia is and what box it occupies
+ * -- the questions behind export, printing, collision and optimising a CSG
+ * design; the box also places the grid of a mesh).  The grid is the sdf_grid of
+ * "Meshes"; the solid is f(p) < iso.  Every output is an exact sum (or a minimum
+ * or maximum) of integer sample indices, so it does not depend on the order of
+ * summation, and exact precision can be checked bit for bit
+ * (tests/measure_ref.py states it in NumPy over the CPU oracle):
+ *   - samples: one per cell of the grid, at the cell's centre.  Sample (i0, i1,
+ *     i2), 0 <= i_c < n[c], lies at p.c = RN(origin[c] + RN(((float)i_c + 0.5f)
+ *     cell[c])); the sum (float)i_c + 0.5f is exact.  w = RN(f(p) - iso), f bit for
+ *     bit what sdf_sample returns for p with this scene, precision and dispatch.
+ *     A sample is inside iff w < 0: a NaN or a zero is outside, as in "Meshes".
+ *   - a row is SDF_MEASURE_SLOTS = 16 int64 over a set of inside samples:
+ *       slot 0        N, the number of samples                     (empty set: 0)
+ *       slots 1..3    S_c = the sum of i_c                                     (0)
+ *       slots 4..9    Q = the sums of i0 i0, i1 i1, i2 i2, i0 i1, i0 i2, i1 i2  (0)
+ *       slots 10..12  lo_c = the smallest i_c                               (n[c])
+ *       slots 13..15  hi_c = the largest i_c                                  (-1)
+ *   - rows: row 0 covers all inside samples.  With SDF_MEASURE_OWNERS, row 1 + k
+ *     (k = 0 .. SDF_MAX_PRIMS - 1) covers the inside samples whose owner is
+ *     primitive k: the owner fold of "Queries" at p, 0 for a Mandelbulb.  Rows of
+ *     primitives >= scene->count are empty rows.  With the flag `moments` holds
+ *     all SDF_MEASURE_ROWS = 17 rows, without it row 0 alone; every slot of every
+ *     row is written by every call.  A scene with a ground plane fills the grid
+ *     below the plane: the owner rows are how a caller leaves the plane out, and
+ *     how a density per primitive becomes a mass.
+ *   - counts (device, 4 int64): [0] bricks whose samples were evaluated, [1]
+ *     bricks taken in closed form (proven inside throughout), [2] bricks in all,
+ *     [3] 0.
+ *   - skipping: bricks are those of "Meshes", 8 x 8 x 8 cells in the same
+ *     numbering, and the test is the mesh's, at the mesh's centre point (lattice
+ *     point 8 b + 4) against the same bound: the proof (sdf3d_amd/csrc/
+ *     mesh_kernel.inc) covers the cell centres of the brick too
+ *     (measure_kernel.inc).  A brick proven outside contributes nothing.  A brick
+ *     proven inside contributes, without SDF_MEASURE_OWNERS, the closed-form sums
+ *     over its index box inside the grid; with the flag it is evaluated, because
+ *     owners vary inside it.  The result is bit for bit the same with and without
+ *     skipping; SDF_MESH_DENSE in grid->flags evaluates every brick.  A
+ *     Mandelbulb, and a grid or scene beyond the proof's range, always run dense,
+ *     as "Meshes" says.
+ *   - limits: n[c] <= 65536 per axis on top of sdf_validate_mesh's checks; with
+ *     at most 2^30 cells every slot and every partial sum stays below 2^62.
+ *   - workspace: device memory, 16-byte aligned; with B bricks and R = 17 rows
+ *     with SDF_MEASURE_OWNERS, else 1: sdf_measure_workspace_bytes = 8 min(B, 4096)
+ *     (16 R + 4) (the launch is grid-stride over a capped number of workgroups, and
+ *     each writes its rows once; a second kernel combines them -- no atomics, no
+ *     initialisation).  It needs no initialisation and its contents after the
+ *     call are unspecified.
+ *   - params and dispatch: as "Meshes" (under SDF_DISPATCH_AUTO one run-time
+ *     specialised kernel per signature, precision and flag, a family of its own
+ *     counted by sdf_jit_count; GENERIC and UNCULLED as there).
+ *   - SDF_E_INVALID_ARG, decided before any device call (sdf_validate_measure is
+ *     that check of scene, params, grid and flags): everything sdf_validate_mesh
+ *     rejects; n[c] > 65536; unknown flag bits; moments or counts NULL; a
+ *     workspace that is NULL, not 16-byte aligned or smaller than
+ *     sdf_measure_workspace_bytes.
+ *   - host conversion, in fp64 over the real-valued lattice coordinates origin +
+ *     (i + 1/2) cell (not over the rounded fp32 sample positions), with c_c =
+ *     cell[c], for a row with N > 0:
+ *       volume      = N c0 c1 c2
+ *       centroid_c  = origin_c + (S_c / N + 1/2) c_c
+ *       covariance  C_cd = (Q_cd / N - (S_c / N)(S_d / N)) c_c c_d + [c = d] c_c^2 / 12
+ *       inertia about the centroid = mass (tr(C) Id - C)
+ *       bounds      = [origin + lo c, origin + (hi + 1) c]
+ *     With a density rho_k per primitive the raw moments of the owner rows are
+ *     combined first, sum_k rho_k (N_k, S_k, Q_k), and the same formulas follow
+ *     (mass = sum_k rho_k N_k c0 c1 c2).
+ *   - asynchronous on `stream`.  No loop bound and no address depends on a
+ *     sampled value.  SDF_ABI_VERSION stays 12: detect the entry point by the
+ *     symbol.
+ *   - surface area (sum the mesh's triangles), partial-cell occupancy or sub-cell
+ *     sampling (pass a finer grid), several devices and gradients of the
+ *     measures are not offered. */
+
 /* Framebuffer element formats (4 channels R,G,B,A per pixel).
  *   RGBA32F  the shader's float fragment_color (voxel_fragment.frag:12,210).
  *   RGBA16F  IEEE half, round to nearest even.
@@ -1321,6 +1401,18 @@ int sdf_sample_grad(const sdf_scene* scene, const sdf_params* params, const floa
                     int64_t n, const float* upstream /* device, n; NULL: every g_i = 1 */,
                     const sdf_grad_out* out, void* workspace, int64_t workspace_bytes,
                     void* stream);
+
+/* Measures ("Measures" above).  Additions: SDF_ABI_VERSION stays 12, detect
+ * them by the symbol.  sdf_validate_measure is the host-only check of scene,
+ * params, grid and flags (no device call); sdf_measure_workspace_bytes the size
+ * of the workspace of `grid` under `flags`, or a negative SDF_E* code. */
+int sdf_validate_measure(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
+                         int32_t flags);
+int64_t sdf_measure_workspace_bytes(const sdf_grid* grid, int32_t flags);
+int sdf_measure(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
+                int32_t flags /* SDF_MEASURE_* */, void* workspace, int64_t workspace_bytes,
+                int64_t* moments /* device, rows x 16 */, int64_t* counts /* device, 4 */,
+                void* stream);
 
 /* Scatter `nparts` packed row-block buffers (part r = rank r's output for
  * tiling {block_rows, r, nparts}), laid out back to back in `parts` with a

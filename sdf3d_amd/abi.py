@@ -23,6 +23,10 @@ ENV_FOG = 0x4         # SDF_ENV_FOG: linear distance fog on every layer that is 
 RAYS_UNIT = 0x1       # SDF_RAYS_UNIT: sdf_render_rays uses dirs as given (unit vectors)
 POINTS_EYE = 0x1      # SDF_POINTS_EYE: sdf_shade_points evaluates the specular term from `eye`
 MESH_DENSE = 0x1      # SDF_MESH_DENSE: sdf_mesh_count evaluates every brick (no skipping)
+MEASURE_OWNERS = 0x1  # SDF_MEASURE_OWNERS: sdf_measure also writes a row per owning primitive
+MEASURE_SLOTS = 16    # SDF_MEASURE_SLOTS: int64 per row of sdf_measure
+MEASURE_ROWS = 17     # SDF_MEASURE_ROWS: row 0 and a row per primitive
+MEASURE_MAX_BLOCKS = 4096   # the workgroups of an sdf_measure launch at most (its workspace formula)
 
 # status codes
 SDF_OK = 0
@@ -262,6 +266,10 @@ SIGNATURES = {
     "sdf_mesh_emit_sharp": (C.c_int, [_P(sdf_scene), _P(sdf_params), _P(sdf_grid),
                                       _P(sdf_mesh_sharp), C.c_void_p, C.c_int64, _P(sdf_mesh_out),
                                       C.c_void_p]),
+    "sdf_validate_measure": (C.c_int, [_P(sdf_scene), _P(sdf_params), _P(sdf_grid), C.c_int32]),
+    "sdf_measure_workspace_bytes": (C.c_int64, [_P(sdf_grid), C.c_int32]),
+    "sdf_measure": (C.c_int, [_P(sdf_scene), _P(sdf_params), _P(sdf_grid), C.c_int32, C.c_void_p,
+                              C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sdf_validate_grad": (C.c_int, [_P(sdf_scene), _P(sdf_params)]),
     "sdf_grad_workspace_bytes": (C.c_int64, [C.c_int64]),
     "sdf_sample_grad": (C.c_int, [_P(sdf_scene), _P(sdf_params), C.c_void_p, C.c_int64,

@@ -92,7 +92,7 @@ KERNEL_SOURCES = [(n, Path(os.path.normpath(CSRC / n))) for n in (
     "render_kernel.inc", "kernel_args.h", "../../include/sdf_abi.h", "wave_bits.h", "shade.h",
     "cr_math.h", "kmath.inc", "prims.inc", "store.inc", "scenes.inc", "trace.inc",
     "pixel_paths.inc", "render_entry.inc", "query_kernel.inc", "grad_kernel.inc",
-    "mesh_kernel.inc", "rays_kernel.inc", "points_kernel.inc", "jit_entry.inc")]
+    "mesh_kernel.inc", "measure_kernel.inc", "rays_kernel.inc", "points_kernel.inc", "jit_entry.inc")]
 HEADERS = [p for _, p in KERNEL_SOURCES] + [CSRC / "host_api.h", CSRC / "render_launch.inc",
                                             CSRC / "turbo_lut.inc"]
 

@@ -120,6 +120,7 @@ struct RenderUnit {
   int (*rays)(const RaysArgs& q, int variant, void* stream);     // sdf_render_rays
   int (*mesh)(const MeshArgs& m, int variant, void* stream, int kind);   // a MeshKind
   int (*points)(const PointsArgs& q, int variant, void* stream);   // sdf_shade_points
+  int (*measure)(const MeasureArgs& m, int variant, void* stream);   // sdf_measure, by m.owners
   // one kernel each, in the units of the primitive scenes alone (null in the
   // Mandelbulb's): the ray generator of sdf_camera_rays, and the gradient
   // kernel followed by grad_reduce into `grad_prims`
@@ -143,6 +144,7 @@ int launch_query_jit(const QueryArgs& q, const RenderPlan& plan, void* stream);
 int launch_rays_jit(const RaysArgs& q, const RenderPlan& plan, void* stream);
 int launch_mesh_jit(const MeshArgs& m, const RenderPlan& plan, void* stream, int kind);
 int launch_points_jit(const PointsArgs& q, const RenderPlan& plan, void* stream);
+int launch_measure_jit(const MeasureArgs& m, const RenderPlan& plan, void* stream);
 int jit_compiled_count();
 
 // One kernel launch for a prepared scene, through the built-in kernel of the
@@ -172,6 +174,10 @@ int launch_planned(const RenderPlan& plan, int (*jit)(const Args&, const RenderP
 // the scan over the bricks' counts (mesh.hip): offsets per brick into the
 // workspace, the totals into counts[0..3] (device)
 int launch_mesh_scan(unsigned char* ws, long long nbricks, long long* counts, void* stream);
+// the combination of the measure kernel's records (mesh.hip): `rows` rows into
+// moments, the bricks' counts into counts[0..3] (device)
+int launch_measure_reduce(const long long* ws, int nblocks, int rows, long long nbricks,
+                          long long* moments, long long* counts, void* stream);
 int launch_deinterleave(const void* parts, int nparts, int part_stride_rows, int row_bytes,
                         int height, int block_rows, void* frame, void* stream);
 int launch_deinterleave_rgb(const void* parts, int nparts, int part_stride_rows, int width,
@@ -312,5 +318,19 @@ inline bool mesh_sharp_args_fit(const MeshArgs& m) {
          m.a.prim_count <= SDF_MAX_PRIMS;
 }
 inline dim3 mesh_grid(const MeshArgs& m) { return dim3((unsigned)m.nbricks); }
+
+// ---- the measure kernels' launch geometry and argument contract -------------
+// Shared by launch_measure_scene and launch_measure_jit.  Grid-stride, one wave
+// per workgroup, a record of the workspace per workgroup: the sizes the
+// kernel's index arithmetic and its 64-bit sums are proven for.
+inline bool measure_args_fit(const MeasureArgs& m) {
+  long long bricks = 1;
+  for (int c = 0; c < 3; ++c) {
+    if (m.n[c] < 1 || m.n[c] > 65536 || m.nb[c] != (m.n[c] + 7) / 8) return false;
+    bricks *= m.nb[c];
+  }
+  return m.nbricks == bricks && m.ws && (m.owners & ~SDF_MEASURE_OWNERS) == 0;
+}
+inline dim3 measure_grid(const MeasureArgs& m) { return dim3((unsigned)measure_blocks(m.nbricks)); }
 
 }  // namespace sdf

@@ -17,6 +17,8 @@
 //     SDF_JIT_RAYS     sdf_jit_rays: rays_body with SDF_JIT_STEPS, SDF_JIT_ENV
 //     SDF_JIT_MESH     sdf_jit_mesh: mesh_body of the MeshKind it expands to
 //     SDF_JIT_POINTS   sdf_jit_points: points_body with SDF_JIT_STEPS
+//     SDF_JIT_MEASURE  sdf_jit_measure: measure_body, with the owner rows when it
+//                      expands to true
 //   SDF_JIT_<flag>     true | false, each of the seven above (a family reads
 //                      its own and ignores the rest)
 // A signature is a primitive list, so the rays and points entries fold.
@@ -34,6 +36,8 @@ extern "C" SDF_RAYS_KERNEL(sdf_jit_rays, JitScene, SDF_JIT_STEPS, true, SDF_JIT_
 extern "C" SDF_MESH_KERNEL(sdf_jit_mesh, JitScene, SDF_JIT_MESH)
 #elif defined(SDF_JIT_POINTS)
 extern "C" SDF_POINTS_KERNEL(sdf_jit_points, JitScene, SDF_JIT_STEPS, true)
+#elif defined(SDF_JIT_MEASURE)
+extern "C" SDF_MEASURE_KERNEL(sdf_jit_measure, JitScene, SDF_JIT_MEASURE)
 #else
-#error "a run-time unit names its family: SDF_JIT_RENDER, _QUERY, _RAYS, _MESH or _POINTS"
+#error "a run-time unit names its family: SDF_JIT_RENDER, _QUERY, _RAYS, _MESH, _POINTS or _MEASURE"
 #endif

@@ -269,6 +269,39 @@ struct MeshArgs {
 };
 // the kernel of a mesh launch (RenderUnit::mesh, launch_mesh_jit: `kind`)
 enum MeshKind { kMeshCount = 0, kMeshEmit = 1, kMeshEmitSharp = 2 };
+// ---- measures (sdf_measure) ------------------------------------------------------
+// The argument block of the measure kernels (measure_kernel.inc measure), their
+// own: `a` carries the prepared scene, nothing else of it is read.  A
+// grid-stride launch of at most kMeasureMaxBlocks one-wave workgroups over the
+// mesh's bricks; each workgroup writes one record to `ws`, the workspace: its
+// rows (1, or SDF_MEASURE_ROWS with owners) of SDF_MEASURE_SLOTS int64, then
+// kMeasureTail int64 (bricks evaluated, bricks in closed form, 0, 0), which
+// measure_reduce (mesh.hip) combines: sums, and min / max for lo / hi.
+// sdf_measure_workspace_bytes() = 8 measure_blocks(nbricks) measure_record(rows).
+constexpr int kMeasureMaxBlocks = 4096;   // 4 waves per SIMD of 256 CUs
+constexpr int kMeasureTail = 4;
+// slots [0, kMeasureSums) of a row are sums, the next three minima, the last three maxima
+constexpr int kMeasureSums = 10;
+constexpr int kMeasureLo = 10, kMeasureHi = 13;
+__host__ __device__ inline long long measure_blocks(long long nbricks) {
+  return nbricks < kMeasureMaxBlocks ? nbricks : kMeasureMaxBlocks;
+}
+__host__ __device__ constexpr int measure_rows(bool owners) { return owners ? SDF_MEASURE_ROWS : 1; }
+__host__ __device__ constexpr int measure_record(int rows) {
+  return rows * SDF_MEASURE_SLOTS + kMeasureTail;
+}
+struct MeasureArgs {
+  KernelArgs a;   // first: the scene evaluators read it at the start of the segment
+  float origin[3], cell[3];
+  int32_t n[3];        // cells (samples) per axis, <= 65536
+  int32_t nb[3];       // bricks per axis, ceil(n / 8)
+  float iso;
+  float skip;          // MeshArgs::skip, the same bound (+INF: every brick is evaluated)
+  long long nbricks;
+  long long* ws;       // measure_blocks(nbricks) records
+  int32_t owners;      // SDF_MEASURE_OWNERS: the launch is of the kernel with the owner rows
+  int32_t reserved;
+};
 // ---- gradients (sdf_sample_grad) ------------------------------------------------
 // The argument block of the gradient kernel (grad_kernel.inc sample_grad), its
 // own: `a` carries the prepared scene, nothing else of it is read.  A grid-stride
@@ -342,6 +375,7 @@ static_assert(sizeof(RaysArgs) <= 4096, "RaysArgs exceeds the 4 KiB kernel-argum
 static_assert(sizeof(PointsArgs) <= 4096, "PointsArgs exceeds the 4 KiB kernel-argument limit");
 static_assert(sizeof(MeshArgs) <= 4096, "MeshArgs exceeds the 4 KiB kernel-argument limit");
 static_assert(sizeof(GradArgs) <= 4096, "GradArgs exceeds the 4 KiB kernel-argument limit");
+static_assert(sizeof(MeasureArgs) <= 4096, "MeasureArgs exceeds the 4 KiB kernel-argument limit");
 // Tiles a wave takes per queue request, queues per launch (workgroup b uses
 // queue b % queues, i.e. one per XCD), and the queues' spacing in uint32s:
 // requests on one address serialise at the memory-side atomic unit, so the

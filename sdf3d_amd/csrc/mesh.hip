@@ -5,6 +5,11 @@
 // of those sums (it also writes the totals), the offsets inside each chunk.
 // Everything is summed in a fixed order in 64-bit integers: no atomics, the
 // same offsets on every run.
+//
+// And the second half of sdf_measure ("Measures"): measure_reduce combines the
+// records the measure kernel's workgroups wrote (kernel_args.h MeasureArgs) into
+// the call's `moments` and `counts` -- sums, and min / max for lo / hi.  Integers:
+// any order gives the same bits.
 #include <hip/hip_runtime.h>
 
 #include "host_api.h"   // this unit's launcher prototypes (and kernel_args.h)
@@ -95,7 +100,67 @@ __global__ __launch_bounds__(kMeshScanChunk) void mesh_scan_offsets(const MeshBr
   }
 }
 
+// Workgroup g < rows: row g of every record into moments[16 g ..]; workgroup
+// `rows`: the records' tails into counts.  Thread = (segment, slot): 64
+// segments of interleaved records, four independent loads in flight per thread
+// (a thread's loads are otherwise one dependent chain: with 16 segments over
+// 4,096 records the combination took longer than the measure kernel at 128^3
+// cells), combined through LDS.
+constexpr int kMeasureReduceSegs = 64;
+constexpr int kMeasureReduceUnroll = 4;
+__device__ __forceinline__ long long measure_reduce_op(bool lo, bool hi, long long v, long long x) {
+  return lo ? (x < v ? x : v) : hi ? (x > v ? x : v) : v + x;
+}
+__global__ __launch_bounds__(kMeasureReduceSegs * SDF_MEASURE_SLOTS) void measure_reduce(
+    const long long* ws, int nblocks, int rows, long long nbricks, long long* moments,
+    long long* counts) {
+  __shared__ long long part[kMeasureReduceSegs * SDF_MEASURE_SLOTS];
+  const int slot = threadIdx.x % SDF_MEASURE_SLOTS, seg = threadIdx.x / SDF_MEASURE_SLOTS;
+  const int g = blockIdx.x;
+  const bool tail = g == rows;
+  const int rec = measure_record(rows);
+  const bool lo = !tail && slot >= kMeasureLo && slot < kMeasureHi;
+  const bool hi = !tail && slot >= kMeasureHi;
+  const bool live = !tail || slot < kMeasureTail;
+  const long long big = 0x7fffffffffffffffll;
+  const long long unit = lo ? big : hi ? -big : 0;
+  long long v = unit;
+  if (live) {
+    const long long* const p = ws + (size_t)g * SDF_MEASURE_SLOTS + slot;
+    long long a[kMeasureReduceUnroll];
+#pragma unroll
+    for (int u = 0; u < kMeasureReduceUnroll; u++) a[u] = unit;
+    for (int b = seg; b < nblocks; b += kMeasureReduceUnroll * kMeasureReduceSegs) {
+#pragma unroll
+      for (int u = 0; u < kMeasureReduceUnroll; u++) {
+        const int bb = b + u * kMeasureReduceSegs;
+        if (bb < nblocks) a[u] = measure_reduce_op(lo, hi, a[u], p[(size_t)bb * rec]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kMeasureReduceUnroll; u++) v = measure_reduce_op(lo, hi, v, a[u]);
+  }
+  part[threadIdx.x] = v;
+  __syncthreads();
+  if (seg != 0 || !live) return;
+  for (int k = 1; k < kMeasureReduceSegs; k++)
+    v = measure_reduce_op(lo, hi, v, part[k * SDF_MEASURE_SLOTS + slot]);
+  if (!tail) moments[(size_t)g * SDF_MEASURE_SLOTS + slot] = v;
+  else counts[slot] = slot < 2 ? v : slot == 2 ? nbricks : 0;
+}
+
 }  // namespace
+
+int launch_measure_reduce(const long long* ws, int nblocks, int rows, long long nbricks,
+                          long long* moments, long long* counts, void* stream) {
+  if (!ws || !moments || !counts || nblocks <= 0 || nblocks > kMeasureMaxBlocks ||
+      (rows != 1 && rows != SDF_MEASURE_ROWS))
+    return (int)hipErrorInvalidValue;
+  (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
+  hipLaunchKernelGGL(measure_reduce, dim3(rows + 1), dim3(kMeasureReduceSegs * SDF_MEASURE_SLOTS), 0,
+                     (hipStream_t)stream, ws, nblocks, rows, nbricks, moments, counts);
+  return (int)hipGetLastError();
+}
 
 int launch_mesh_scan(unsigned char* ws, long long nbricks, long long* counts, void* stream) {
   if (!ws || !counts || nbricks <= 0) return (int)hipErrorInvalidValue;

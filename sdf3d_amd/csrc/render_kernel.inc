@@ -110,6 +110,7 @@ namespace SDF_NS {
 #include "grad_kernel.inc"      // sdf_sample_grad
 #endif
 #include "mesh_kernel.inc"      // sdf_mesh_count, sdf_mesh_emit, sdf_mesh_emit_sharp
+#include "measure_kernel.inc"   // sdf_measure
 #include "rays_kernel.inc"      // sdf_render_rays, sdf_camera_rays
 #include "points_kernel.inc"    // sdf_shade_points
 #ifdef SDF_JIT_SIGNATURE
@@ -121,6 +122,7 @@ namespace SDF_NS {
 #undef SDF_RENDER_KERNEL
 #undef SDF_QUERY_KERNEL
 #undef SDF_MESH_KERNEL
+#undef SDF_MEASURE_KERNEL
 #undef SDF_RAYS_KERNEL
 #undef SDF_POINTS_KERNEL
 #undef scene_sdf

@@ -180,6 +180,25 @@ static int launch_mesh(const MeshArgs& m, int variant, void* stream, int kind) {
   });
 }
 
+// one launch of scene kernel S for sdf_measure: grid-stride, one wave per
+// workgroup, under the family's contract (host_api.h measure_args_fit); the
+// kernel with the owner rows when the arguments ask for them
+template <class S>
+static int launch_measure_scene(const MeasureArgs& m, hipStream_t s) {
+  if (!measure_args_fit(m)) return (int)hipErrorInvalidValue;
+  const dim3 block(64), grid = measure_grid(m);
+  (void)hipGetLastError();  // a stale error of an earlier call is not this launch's
+  if (m.owners) hipLaunchKernelGGL((SDF_NS::measure<S, true>), grid, block, 0, s, m);
+  else hipLaunchKernelGGL((SDF_NS::measure<S, false>), grid, block, 0, s, m);
+  return (int)hipGetLastError();
+}
+
+static int launch_measure(const MeasureArgs& m, int variant, void* stream) {
+  return with_scene(variant, [&](auto scene) {
+    return launch_measure_scene<typename decltype(scene)::type>(m, (hipStream_t)stream);
+  });
+}
+
 #if !SDF_TU_BULB
 // sdf_sample_grad: the grid-stride gradient kernel, then the sum of its rows
 // into `grad_prims` (device, kGradSlots floats) when it and g.rows are set.
@@ -299,13 +318,15 @@ static int launch_frames(const FramesArgs& a, int variant, void* stream, int nbl
 #if SDF_TU_BULB
 const RenderUnit& bulb_unit() {
   static const RenderUnit u = {launch_render, launch_frames, launch_query, launch_rays,
-                               launch_mesh,   launch_points, nullptr,      nullptr};
+                               launch_mesh,   launch_points, launch_measure, nullptr,
+                               nullptr};
   return u;
 }
 #else
 const RenderUnit& unit() {
   static const RenderUnit u = {launch_render, launch_frames, launch_query,       launch_rays,
-                               launch_mesh,   launch_points, launch_camera_rays, launch_grad};
+                               launch_mesh,   launch_points, launch_measure,
+                               launch_camera_rays, launch_grad};
   return u;
 }
 #endif

@@ -1521,6 +1521,76 @@ int sdf_mesh_emit(const sdf_scene* scene, const sdf_params* params, const sdf_gr
   return sdf_mesh_emit_sharp(scene, params, grid, nullptr, workspace, workspace_bytes, out, stream);
 }
 
+// ---- measures (sdf_abi.h "Measures") ---------------------------------------------
+namespace {
+// scene, params, grid and flags of a measure call: a mesh's checks, then its own
+int validate_measure(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
+                     int32_t flags, int64_t* nbricks) {
+  const int rc = validate_mesh(scene, params, grid, nbricks);
+  if (rc != SDF_OK) return rc;
+  for (int c = 0; c < 3; ++c)
+    if (grid->n[c] > 65536) return SDF_E_INVALID_ARG;
+  return (flags & ~SDF_MEASURE_OWNERS) ? SDF_E_INVALID_ARG : SDF_OK;
+}
+int64_t measure_workspace(int64_t nbricks, int32_t flags) {
+  const int rows = sdf::measure_rows((flags & SDF_MEASURE_OWNERS) != 0);
+  return sdf::measure_blocks(nbricks) * int64_t(sdf::measure_record(rows)) * int64_t(sizeof(int64_t));
+}
+}  // namespace
+
+int sdf_validate_measure(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
+                         int32_t flags) {
+  return validate_measure(scene, params, grid, flags, nullptr);
+}
+
+int64_t sdf_measure_workspace_bytes(const sdf_grid* grid, int32_t flags) {
+  int64_t nbricks = 0;
+  const int rc = validate_grid(grid, &nbricks);
+  if (rc != SDF_OK) return rc;
+  for (int c = 0; c < 3; ++c)
+    if (grid->n[c] > 65536) return SDF_E_INVALID_ARG;
+  if (flags & ~SDF_MEASURE_OWNERS) return SDF_E_INVALID_ARG;
+  return measure_workspace(nbricks, flags);
+}
+
+// One validated measure: the scene's plan with the grid, the measure kernel of
+// the flags over the bricks, then the combination of its workgroups' records.
+int sdf_measure(const sdf_scene* scene, const sdf_params* params, const sdf_grid* grid,
+                int32_t flags, void* workspace, int64_t workspace_bytes, int64_t* moments,
+                int64_t* counts, void* stream) {
+  int64_t nbricks = 0;
+  const int rc = validate_measure(scene, params, grid, flags, &nbricks);
+  if (rc != SDF_OK) return rc;
+  if (!moments || !counts) return SDF_E_INVALID_ARG;
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0 ||
+      workspace_bytes < measure_workspace(nbricks, flags))
+    return SDF_E_INVALID_ARG;
+  std::unique_ptr<sdf::RenderPlan> plan(new sdf::RenderPlan());
+  const int prc = scene_plan(scene, nullptr, query_params(*params, false), plan.get());
+  if (prc != SDF_OK) return prc;
+  std::unique_ptr<sdf::MeasureArgs> m(new sdf::MeasureArgs());
+  m->a = plan->a;
+  for (int i = 0; i < 3; ++i) {
+    m->origin[i] = grid->origin[i];
+    m->cell[i] = grid->cell[i];
+    m->n[i] = grid->n[i];
+    m->nb[i] = (grid->n[i] + 7) / 8;
+  }
+  m->iso = grid->iso;
+  m->skip = mesh_skip_bound(*scene, *grid);
+  m->nbricks = nbricks;
+  m->ws = static_cast<long long*>(workspace);
+  m->owners = flags & SDF_MEASURE_OWNERS;
+  m->reserved = 0;
+  const int lrc = sdf::launch_planned(*plan, sdf::launch_measure_jit, &sdf::RenderUnit::measure, *m,
+                                      stream);
+  if (lrc != SDF_OK) return lrc;
+  const int err = sdf::launch_measure_reduce(m->ws, (int)sdf::measure_blocks(nbricks),
+                                             sdf::measure_rows(m->owners != 0), nbricks,
+                                             (long long*)moments, (long long*)counts, stream);
+  return err == hipSuccess ? SDF_OK : SDF_E_HIP;
+}
+
 // ---- gradients (sdf_abi.h "Gradients") -----------------------------------------
 static_assert(sizeof(sdf_grad_out) == 24, "sdf_grad_out layout");
 namespace {

@@ -13,6 +13,7 @@ import math
 from typing import NamedTuple
 
 from . import abi
+from .measure import Measure
 from .scenes import Frame
 
 
@@ -536,6 +537,40 @@ class Renderer:
             if stream is not None:
                 stream.synchronize()   # the workspace is released on return
         return Mesh(verts, tris, nrm, own, (nv, nt, evaluated, bricks))
+
+    # ---- measures (sdf_abi.h "Measures") --------------------------------------
+    def measure(self, frame: Frame, origin, cell, n, iso: float = 0.0, owners: bool = False,
+                dense: bool = False, stream=None) -> Measure:
+        """Volume, centroid, inertia and bounds of the solid ``f(p) < iso`` of
+        ``frame.scene`` inside the grid of `n` cells of size `cell` from `origin`,
+        one sample per cell centre (sdf_measure).  Returns a
+        ``sdf3d_amd.measure.Measure`` of the call's integer rows and counts: row
+        0 the whole solid, with `owners` a row per owning primitive besides (for
+        ``select`` and per-primitive densities).  `dense` evaluates every brick
+        (SDF_MESH_DENSE); the rows are the same either way.  The host waits for
+        the rows."""
+        torch = self.torch
+        g = grid(origin, cell, n, iso, dense)
+        flags = abi.MEASURE_OWNERS if owners else 0
+        abi.check(self.lib.sdf_validate_measure(C.byref(frame.scene), C.byref(frame.params),
+                                                C.byref(g), flags), "sdf_validate_measure")
+        nbytes = int(self.lib.sdf_measure_workspace_bytes(C.byref(g), flags))
+        if nbytes < 0:
+            abi.check(nbytes, "sdf_measure_workspace_bytes")
+        rows = abi.MEASURE_ROWS if owners else 1
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+        moments = torch.empty((rows, abi.MEASURE_SLOTS), dtype=torch.int64, device=self.device)
+        counts = torch.empty((4,), dtype=torch.int64, device=self.device)
+        with self._on_device():
+            rc = self.lib.sdf_measure(C.byref(frame.scene), C.byref(frame.params), C.byref(g), flags,
+                                      C.c_void_p(ws.data_ptr()), nbytes,
+                                      C.c_void_p(moments.data_ptr()),
+                                      C.c_void_p(counts.data_ptr()), self._stream(stream))
+            abi.check(rc, "sdf_measure")
+            if stream is not None:
+                stream.synchronize()   # the copies below run on the current stream
+            return Measure(moments.cpu().numpy(), counts.cpu().tolist(), tuple(g.origin),
+                           tuple(g.cell), tuple(g.n))
 
     # ---- caller-supplied rays (sdf_abi.h "Rays") ----------------------------
     def render_rays(self, frame: Frame, origins, dirs, unit: bool = False, out=None,
